@@ -13,11 +13,16 @@ waveform -> [all-reduce over ranks] -> sign step -> projection, plus the per-ste
 read-back the reference does (train.py:146-153), pipelined one step behind so it stays off the critical path.
 Weak scaling: the per-GPU batch is fixed, `value` counts 32-clip steps over ALL ranks per second.
 
-Two arithmetic modes are timed in the same invocation, W warm-up + exactly K timed steps each:
-  * fp32-parity (split-bf16, three MFMA passes) — the HEADLINE (`value`, `dtype`, `roofline`): the reference computes in
-    float32 and this is the mode that reproduces its sign(grad) on the goldens (tests/test_gpu_model.py);
-  * bf16 — reported beside it in the `bf16` block with its own roofline and its MEASURED disagreement with the
-    fp32-parity gradient on this very batch (sign-flip rate, cosine).
+A plain run times the HEADLINE mode only, W warm-up + exactly K timed steps, replayed from captured hipGraphs (--eager: launched):
+fp32-parity (split-bf16, three MFMA passes; `value`, `dtype`): the reference computes in float32 and this is the mode that
+reproduces its sign(grad) on the goldens (tests/test_gpu_model.py).  `--dump-outputs DIR` writes what the last timed step
+returned (perturbation, gradient, loss, logits, greedy ids) as DIR/<name>.npy.
+
+--full adds everything else, as one run:
+  * bf16 — timed the same way and reported beside the headline in the `bf16` block with its own roofline and its MEASURED
+    disagreement with the fp32-parity gradient on this very batch (sign-flip rate, cosine);
+  * `roofline` (HIP events around every GEMM of the last timed step, HBM traffic from two rocprofv3 --pmc child passes),
+    `roofline_fft` (tools/proj_bench.py) and `cpu_baseline` (the oracle on a bounded sample).
 """
 from __future__ import annotations
 
@@ -51,7 +56,13 @@ def parse():
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--arch", default="base", choices=["base", "large-lv60", "tiny"])
-    ap.add_argument("--modes", default="fp32,bf16", help="comma list of fp32 (= fp32-parity, split-bf16) and bf16; the FIRST is the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also time bf16 and measure roofline, HBM traffic, roofline_fft and cpu_baseline; the --no_* / --prof_steps / "
+                         "--pmc_json / --cpu_* options below act in this mode only")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write the headline mode's last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--modes", default=None,
+                    help="comma list of fp32 (= fp32-parity, split-bf16) and bf16; the FIRST is the headline (default: fp32, with --full fp32,bf16)")
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"], help="time only this mode (same as --modes X)")
     ap.add_argument("--norm_type", default="snr")
     ap.add_argument("--snr_db", type=float, default=40.0)
@@ -72,7 +83,10 @@ def parse():
                     help="skip the live HBM-traffic measurement (two short rocprofv3 --pmc child runs of the headline mode BEFORE this process "
                          "touches the GPU; N = 1 only); roofline.traffic is then null unless --pmc_json is given")
     ap.add_argument("--no_fft_bench", action="store_true", help="skip the FFT / projection path timing (roofline_fft block)")
-    return ap.parse_args()
+    ar = ap.parse_args()
+    if ar.steps < 1 or ar.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return ar
 
 
 def live_pmc(ar, mode):
@@ -100,7 +114,7 @@ def live_pmc(ar, mode):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK",
                                                             "LOCAL_WORLD_SIZE", "ROLE_RANK", "ROLE_WORLD_SIZE", "TORCHELASTIC_RUN_ID")}
     env["TMPDIR"] = "/tmp"
-    child = [sys.executable, os.path.abspath(__file__), "--dtype", mode, "--steps", "2", "--warmup", "1", "--eager", "--no_cpu_baseline",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--dtype", mode, "--steps", "2", "--warmup", "1", "--eager", "--no_cpu_baseline",
              "--no_fft_bench", "--no_prof", "--no_pmc", "--batch", str(ar.batch), "--seconds", str(ar.seconds), "--arch", ar.arch,
              "--norm_type", ar.norm_type, "--snr_db", str(ar.snr_db), "--label_tokens", str(ar.label_tokens)]
     tot, cnt = {}, {}
@@ -183,6 +197,21 @@ def make_transcript(i: int, n_chars: int, seed: int) -> str:
     return s[:n_chars].rstrip().ljust(n_chars, "a")
 
 
+DUMP_MAX_ELEMS = 3 << 20      # 12 MB of float32 per array: the five arrays stay under 64 MB together
+
+
+def dump_outputs(d, arrays):
+    """{name: tensor} -> d/<name>.npy as float32.  An array of more than DUMP_MAX_ELEMS elements is replaced by a fixed sample of
+    its flattened elements (seeded, sorted indices), the same sample in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy().astype(np.float32)
+        if x.size > DUMP_MAX_ELEMS:
+            x = x.ravel()[np.sort(np.random.default_rng(0).choice(x.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(d, f"{name}.npy"), x)
+
+
 def cpu_baseline(a, args_ns, L, batch, label_tokens, seed, steps, weight_grads):
     """The oracle's PGD step (torch CPU, float32, all host cores) on a bounded sample of the same workload: one warm-up
     step, then `steps` timed ones.  weight_grads: keep the model parameters' requires_grad as the reference does
@@ -215,6 +244,8 @@ def main():
     ar = parse()
     if ar.dtype:
         ar.modes = ar.dtype
+    elif ar.modes is None:
+        ar.modes = "fp32,bf16" if ar.full else "fp32"
     modes = [m for m in ar.modes.split(",") if m]
     for m in modes:
         if m not in ("fp32", "bf16"):
@@ -222,7 +253,7 @@ def main():
     if "WORLD_SIZE" not in os.environ and ar.gpus > 1:
         sys.exit(spawn_ranks(ar.gpus))
     live_traffic, live_note = None, "not measured (N > 1, --no_pmc or --no_prof)"
-    if ar.gpus == 1 and os.environ.get("WORLD_SIZE", "1") == "1" and not ar.no_pmc and not ar.no_prof and not ar.pmc_json:
+    if ar.full and ar.gpus == 1 and os.environ.get("WORLD_SIZE", "1") == "1" and not ar.no_pmc and not ar.no_prof and not ar.pmc_json:
         live_traffic, live_note = live_pmc(ar, modes[0])          # child processes; this one has not touched the GPU yet
         if live_traffic is None:
             sys.stderr.write(f"[bench] roofline.traffic stays null: {live_note}\n")
@@ -302,7 +333,7 @@ def main():
         st_host = [torch.empty(8).pin_memory() for _ in range(2)]
         done = [torch.cuda.Event() for _ in range(2)]
         book = {"loss": [], "wer": [], "wer_global": []}
-        no_prof = ar.no_prof
+        no_prof = ar.no_prof or not ar.full
         graphs = None
         if not ar.eager:
             graphs = [stepper.capture(p, cleans[j], labels[j], logits_out=logits_buf[j % 2]) for j in range(NB)]
@@ -311,6 +342,7 @@ def main():
         n_prof = 0 if (no_prof or rank != 0) else (ar.steps if ar.prof_steps <= 0 else min(ar.prof_steps, ar.steps))
         prof_from = ar.warmup + ar.steps - n_prof
         replayed = [0]
+        last = {}
 
         def launch(i):
             k = i % 2
@@ -325,6 +357,7 @@ def main():
             ids_host[k].copy_(ids_dev[k], non_blocking=True)
             st_host[k].copy_(stepper.stats, non_blocking=True)
             done[k].record()
+            last.update(r=r, k=k)
 
         def collect(i):
             """Host side of train.py:146-153 for step i: loss value + WER of the greedy decode vs ground truth."""
@@ -366,6 +399,10 @@ def main():
         if world > 1:
             torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax[0])
+        if ar.dump_outputs and rank == 0 and dtype == modes[0]:
+            r = last["r"]
+            dump_outputs(ar.dump_outputs, {"perturbation": p, "grad": stepper.grad, "loss": r["loss"].reshape(1), "logits": r["logits"],
+                                           "greedy_ids": ids_host[last["k"]]})
 
         passes = 3 if dtype == "fp32" else 1
         roofline = None
@@ -413,10 +450,11 @@ def main():
         if book["wer_global"]:
             res["last_wer_all_ranks"] = book["wer_global"][-1]
         # the gradient of ONE more step from the common starting point, for the cross-mode comparison below
-        pc = p0.clone()
-        stepper.step(pc, cleans[0], labels[0], want_logits=False)
-        torch.cuda.synchronize()
-        res["_grad"] = stepper.grad.detach().clone()
+        if ar.full or len(modes) > 1:
+            pc = p0.clone()
+            stepper.step(pc, cleans[0], labels[0], want_logits=False)
+            torch.cuda.synchronize()
+            res["_grad"] = stepper.grad.detach().clone()
         res["_fl_step"] = fl_step
         return res
 
@@ -460,11 +498,11 @@ def main():
                                                 "(train.py:160-161); measured on this batch from the common starting point"}
             res[m if m != "fp32" else "fp32_parity"] = o
         head.pop("_grad", None)
-        if not ar.no_fft_bench and ar.seconds == 10.0:
+        if ar.full and not ar.no_fft_bench and ar.seconds == 10.0:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import proj_bench
             res["roofline_fft"] = proj_bench.roofline_block(dev)
-        if not ar.no_cpu_baseline and world == 1:
+        if ar.full and not ar.no_cpu_baseline and world == 1:
             nthreads = torch.get_num_threads()
             cb = min(ar.cpu_batch, B)
             ts = cpu_baseline(a, args0, L, cb, ar.label_tokens, 5, ar.cpu_steps, weight_grads=False)

@@ -114,7 +114,7 @@ def test_load_model_from_local_checkpoint(tmp_path, norm, stable):
 
 
 def test_bench_line_contract():
-    """`python bench.py` (tiny shape so that it takes seconds): ONE JSON line on stdout with the driver's contract — metric / value /
+    """`python bench.py --full` (tiny shape so that it takes seconds): ONE JSON line on stdout with the driver's contract — metric / value /
     ms_per_step / n_gpus / scaling / dtype / data / config.workload — plus the `roofline` object measured live by HIP events around the
     GEMM launches and the `cpu_baseline` object (the oracle on a bounded sample, labelled as an extrapolated port); the step is replayed
     from captured hipGraphs except for the sampled step."""
@@ -122,7 +122,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--arch", "tiny", "--steps", "4", "--warmup", "1", "--batch", "2", "--seconds", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--arch", "tiny", "--steps", "4", "--warmup", "1", "--batch", "2", "--seconds", "1",
                         "--label_tokens", "10", "--cpu_batch", "1", "--cpu_steps", "1", "--no_baseline_faithful", "--no_fft_bench"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -144,3 +144,36 @@ def test_bench_line_contract():
     cb = d["cpu_baseline"]
     assert cb["value"] > 0 and cb["cores"] >= 1 and cb["kind"].startswith("port") and "extrapolated" in cb["kind"] and cb["sample"]
     assert "bf16" in d and d["bf16"]["value"] > 0 and "grad_sign_flip_rate" in d["bf16"]["vs_headline_mode"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`python bench.py` without --full: the headline mode only, every timed step replayed from the captured hipGraphs, none of the
+    blocks --full adds.  --dump-outputs writes what the last timed step returned as float32 .npy files, and a second run with the
+    same arguments writes the same arrays (the inputs are seeded), so that two builds can be compared output for output."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    B, L = 2, 16000
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--arch", "tiny", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                            "--seconds", "1", "--label_tokens", "10", "--dump-outputs", str(d)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["metric"] == "pgd_steps_per_sec" and line["steps"] == 3 and line["warmup"] == 1 and line["higher_is_better"] is True
+        assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] / 1e3 - 1.0) < 1e-3 and line["dtype"].startswith("bf16x3")
+        assert line["config"]["hip_graph_replayed_steps"] == 3 and line["roofline"] is None
+        assert not {"bf16", "cpu_baseline", "roofline_fft"} & set(line), sorted(line)
+        out = {n: np.load(d / f"{n}.npy") for n in ("perturbation", "grad", "loss", "logits", "greedy_ids")}
+        assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in out.values())
+        assert out["perturbation"].shape == (1, L) and out["grad"].shape == (1, L) and float(np.abs(out["grad"]).max()) > 0
+        assert out["logits"].ndim == 3 and out["logits"].shape[0] == B and out["greedy_ids"].shape == out["logits"].shape[:2]
+        assert out["loss"].shape == (1,) and out["loss"][0] == np.float32(line["config"]["last_loss"])
+        dumps.append(out)
+    for n, x in dumps[0].items():
+        assert np.array_equal(x, dumps[1][n]), n

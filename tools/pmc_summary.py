@@ -1,10 +1,10 @@
 """Summarise two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py` into HBM bytes per kernel launch, next to the
 ALGORITHMIC bytes per launch that the same bench run computed from the GEMM descriptors.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o runc -- python3 bench.py --dtype fp32 --steps 2 --warmup 1 --no_cpu_baseline --no_fft_bench --no_prof
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -o runc -- python3 bench.py --dtype fp32 --steps 2 --warmup 1 --no_cpu_baseline --no_fft_bench --no_prof
-    python bench.py --dtype fp32 --steps 5 --no_cpu_baseline --no_fft_bench > bench_fp32.json          # carries all_gemm_variants[*].algorithmic_MB_per_launch
-    python tools/pmc_summary.py gpurun_out/pmc_fetch gpurun_out/pmc_write 4 fp32 bench_fp32.json > profiles/<round>_hbm_traffic_pmc_fp32.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT/pmc_fetch -o runc -- python3 bench.py --full --dtype fp32 --steps 2 --warmup 1 --no_cpu_baseline --no_fft_bench --no_prof
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d OUT/pmc_write -o runc -- python3 bench.py --full --dtype fp32 --steps 2 --warmup 1 --no_cpu_baseline --no_fft_bench --no_prof
+    python bench.py --full --dtype fp32 --steps 5 --no_cpu_baseline --no_fft_bench > bench_fp32.json          # carries all_gemm_variants[*].algorithmic_MB_per_launch
+    python tools/pmc_summary.py OUT/pmc_fetch OUT/pmc_write 4 fp32 bench_fp32.json > profiles/<round>_hbm_traffic_pmc_fp32.json
 
 Units and corrections follow /opt/skills/guides/MI355X_MICROARCH.md (HBM / rocprofv3): both counters are in KB (x1024), and
 FETCH_SIZE under-reports by 2x on gfx950 (doubled here).  The third argument is the number of steps the run executed

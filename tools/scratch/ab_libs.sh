@@ -9,7 +9,7 @@ for round in 1 2; do
   for spec in "$@"; do
     name=${spec%%=*}; path=${spec#*=}
     cp $path $L
-    timeout -k 10 200 python bench.py --dtype fp32 --steps 40 --warmup 5 --no_cpu_baseline --no_fft_bench --no_pmc 2>/dev/null | python3 -c "
+    timeout -k 10 200 python bench.py --full --dtype fp32 --steps 40 --warmup 5 --no_cpu_baseline --no_fft_bench --no_pmc 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$name', d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'])"
   done

@@ -1,6 +1,6 @@
 """Per-launch durations of ONE PGD step from a rocprofv3 kernel trace (the last step of the run), in launch order:
 
-    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d OUT -o runc -- python3 bench.py --dtype fp32 --steps 2 --warmup 1 --eager --no_cpu_baseline --no_fft_bench --no_prof
+    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d OUT -o runc -- python3 bench.py --full --dtype fp32 --steps 2 --warmup 1 --eager --no_cpu_baseline --no_fft_bench --no_prof
     python tools/step_trace.py OUT > step_trace.txt
 
 Columns: start (us, relative to the step's first kernel), duration (us), grid, kernel name."""
