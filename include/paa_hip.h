@@ -110,6 +110,23 @@ paa_status paa_istft(paa_proj* h, const float* d_S, int B, int T, float* d_out, 
 
 /* train.py:160-161  p += lr * sign(grad). */
 paa_status paa_sign_step(float* d_p, const float* d_grad, float lr, int L, void* stream);
+/* train.py:165-175 with torch.optim.Adam(lr) as build.py:352-359 builds it (foreach, capturable=False,
+ * weight_decay 0, amsgrad / maximize off), in the order of torch/optim/adam.py _multi_tensor_adam, per element i < L:
+ *   g = grad_sign * d_grad[i]
+ *   m = lerp(m, g, w1)                  w1 = (float)(1 - beta1); ATen/native/Lerp.h: |w1| < 0.5 ? fma(w1, g - m, m)
+ *                                                                 : fma(-(g - m), 1 - w1, g)
+ *   v = v * beta2;  v = fma(omb2, g * g, v)                       omb2 = (float)(1 - beta2)   (_foreach_addcmul_)
+ *   d = sqrt(v) / d_scal[1];  d = d + eps
+ *   p = fma(d_scal[0], m / d, p)                                  (_foreach_addcdiv_)
+ *   d_grad_out[i] = g                   (d_grad_out may be NULL)
+ * The three FMAs are the contractions torch's own gfx950 foreach kernels execute; sqrt and division are IEEE-rounded,
+ * so the result equals torch.optim.Adam fed the same gradient, bit for bit.
+ * d_scal: device [2] = { -lr / (1 - beta1^t), sqrt(1 - beta2^t) }, computed on the host in double as
+ * _multi_tensor_adam does and rounded to f32.  Read from device memory so that a captured graph picks up the new
+ * step count and a StepLR-changed lr on every replay.  Stream-ordered, allocates nothing, capturable. */
+paa_status paa_adam_step(float* d_p, const float* d_grad, float grad_sign, float* d_exp_avg, float* d_exp_avg_sq,
+                         const float* d_scal, float w1, float beta2, float omb2, float eps, float* d_grad_out, int L,
+                         void* stream);
 /* core/projections.py:37-39 project_linf(p, min_val, max_val): in-place clamp of n floats to [lo, hi]. */
 paa_status paa_clamp(float* d_p, int64_t n, float lo, float hi, void* stream);
 /* train.py:136  out = clamp(clean + p, -1, 1), p broadcast over the batch. */

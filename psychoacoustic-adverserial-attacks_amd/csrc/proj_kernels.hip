@@ -365,6 +365,61 @@ __global__ void k_sign_step(float* __restrict__ p, const float* __restrict__ g, 
     p[i] = p[i] + lr * s;
 }
 
+// train.py:165-175 with torch.optim.Adam(lr) as build.py:352-359 builds it: one element of torch's foreach Adam step
+// (torch/optim/adam.py _multi_tensor_adam, non-capturable; see paa_adam_step in include/paa_hip.h).  Every rounding is
+// spelled out: contraction is off, and the three FMAs are the ones torch's gfx950 foreach kernels execute (lerp, addcmul,
+// addcdiv each compile to one v_fma_f32 / v_pk_fma_f32 there); the sqrt and the two divisions are IEEE-rounded, as there.
+struct AdamScal {
+    float step_size, bc2_sqrt, w1, beta2, omb2, eps, grad_sign;
+};
+
+__device__ __forceinline__ void adam_elem(float& p, float gin, float& m, float& v, float& gout, const AdamScal& s) {
+#pragma clang fp contract(off)
+    const float g = s.grad_sign * gin;
+    const float diff = g - m;                                            // ATen/native/Lerp.h
+    m = (fabsf(s.w1) < 0.5f) ? __builtin_fmaf(s.w1, diff, m) : __builtin_fmaf(-diff, 1.f - s.w1, g);
+    v = v * s.beta2;                                                     // _foreach_mul_
+    v = __builtin_fmaf(s.omb2, g * g, v);                                // _foreach_addcmul_
+    float d = sqrtf(v) / s.bc2_sqrt;                                     // _foreach_sqrt, _foreach_div_
+    d = d + s.eps;                                                       // _foreach_add_
+    p = __builtin_fmaf(s.step_size, m / d, p);                           // _foreach_addcdiv_
+    gout = g;
+}
+
+// Streaming: one float4 of each operand per thread, the L % 4 tail by the first threads of block 0.  The vector path
+// needs every pointer 16-byte aligned; otherwise the whole vector is done element by element.
+__global__ void k_adam_step(float* __restrict__ p, const float* __restrict__ grad, float grad_sign, float* __restrict__ m,
+                            float* __restrict__ v, const float* __restrict__ scal, float w1, float beta2, float omb2, float eps,
+                            float* __restrict__ gout, int n, int vec) {
+    const AdamScal s{scal[0], scal[1], w1, beta2, omb2, eps, grad_sign};
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n4 = vec ? (n >> 2) : 0;
+    if (i < n4) {
+        float4 pp = reinterpret_cast<const float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(grad)[i];
+        float4 mm = reinterpret_cast<const float4*>(m)[i];
+        float4 vv = reinterpret_cast<const float4*>(v)[i];
+        float4 go;
+        adam_elem(pp.x, gg.x, mm.x, vv.x, go.x, s);
+        adam_elem(pp.y, gg.y, mm.y, vv.y, go.y, s);
+        adam_elem(pp.z, gg.z, mm.z, vv.z, go.z, s);
+        adam_elem(pp.w, gg.w, mm.w, vv.w, go.w, s);
+        reinterpret_cast<float4*>(p)[i] = pp;
+        reinterpret_cast<float4*>(m)[i] = mm;
+        reinterpret_cast<float4*>(v)[i] = vv;
+        if (gout) reinterpret_cast<float4*>(gout)[i] = go;
+    }
+    const int j = (n4 << 2) + i;                 // the elements the vector path leaves: at most 3, or all of them
+    if (j < n && (!vec || i < 4)) {
+        float pp = p[j], mm = m[j], vv = v[j], go;
+        adam_elem(pp, grad[j], mm, vv, go, s);
+        p[j] = pp;
+        m[j] = mm;
+        v[j] = vv;
+        if (gout) gout[j] = go;
+    }
+}
+
 __global__ void k_compose_clamp(const float* __restrict__ x, const float* __restrict__ p, float* __restrict__ out,
                                 int B, int L) {
     const int64_t n = (int64_t)B * L;
@@ -751,6 +806,22 @@ extern "C" paa_status paa_batch_stats(paa_proj* h, const float* d_clean, int B, 
 extern "C" paa_status paa_sign_step(float* d_p, const float* d_grad, float lr, int L, void* stream) {
     if (!d_p || !d_grad) PAA_FAIL(PAA_ERR_ARG, "paa_sign_step: null argument");
     hipLaunchKernelGGL(k_sign_step, dim3(cdiv(L, 256)), dim3(256), 0, (hipStream_t)stream, d_p, d_grad, lr, L);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
+extern "C" paa_status paa_adam_step(float* d_p, const float* d_grad, float grad_sign, float* d_exp_avg, float* d_exp_avg_sq,
+                                    const float* d_scal, float w1, float beta2, float omb2, float eps, float* d_grad_out, int L,
+                                    void* stream) {
+    if (!d_p || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_scal) PAA_FAIL(PAA_ERR_ARG, "paa_adam_step: null argument");
+    if (L < 1) PAA_FAIL(PAA_ERR_SIZE, "paa_adam_step: L=%d", L);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_grad) |
+                        reinterpret_cast<uintptr_t>(d_exp_avg) | reinterpret_cast<uintptr_t>(d_exp_avg_sq) |
+                        reinterpret_cast<uintptr_t>(d_grad_out);
+    const int vec = (a & 15) == 0;
+    const int threads = vec ? std::max(L >> 2, 1) : L;
+    hipLaunchKernelGGL(k_adam_step, dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream, d_p, d_grad, grad_sign,
+                       d_exp_avg, d_exp_avg_sq, d_scal, w1, beta2, omb2, eps, d_grad_out, L, vec);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }

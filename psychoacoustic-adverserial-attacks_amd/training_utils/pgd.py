@@ -17,6 +17,12 @@ whole-GLOBAL-batch statistics (projections.py:11-35, 56-66); the SNR target norm
 device — so ranks may hold different numbers of clips, in any step, without a collective of their own.  The WER counters
 are the host-side bookkeeping of the PREVIOUS step (train.py:149-153 runs one step behind the GPU), reduced with the same
 buffer.  The layout of the 8 slots is defined HERE (ST_*) and documented in include/paa_hip.h (paa_model_fwd_bwd, d_stats).
+
+Second update rule (``optimizer=``): torch.optim.Adam as build.py:352-359 creates it (train.py:165-175).  Only the first launch
+after the collective changes (``paa_adam_step`` instead of ``paa_sign_step``); the moments and the step count stay in
+``optimizer.state[p]``, so ``optimizer.state_dict()`` and a later plain ``optimizer.step()`` see the steps taken here.  The
+per-step scalars (-lr / (1 - beta1^t), sqrt(1 - beta2^t)) are computed on the host as torch does and reach the device
+through the same pinned ring as the WER counters, so a captured graph picks up the step count and a StepLR lr on replay.
 """
 from __future__ import annotations
 
@@ -27,12 +33,44 @@ from .. import _lib, runtime
 FREQ_NORMS = ("fletcher_munson", "min_max_freqs", "max_phon")
 N_STATS = 8
 ST_LOSS, ST_SQ, ST_TV, ST_WER_ERR, ST_WER_REF, ST_CLIPS = 0, 1, 2, 3, 4, 5
+RING = 4
+
+
+def adam_unsupported(optimizer):
+    """None if ``optimizer`` is the plain torch.optim.Adam the device step implements (one param group holding one tensor,
+    float hyper-parameters, weight_decay 0, amsgrad / maximize / capturable / differentiable / fused off, the foreach
+    kernels), else the name of the first option it does not cover."""
+    if type(optimizer) is not torch.optim.Adam:
+        return f"optimizer {type(optimizer).__name__}"
+    if len(optimizer.param_groups) != 1 or len(optimizer.param_groups[0]["params"]) != 1:
+        return "more than one parameter"
+    g = optimizer.param_groups[0]
+    if g.get("weight_decay", 0) != 0:
+        return "weight_decay"
+    for k in ("amsgrad", "maximize", "capturable", "differentiable", "fused"):
+        if g.get(k):
+            return k
+    if g.get("foreach") is False:
+        return "foreach=False"
+    if any(isinstance(x, torch.Tensor) for x in (g["lr"], *g["betas"], g["eps"])):
+        return "tensor hyper-parameters"
+    return None
+
+
+def adam_scalars(lr, beta1, beta2, step):
+    """[-lr / (1 - beta1^t), sqrt(1 - beta2^t)] in double, as torch/optim/adam.py _multi_tensor_adam (capturable=False)
+    computes step_size and bias_correction2_sqrt; the foreach kernels round them to f32."""
+    bc1 = 1 - beta1 ** step
+    bc2 = 1 - beta2 ** step
+    return (lr / bc1) * -1, bc2 ** 0.5
 
 
 class PgdStepper:
-    def __init__(self, model, args, length: int, interp=None, spl_thresh=None, group=None, force_collective=False):
+    def __init__(self, model, args, length: int, interp=None, spl_thresh=None, group=None, force_collective=False,
+                 optimizer=None):
         """``force_collective``: run the packed all-reduce (and the global-statistics projection) even with a single rank —
-        the way the one-GPU test box executes the RCCL branch (tests/test_gpu_rccl.py)."""
+        the way the one-GPU test box executes the RCCL branch (tests/test_gpu_rccl.py).  ``optimizer``: a torch.optim.Adam
+        over the perturbation (``adam_unsupported`` is None); the step then applies its update instead of the sign step."""
         self.model, self.args, self.L = model, args, int(length)
         self.dev = model.device
         self.norms = str(args.norm_type).split("+")
@@ -59,9 +97,23 @@ class PgdStepper:
             a = type("A", (), dict(vars(args)))()
             a.norm_type = n
             self._prm.append(runtime.params_of(a))
-        self._wer_ring = [torch.zeros(2, dtype=torch.float32).pin_memory() for _ in range(4)] if self.collective else None
-        self._wer_i = 0
         self._wer_next = (0.0, 0.0)
+        self.optimizer = optimizer
+        if optimizer is not None:
+            why = adam_unsupported(optimizer)
+            if why is not None:
+                raise NotImplementedError(f"the device Adam step does not implement {why}")
+            self.adam_p = optimizer.param_groups[0]["params"][0]
+            if self.adam_p.numel() != self.L:
+                raise ValueError(f"optimizer parameter has {self.adam_p.numel()} elements, expected {self.L}")
+            self.adam_scal = torch.zeros(2, dtype=torch.float32, device=self.dev)
+            self.adam_grad = torch.zeros_like(self.adam_p, dtype=torch.float32, device=self.dev)
+        # host -> device scalars of each step: [wer errors, wer reference words, adam step_size, adam bias_correction2_sqrt].
+        # The copies are asynchronous, so a slot is rewritten only after the event behind its copies has completed.
+        self._ring = [torch.zeros(4, dtype=torch.float32).pin_memory() for _ in range(RING)] \
+            if (self.collective or optimizer is not None) else None
+        self._ring_ev = [None] * RING
+        self._ring_i = 0
 
     # ---- bookkeeping carried by the packed vector -------------------------------------------------------------
     def set_wer_counts(self, errors: float, ref_words: float):
@@ -69,16 +121,50 @@ class PgdStepper:
         gradient, so its all-reduce sums them over ranks; read the global sums from ``stats[3:5]`` afterwards."""
         self._wer_next = (float(errors), float(ref_words))
 
-    def _push_wer(self):
-        """This rank's WER counters of the previous step go behind the gradient (pinned ring: the copy is asynchronous,
-        so a slot must stay untouched until the GPU has consumed it)."""
-        if not self.collective:
+    def adam_consts(self):
+        """(w1, beta2, omb2, eps) of the optimizer's param group as the foreach kernels see them (f32 by value)."""
+        g = self.optimizer.param_groups[0]
+        b1, b2 = g["betas"]
+        return float(1 - b1), float(b2), float(1 - b2), float(g["eps"])
+
+    def _adam_state(self):
+        """optimizer.state[p], created as torch's Adam._init_group does on its first step (non-capturable, non-fused)."""
+        st = self.optimizer.state[self.adam_p]
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0, dtype=torch.float32)
+            st["exp_avg"] = torch.zeros_like(self.adam_p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(self.adam_p, memory_format=torch.preserve_format)
+        return st
+
+    def _pre_step(self, consts=None):
+        """Host side of one step, before its launches (eager step, single-graph replay and _SplitGraph.replay alike): this
+        rank's WER counters of the previous step go behind the gradient, and for Adam the step count is advanced and the
+        step's scalars go to ``adam_scal``.  ``consts``: the (w1, beta2, omb2, eps) a graph captured by value."""
+        if self._ring is None:
             return
-        h = self._wer_ring[self._wer_i & 3]
-        self._wer_i += 1
-        h[0], h[1] = self._wer_next
-        self._wer_next = (0.0, 0.0)
-        self.stats[ST_WER_ERR:ST_WER_REF + 1].copy_(h, non_blocking=True)
+        k = self._ring_i % RING
+        self._ring_i += 1
+        if self._ring_ev[k] is not None:
+            self._ring_ev[k].synchronize()
+        h = self._ring[k]
+        if self.collective:
+            h[0], h[1] = self._wer_next
+            self._wer_next = (0.0, 0.0)
+            self.stats[ST_WER_ERR:ST_WER_REF + 1].copy_(h[0:2], non_blocking=True)
+        if self.optimizer is not None:
+            if consts is not None and self.adam_consts() != consts:
+                raise ValueError("Adam betas / eps changed after capture(); capture the step again")
+            g = self.optimizer.param_groups[0]
+            st = self._adam_state()
+            if self.adam_p.grad is not self.adam_grad:
+                self.adam_p.grad = self.adam_grad
+            st["step"] += 1                                                  # _multi_tensor_adam: steps on the CPU
+            self.optimizer._opt_called = True       # what torch's wrapped optimizer.step() sets for the LR schedulers' order check
+            h[2], h[3] = adam_scalars(g["lr"], g["betas"][0], g["betas"][1], st["step"].item())
+            self.adam_scal.copy_(h[2:4], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        self._ring_ev[k] = ev
 
     # ---- the two halves of a step (everything before / after the collective) ----------------------------------
     def _pre(self, p, clean, labels, want_logits=True, logits_out=None):
@@ -97,7 +183,14 @@ class PgdStepper:
         lib, L, B = _lib.lib(), self.L, clean.shape[0]
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr()
-            _lib.check(lib.paa_sign_step(_lib.ptr(p), _lib.ptr(self.grad), float(self.args.lr), L, st))   # train.py:160-161
+            if self.optimizer is None:
+                _lib.check(lib.paa_sign_step(_lib.ptr(p), _lib.ptr(self.grad), float(self.args.lr), L, st))   # train.py:160-161
+            else:                       # train.py:168-171: Adam minimises -direction * loss, self.grad = d(direction * loss)
+                w1, b2, omb2, eps = self.adam_consts()
+                ast = self._adam_state()
+                _lib.check(lib.paa_adam_step(_lib.ptr(p), _lib.ptr(self.grad), -1.0, _lib.ptr(ast["exp_avg"]),
+                                             _lib.ptr(ast["exp_avg_sq"]), _lib.ptr(self.adam_scal), w1, b2, omb2, eps,
+                                             _lib.ptr(self.adam_grad), L, st))
             for n, prm in zip(self.norms, self._prm):                                                   # train.py:162
                 if self.need_clean_stats and n in ("snr", "tv"):
                     _lib.check(lib.paa_project_ext(self.proj.h, prm, _lib.ptr(p), 1, _lib.ptr(self.stats[ST_SQ:ST_TV + 1]),
@@ -111,7 +204,15 @@ class PgdStepper:
         clean = runtime.as_f32_cuda(clean, "clean_audio")
         if p.numel() != self.L or clean.shape[-1] != self.L:
             raise ValueError(f"Loaded perturbation length {p.numel()} / clip length {clean.shape[-1]} != expected {self.L}")
-        self._push_wer()
+        self._check_p(p)
+        self._pre_step()
+        return self._body(p, clean, labels, want_logits, logits_out)
+
+    def _check_p(self, p):
+        if self.optimizer is not None and p.data_ptr() != self.adam_p.data_ptr():
+            raise ValueError("the Adam step updates the optimizer's own parameter; pass that tensor as p")
+
+    def _body(self, p, clean, labels, want_logits=True, logits_out=None):
         r = self._pre(p, clean, labels, want_logits, logits_out)
         if self.collective:
             torch.distributed.all_reduce(self.packed, op=torch.distributed.ReduceOp.SUM, group=self.group)
@@ -123,8 +224,17 @@ class PgdStepper:
         """Capture one step on fixed buffers into hipGraphs (the launch sequence allocates nothing and never
         synchronises, so it is capturable as is).  Returns (graph, result dict); ``graph.replay()`` re-runs the step
         in place on ``p`` with whatever ``clean`` / ``labels`` currently hold.  With several ranks the halves before
-        and after the collective are two graphs and the all-reduce runs between their replays."""
+        and after the collective are two graphs and the all-reduce runs between their replays.
+
+        With Adam the result is always an object with ``replay()`` (the step's scalars are pushed before each replay), betas
+        and eps are captured by value (``replay()`` raises ValueError once they change), and the warm-up step is undone:
+        ``p``, the optimizer state and the step count are as before the call."""
         lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
+        saved = None
+        if self.optimizer is not None:
+            self._check_p(p)
+            ast = self._adam_state()
+            saved = (p.detach().clone(), ast["exp_avg"].clone(), ast["exp_avg_sq"].clone(), ast["step"].clone())
         if logits_out is None:
             logits_out = torch.empty(clean.shape[0], self.model.frames, self.model.arch.vocab_size, device=self.dev)
         s = torch.cuda.Stream(device=self.dev)
@@ -132,11 +242,19 @@ class PgdStepper:
         with torch.cuda.stream(s):                       # warm-up on the side stream, as torch's capture rules require
             self.step(p, clean, lab, logits_out=logits_out)
         torch.cuda.current_stream(self.dev).wait_stream(s)
+        if saved is not None:
+            torch.cuda.synchronize(self.dev)
+            p.detach().copy_(saved[0])
+            ast["exp_avg"].copy_(saved[1])
+            ast["exp_avg_sq"].copy_(saved[2])
+            ast["step"].copy_(saved[3])
         if not self.collective:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                r = self.step(p, clean, lab, logits_out=logits_out)
-            return g, r
+                r = self._body(p, clean, lab, logits_out=logits_out)
+            if self.optimizer is None:
+                return g, r
+            return _AdamGraph(self, g), r
         # No collective may be in flight while a capture is open (the process group's watchdog thread polls its events), and the
         # captures only guard THIS thread's launches: the RCCL call between them runs eagerly.
         torch.cuda.synchronize(self.dev)
@@ -151,14 +269,27 @@ class PgdStepper:
         return _SplitGraph(self, g1, g2), r
 
 
+class _AdamGraph:
+    """Single-graph Adam step: replay() = host scalars of the step, then the captured launches."""
+
+    def __init__(self, stepper, g):
+        self.stepper, self.g = stepper, g
+        self.consts = stepper.adam_consts()
+
+    def replay(self):
+        self.stepper._pre_step(self.consts)
+        self.g.replay()
+
+
 class _SplitGraph:
     """replay() = pre-collective graph, all-reduce of the packed vector, post-collective graph."""
 
     def __init__(self, stepper, g1, g2):
         self.stepper, self.g1, self.g2 = stepper, g1, g2
+        self.consts = stepper.adam_consts() if stepper.optimizer is not None else None
 
     def replay(self):
-        self.stepper._push_wer()
+        self.stepper._pre_step(self.consts)
         self.g1.replay()
         torch.distributed.all_reduce(self.stepper.packed, op=torch.distributed.ReduceOp.SUM, group=self.stepper.group)
         self.g2.replay()

@@ -13,7 +13,7 @@ import torch
 
 from .. import _lib, runtime
 from ..core import loss_helpers
-from .pgd import FREQ_NORMS, PgdStepper
+from .pgd import FREQ_NORMS, PgdStepper, adam_unsupported
 
 logger = logging.getLogger(__name__)
 
@@ -80,6 +80,19 @@ def perturbation_constraint(p: torch.Tensor, clean_audio, args, interp, spl_thre
     return q if out_len == L else q[..., :out_len]
 
 
+def adam_route(optimizer, world: int) -> str:
+    """Which update the Adam branch runs: "device" (paa_adam_step inside PgdStepper's launch sequence) for the plain
+    torch.optim.Adam build.py:352-359 creates, "eager" (torch's own optimizer.step) for any other optimizer on one rank.
+    With several ranks only the device step exists: NotImplementedError names the option it does not cover."""
+    why = adam_unsupported(optimizer)
+    if why is None:
+        return "device"
+    if world > 1:
+        raise NotImplementedError(f"the data-parallel Adam step does not implement {why}; use the defaults of "
+                                  "torch.optim.Adam(lr=...) or a single rank")
+    return "eager"
+
+
 def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, processor, interp, wer_metric,
                 spl_thresh, optimizer) -> TrainEpochResult:
     """train.py:103-182.  ``model`` is a ``paa_amd.model.PaaModel``."""
@@ -90,12 +103,17 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
     if args.optimizer_type == "adam" and optimizer is None:
         raise ValueError("Adam optimizer selected but optimizer is None")                          # train.py:167
     L = p.shape[-1]
+    world = 1
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        world = torch.distributed.get_world_size()
+    # The eager torch chain stays only for a one-rank run whose optimizer the device step does not implement (weight decay,
+    # AMSGrad, ...): there it is what the reference runs, and the data-parallel machinery has nothing to add.
+    eager_adam = args.optimizer_type == "adam" and adam_route(optimizer, world) == "eager"
+    step_opt = optimizer if args.optimizer_type == "adam" and not eager_adam else None
     stepper = getattr(model, "_stepper", None)
-    if stepper is None or stepper.args is not args or stepper.L != L:
-        stepper = PgdStepper(model, args, L, interp, spl_thresh)
+    if stepper is None or stepper.args is not args or stepper.L != L or stepper.optimizer is not step_opt:
+        stepper = PgdStepper(model, args, L, interp, spl_thresh, optimizer=step_opt)
         model._stepper = stepper
-    if args.optimizer_type == "adam" and stepper.world > 1:
-        raise NotImplementedError("the Adam branch runs on one GPU; the data-parallel step is the PGD branch (SURVEY 8e)")
     for clean_audio, target_texts in train_data_loader:
         t0 = time.perf_counter()
         clean_audio = clean_audio.to(args.device, torch.float32, non_blocking=True).contiguous()   # train.py:129
@@ -104,6 +122,8 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
             if isinstance(p, torch.nn.Parameter) or p.requires_grad:
                 p = p.detach()
             r = stepper.step(p, clean_audio, labels)
+        elif not eager_adam:
+            r = stepper.step(p.data, clean_audio, labels)          # p.grad = -grad, as train.py:170 leaves it
         else:
             if p.dtype != torch.float32 or not p.is_cuda:
                 raise TypeError(f"the Adam branch needs a float32 perturbation on the GPU, got {p.dtype} on {p.device}")
