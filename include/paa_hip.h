@@ -132,6 +132,20 @@ paa_status paa_clamp(float* d_p, int64_t n, float lo, float hi, void* stream);
 /* train.py:136  out = clamp(clean + p, -1, 1), p broadcast over the batch. */
 paa_status paa_compose_clamp(const float* d_clean, const float* d_p, float* d_out, int B, int L, void* stream);
 
+/* ---- per-clip perturbations: one row delta_b per clip b (the per-utterance attack next to the universal one) ----- */
+/* training_utils/train.py:69-99 perturbation_constraint applied to every row on its own: row r of d_src (rows, L) is
+ * projected as perturbation_constraint(src[r][None], clean[r][None], args) projects it — l2 and fletcher_munson from the
+ * row's own norm, snr from clean row r's own mean power (clean.numel() = L), tv from TV(clean[r]); linf, min_max_freqs and
+ * max_phon are row-local already.  d_clean (rows, L) is required for snr / tv (PAA_ERR_NEED_CLEAN as paa_project).  In place
+ * when d_src == d_dst, out of place otherwise (the two must not overlap).  rows = 1 is paa_project_to / paa_project on that
+ * row.  One launch sequence for all rows; the workspace is the one paa_proj_create sized (rows <= max_batch, L <= max_len). */
+paa_status paa_project_rows(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
+                            const float* d_clean, int L, void* stream);
+/* train.py:136 with one perturbation row per clip: out[b] = clamp(clean[b] + p[b], -1, 1); d_p (p_rows, L), p_rows in
+ * {1, B}; p_rows = 1 is paa_compose_clamp. */
+paa_status paa_compose_clamp_rows(const float* d_clean, const float* d_p, int p_rows, float* d_out, int B, int L,
+                                  void* stream);
+
 /* ------------------------------------------------------------------ model context ---------- */
 /* Wav2Vec2ForCTC forward + CTC loss + backward to the waveform (core/loss_helpers.py:12-23 ->
  * transformers modeling_wav2vec2.py:1667-1736; training_utils/train.py:136-158). */
@@ -179,10 +193,22 @@ paa_status paa_model_fwd_bwd(paa_model* m, const float* d_clean, const float* d_
                              int B, int S_max, int direction, float* d_grad, float* d_logits, float* d_stats,
                              void* stream);
 
+/* train.py:136-158 with one perturbation row per clip: d_p is (p_rows, L), p_rows in {1, B}.  p_rows = 1 is exactly
+ * paa_model_fwd_bwd.  p_rows = B: clip b is composed as clamp(clean[b] + d_p[b], -1, 1) and d_grad (B, L) receives
+ * direction * mask_b * dLoss/dperturbed_b in row b — the clip's own gradient (in eval mode clip b's loss depends on
+ * delta_b alone), with no sum over the clips.  d_logits / d_stats as paa_model_fwd_bwd. */
+paa_status paa_model_fwd_bwd_rows(paa_model* m, const float* d_clean, const float* d_p, int p_rows, const int32_t* d_labels,
+                                  int B, int S_max, int direction, float* d_grad, float* d_logits, float* d_stats,
+                                  void* stream);
+
 /* Forward + CTC loss only (core/loss_helpers.py:46-57 get_loss, training_utils/evaluation.py:5-31): clamp = 0 adds p
  * without clamping as the reference's evaluation does (evaluation.py:16); d_p may be NULL (clean evaluation). */
 paa_status paa_model_forward(paa_model* m, const float* d_clean, const float* d_p, int clamp, const int32_t* d_labels,
                              int B, int S_max, float* d_logits, float* d_stats, void* stream);
+/* The same with d_p (p_rows, L), p_rows in {1, B}, one perturbation row per clip when p_rows = B
+ * (training_utils/evaluation.py:5-31 on per-clip perturbations). */
+paa_status paa_model_forward_rows(paa_model* m, const float* d_clean, const float* d_p, int p_rows, int clamp,
+                                  const int32_t* d_labels, int B, int S_max, float* d_logits, float* d_stats, void* stream);
 
 /* core/loss_helpers.py:26,61  pred_ids = torch.argmax(logits, dim=-1): d_logits (rows, V) f32 -> d_ids (rows) int16
  * (first maximum wins; a NaN counts as the maximum, as in torch).  Feeds the host-side greedy CTC decode / WER. */

@@ -1,0 +1,182 @@
+"""Per-clip (per-utterance) attack entry point: every clip of a split gets its own perturbation delta_b, crafted with
+``--pgd_steps`` device steps (training_utils/clip_attack.ClipStepper) under the same constraint sets as the universal
+runner, then evaluated clean and adversarial.
+
+    python -m paa_amd.attack_clips --norm_type snr --snr_db 40 --pgd_steps 20 [--split test] [--data_dir DIR]
+
+Writes ``clip_results.json`` (one record per clip, then the summary means) and int16 wavs of the first
+``--num_items_to_inspect`` adversarial clips into the run directory.  Launched with several ranks (WORLD_SIZE / RANK), the
+clips of every global batch are sharded over the ranks (build.shard_batches), each rank attacks its shard without any
+collective, and one gather after the last batch brings the records to rank 0, which writes the file.
+"""
+from __future__ import annotations
+
+import copy
+import json
+import math
+import os
+import sys
+
+import torch
+
+from .core import iso, loss_helpers
+from .training_utils import build, parser, save
+from .training_utils.clip_attack import ClipStepper, clip_nll, compose_rows, init_rows, project_rows
+
+SPLITS = ("test", "val", "train")
+RECORD_FIELDS = ("index", "clean_wer", "adv_wer", "clean_ctc", "final_ctc", "l2", "linf", "snr_db")
+TARGET_FIELD = "target_wer"
+SUMMARY_FIELDS = ("clean_wer", "adv_wer", "final_ctc", "l2", "linf", "snr_db")
+
+
+def create_arg_parser():
+    p = parser.create_arg_parser()
+    p.add_argument("--pgd_steps", type=int, default=100, help="per-clip attack: device steps per batch")
+    p.add_argument("--split", type=str, choices=list(SPLITS), default="test", help="per-clip attack: the split attacked")
+    return p
+
+
+def clip_batches(batches, rank: int = 0, world: int = 1):
+    """Global batches (x (n, L), texts) of a split -> this rank's shards as (x, texts, global clip indices).  The index of a
+    clip is its position in the split, whatever the batch size or the number of ranks."""
+    tagged, first = [], 0
+    for x, texts in batches:
+        idx = list(range(first, first + len(texts)))
+        first += len(texts)
+        tagged.append((x, list(zip(idx, texts))))
+    out = []
+    for x, pairs in build.shard_batches(tagged, rank, world, keep_empty=True):
+        if len(pairs):
+            out.append((x, [t for _, t in pairs], [i for i, _ in pairs]))
+    return out
+
+
+def split_batches(args, world: int = 1):
+    """The split ``args.split`` of build.create_data_loaders as global batches of ``batch_size * world`` clips, and the
+    clip length."""
+    g = copy.copy(args)
+    g.batch_size = int(args.batch_size) * world
+    tr, ev, te, length = build.create_data_loaders(g)
+    return {"train": tr, "val": ev, "test": te}[args.split], length
+
+
+def gather_records(records, world: int = 1, group=None):
+    """All ranks' records, sorted by clip index (one collective; the identity with one rank)."""
+    if world > 1:
+        parts = [None] * world
+        torch.distributed.all_gather_object(parts, list(records), group=group)
+        records = [r for part in parts for r in part]
+    return sorted(records, key=lambda r: r["index"])
+
+
+def summarize(records, targeted: bool = False):
+    keys = SUMMARY_FIELDS + ((TARGET_FIELD,) if targeted else ())
+    n = len(records)
+    return {k: (sum(float(r[k]) for r in records) / n if n else float("nan")) for k in keys} | {"clips": n}
+
+
+def results_dict(records, args):
+    targeted = args.attack_mode == "targeted"
+    return {"norm_type": str(args.norm_type), "attack_mode": args.attack_mode, "optimizer_type": args.optimizer_type,
+            "split": args.split, "pgd_steps": int(args.pgd_steps), "clips": list(records),
+            "summary": summarize(records, targeted)}
+
+
+def write_results(path, records, args):
+    with open(path, "w") as f:
+        json.dump(results_dict(records, args), f, indent=2)
+
+
+def _wer(pred, ref):
+    e, w = loss_helpers.wer_counts([pred], [ref])
+    return e / max(w, 1)
+
+
+def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper=None):
+    """Attack one batch of clips (x (B, L) on the device) and return (records, delta, adversarial waveforms)."""
+    B, L = x.shape
+    labels = loss_helpers.make_labels(texts, processor, args, B)
+    delta = torch.from_numpy(init_rows(L, idx, int(args.seed))).to(x.device)
+    project_rows(delta, x, args, interp, spl_thresh)                      # build.py:301-304, per clip
+    if args.optimizer_type == "adam":
+        optimizer = torch.optim.Adam([delta], lr=args.lr)
+        stepper = ClipStepper(model, args, L, interp, spl_thresh, optimizer=optimizer)
+    elif stepper is None:
+        stepper = ClipStepper(model, args, L, interp, spl_thresh)
+    for _ in range(int(args.pgd_steps)):
+        stepper.step(delta.data, x, labels, want_logits=False)
+    delta = delta.detach()
+    clean_out = model.forward(x, None, labels)
+    adv_out = model.forward(x, delta, labels, clamp=True)
+    clean_nll = clip_nll(model, clean_out["logits"], labels).cpu()
+    adv_nll = clip_nll(model, adv_out["logits"], labels).cpu()
+    refs = loss_helpers.clean_transcripts(texts)
+    clean_pred, _ = loss_helpers.wer_texts(clean_out["logits"], texts, processor)
+    adv_pred, _ = loss_helpers.wer_texts(adv_out["logits"], texts, processor)
+    target = loss_helpers.clean_transcripts([" ".join([args.target] * args.target_reps)])[0]
+    l2 = delta.norm(dim=1).cpu()
+    linf = delta.abs().amax(dim=1).cpu()
+    sig = x.double().pow(2).sum(dim=1).cpu()
+    noise = delta.double().pow(2).sum(dim=1).cpu()
+    records = []
+    for b in range(B):
+        rec = {"index": int(idx[b]), "clean_wer": _wer(clean_pred[b], refs[b].lower()), "adv_wer": _wer(adv_pred[b], refs[b].lower()),
+               "clean_ctc": float(clean_nll[b]), "final_ctc": float(adv_nll[b]), "l2": float(l2[b]), "linf": float(linf[b]),
+               "snr_db": float(10.0 * math.log10(float(sig[b]) / float(noise[b]))) if float(noise[b]) > 0 else float("inf")}
+        if args.attack_mode == "targeted":
+            rec[TARGET_FIELD] = _wer(adv_pred[b], target.lower())
+        records.append(rec)
+    return records, delta, compose_rows(x, delta), stepper
+
+
+def main(args) -> int:
+    if not torch.cuda.is_available():
+        raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")
+    if not str(args.device).startswith("cuda"):
+        args.device = "cuda"
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if world > 1:
+        local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
+        torch.cuda.set_device(local)
+        args.device = f"cuda:{local}"
+        if not torch.distributed.is_initialized():
+            backend = os.environ.get("PAA_DIST_BACKEND", "nccl")
+            if backend == "nccl":
+                torch.distributed.init_process_group("nccl", device_id=torch.device(args.device))
+            else:
+                torch.distributed.init_process_group(backend)
+    args.attack_size_string = build.attack_size_string(args)
+    root = getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
+    args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
+                                 f"clips_{args.norm_type}_{args.attack_size_string}_{args.attack_mode}_{args.optimizer_type}")
+    os.makedirs(args.save_dir, exist_ok=True)
+    interp = iso.build_weight_interpolator()
+    spl_thresh = build.init_phon_threshold_tensor(args)
+    batches, length = split_batches(args, world)
+    mine = clip_batches(batches, rank, world)
+    model, processor = build.load_model(args, max_batch=max([len(t) for _, t, _ in mine] or [1]), length=length)
+    records, stepper = [], None
+    n_wav = int(args.num_items_to_inspect)
+    for x, texts, idx in mine:
+        x = x.to(args.device, torch.float32).contiguous()
+        recs, _, adv, stepper = attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper)
+        records += recs
+        for b, i in enumerate(idx):
+            if i < n_wav:
+                save.save_audio(os.path.join(args.save_dir, f"adv_clip{i}.wav"), adv[b], sample_rate=args.sr)
+        if not getattr(args, "silent", False):
+            print(f"[rank {rank}] clips {idx[0]}..{idx[-1]}: mean adv WER "
+                  f"{sum(r['adv_wer'] for r in recs) / len(recs):.4f}, mean final CTC {sum(r['final_ctc'] for r in recs) / len(recs):.4f}",
+                  flush=True)
+    records = gather_records(records, world)
+    if rank == 0:
+        write_results(os.path.join(args.save_dir, "clip_results.json"), records, args)
+        print(json.dumps(summarize(records, args.attack_mode == "targeted")), flush=True)
+    if world > 1:
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(create_arg_parser().parse_args()))

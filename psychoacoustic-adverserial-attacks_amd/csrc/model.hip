@@ -396,7 +396,8 @@ static paa_status linear(const paa_model* m, CBf x, CBf w, const float* bias, fl
     return gemm(d, st);
 }
 
-static paa_status forward(paa_model* m, const float* clean, const float* p, int clamp, int B, hipStream_t st) {
+// p_ld: row stride of p (0 = the universal row, L = one row per clip)
+static paa_status forward(paa_model* m, const float* clean, const float* p, int p_ld, int clamp, int B, hipStream_t st) {
     const paa_arch& a = m->a;
     const int nc = a.n_conv, H = a.hidden, F = a.ffn, V = a.vocab, nh = a.heads, hd = H / nh, G = a.pos_groups, Hg = H / G;
     const int M = B * m->P, T = m->T, P = m->P, Tp = m->Tp;
@@ -404,7 +405,7 @@ static paa_status forward(paa_model* m, const float* clean, const float* p, int 
     {
         ConvL& c = m->conv[0];
         Conv0Args ca{};
-        ca.clean = clean; ca.p = p; ca.clamp = clamp; ca.B = B; ca.L = m->L; ca.T = c.T; ca.P = c.P; ca.C = c.cout;
+        ca.clean = clean; ca.p = p; ca.p_ld = p_ld; ca.grad_rows = p_ld != 0; ca.clamp = clamp; ca.B = B; ca.L = m->L; ca.T = c.T; ca.P = c.P; ca.C = c.cout;
         ca.k = c.k; ca.stride = c.s; ca.w = c.w0; ca.bias = c.b; ca.gamma = c.g; ca.beta = c.beta; ca.eps = 1e-5f;
         ca.pre = c.pre; ca.pre16 = c.pre16; ca.gate = c.gate; ca.actb = c.actb; ca.gn_stats = m->gn_stats; ca.row_stats = c.row_stats;
         if (a.feat_norm_layer) PAA_TRY(conv0_ln_forward(ca, st)); else PAA_TRY(conv0_gn_forward(ca, m->c0_part, st));
@@ -519,7 +520,7 @@ static paa_status forward(paa_model* m, const float* clean, const float* p, int 
     return PAA_OK;
 }
 
-static paa_status backward(paa_model* m, const float* clean, const float* p, int clamp, int B, float* grad, hipStream_t st) {
+static paa_status backward(paa_model* m, const float* clean, const float* p, int p_ld, int clamp, int B, float* grad, hipStream_t st) {
     const paa_arch& a = m->a;
     const int nc = a.n_conv, H = a.hidden, F = a.ffn, V = a.vocab, nh = a.heads, hd = H / nh, G = a.pos_groups, Hg = H / G;
     const int M = B * m->P, T = m->T, P = m->P, Tp = m->Tp;
@@ -651,7 +652,7 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
     {
         ConvL& c = m->conv[0];
         Conv0Args ca{};
-        ca.clean = clean; ca.p = p; ca.clamp = clamp; ca.B = B; ca.L = m->L; ca.T = c.T; ca.P = c.P; ca.C = c.cout;
+        ca.clean = clean; ca.p = p; ca.p_ld = p_ld; ca.grad_rows = p_ld != 0; ca.clamp = clamp; ca.B = B; ca.L = m->L; ca.T = c.T; ca.P = c.P; ca.C = c.cout;
         ca.k = c.k; ca.stride = c.s; ca.w = c.w0; ca.bias = c.b; ca.gamma = c.g; ca.beta = c.beta; ca.eps = 1e-5f;
         ca.gn_stats = m->gn_stats; ca.gn_bsums = m->gn_bsums; ca.row_stats = c.row_stats; ca.dpre = m->gF[0]; ca.G = m->G;
         ca.dpreb = m->g0H; ca.G1 = m->G1; ca.w1b = m->c0_w1H; ca.Mx = m->c0_Mx; ca.kc = m->c0_kc;
@@ -660,16 +661,19 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
     return PAA_OK;
 }
 
-extern "C" paa_status paa_model_fwd_bwd(paa_model* m, const float* d_clean, const float* d_p, const int32_t* d_labels, int B,
-                                        int S_max, int direction, float* d_grad, float* d_logits, float* d_stats,
-                                        void* stream) {
+// p_rows = 1: d_p is the universal (1, L) row, d_grad (1, L) sums over the clips.  p_rows = B: d_p (B, L) holds one row per
+// clip and d_grad (B, L) receives one gradient row per clip (no sum over the clips).
+static paa_status fwd_bwd_impl(paa_model* m, const float* d_clean, const float* d_p, int p_rows, const int32_t* d_labels, int B,
+                               int S_max, int direction, float* d_grad, float* d_logits, float* d_stats, void* stream) {
     if (!m || !d_clean) PAA_FAIL(PAA_ERR_ARG, "paa_model_fwd_bwd: null argument");
     if (B < 1 || B > m->Bmax) PAA_FAIL(PAA_ERR_SIZE, "batch %d exceeds max_batch %d", B, m->Bmax);
+    if (p_rows != 1 && p_rows != B) PAA_FAIL(PAA_ERR_SIZE, "p_rows=%d must be 1 or the batch %d", p_rows, B);
     if (d_labels && (S_max < 1 || S_max > m->S_cap)) PAA_FAIL(PAA_ERR_SIZE, "S_max=%d exceeds capacity %d", S_max, m->S_cap);
     if (d_grad && !d_labels) PAA_FAIL(PAA_ERR_ARG, "gradient requested without labels");
     hipStream_t st = (hipStream_t)stream;
     const int clamp = d_p ? 1 : 0;
-    PAA_TRY(forward(m, d_clean, d_p, clamp, B, st));
+    const int p_ld = p_rows > 1 ? m->L : 0;
+    PAA_TRY(forward(m, d_clean, d_p, p_ld, clamp, B, st));
     const int V = m->a.vocab;
     if (d_logits) {
         hipLaunchKernelGGL(k_copy_logits, dim3(std::min(cdiv((int64_t)B * m->T * V, 256), 2048)), dim3(256), 0, st,
@@ -681,19 +685,32 @@ extern "C" paa_status paa_model_fwd_bwd(paa_model* m, const float* d_clean, cons
                     d_grad ? m->dlogits : nullptr, d_grad ? m->dlogitsH : NOBF, m->ctc_work, st));
         if (d_stats) PAA_TRY(sum_small(m->nll, B, d_stats, st));
     }
-    if (d_grad) PAA_TRY(backward(m, d_clean, d_p, clamp, B, d_grad, st));
+    if (d_grad) PAA_TRY(backward(m, d_clean, d_p, p_ld, clamp, B, d_grad, st));
     return PAA_OK;
+}
+
+extern "C" paa_status paa_model_fwd_bwd(paa_model* m, const float* d_clean, const float* d_p, const int32_t* d_labels, int B,
+                                        int S_max, int direction, float* d_grad, float* d_logits, float* d_stats,
+                                        void* stream) {
+    return fwd_bwd_impl(m, d_clean, d_p, 1, d_labels, B, S_max, direction, d_grad, d_logits, d_stats, stream);
+}
+
+extern "C" paa_status paa_model_fwd_bwd_rows(paa_model* m, const float* d_clean, const float* d_p, int p_rows,
+                                             const int32_t* d_labels, int B, int S_max, int direction, float* d_grad,
+                                             float* d_logits, float* d_stats, void* stream) {
+    return fwd_bwd_impl(m, d_clean, d_p, p_rows, d_labels, B, S_max, direction, d_grad, d_logits, d_stats, stream);
 }
 
 // Forward + CTC loss only, with explicit control of the clamp: the reference's evaluation adds p WITHOUT clamping
 // (training_utils/evaluation.py:16), its training step clamps (train.py:136).
-extern "C" paa_status paa_model_forward(paa_model* m, const float* d_clean, const float* d_p, int clamp, const int32_t* d_labels,
-                                        int B, int S_max, float* d_logits, float* d_stats, void* stream) {
+static paa_status forward_impl(paa_model* m, const float* d_clean, const float* d_p, int p_rows, int clamp,
+                               const int32_t* d_labels, int B, int S_max, float* d_logits, float* d_stats, void* stream) {
     if (!m || !d_clean) PAA_FAIL(PAA_ERR_ARG, "paa_model_forward: null argument");
     if (B < 1 || B > m->Bmax) PAA_FAIL(PAA_ERR_SIZE, "batch %d exceeds max_batch %d", B, m->Bmax);
+    if (p_rows != 1 && p_rows != B) PAA_FAIL(PAA_ERR_SIZE, "p_rows=%d must be 1 or the batch %d", p_rows, B);
     if (d_labels && (S_max < 1 || S_max > m->S_cap)) PAA_FAIL(PAA_ERR_SIZE, "S_max=%d exceeds capacity %d", S_max, m->S_cap);
     hipStream_t st = (hipStream_t)stream;
-    PAA_TRY(forward(m, d_clean, d_p, (d_p && clamp) ? 1 : 0, B, st));
+    PAA_TRY(forward(m, d_clean, d_p, p_rows > 1 ? m->L : 0, (d_p && clamp) ? 1 : 0, B, st));
     const int V = m->a.vocab;
     if (d_logits) {
         hipLaunchKernelGGL(k_copy_logits, dim3(std::min(cdiv((int64_t)B * m->T * V, 256), 2048)), dim3(256), 0, st,
@@ -705,6 +722,17 @@ extern "C" paa_status paa_model_forward(paa_model* m, const float* d_clean, cons
         if (d_stats) PAA_TRY(sum_small(m->nll, B, d_stats, st));
     }
     return PAA_OK;
+}
+
+extern "C" paa_status paa_model_forward(paa_model* m, const float* d_clean, const float* d_p, int clamp, const int32_t* d_labels,
+                                        int B, int S_max, float* d_logits, float* d_stats, void* stream) {
+    return forward_impl(m, d_clean, d_p, 1, clamp, d_labels, B, S_max, d_logits, d_stats, stream);
+}
+
+extern "C" paa_status paa_model_forward_rows(paa_model* m, const float* d_clean, const float* d_p, int p_rows, int clamp,
+                                             const int32_t* d_labels, int B, int S_max, float* d_logits, float* d_stats,
+                                             void* stream) {
+    return forward_impl(m, d_clean, d_p, p_rows, clamp, d_labels, B, S_max, d_logits, d_stats, stream);
 }
 
 // torch.argmax(logits, dim=-1) of core/loss_helpers.py:26,61 on a caller-owned (rows, V) f32 tensor -> int16 ids.

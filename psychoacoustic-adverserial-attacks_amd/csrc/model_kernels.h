@@ -24,7 +24,9 @@ paa_status softmax_bwd(float* dp, const float* p, int n_mat, int rows_per_mat, i
 // First feature-encoder layer (C_in = 1).  Activations are channel-last with P >= T rows per clip.
 struct Conv0Args {
     const float* clean;      // (B, L)
-    const float* p;          // (L) or null
+    const float* p;          // (L), (B, L) or null
+    int p_ld;                // row stride of p: 0 = one universal row, L = one row per clip
+    int grad_rows;           // backward: grad is (B, L), one row per clip (no sum over clips)
     int clamp;               // clamp(clean + p, -1, 1)
     int B, L, T, P, C, k, stride;
     const float* w;          // [C][k]
@@ -48,12 +50,12 @@ struct Conv0Args {
     float* kc;               //   (B, 16)    sum_c W1_b[c][j] * (s2_bc * rstd_bc * mean_bc - s1_bc)
     float* part;             // scratch partials
 };
-// Input sample i of clip b: clamp(clean[b][i] + p[i], -1, 1) (train.py:136) — or clean + p unclamped
+// Input sample i of clip b: clamp(clean[b][i] + p[b * p_ld + i], -1, 1) (train.py:136) — or clean + p unclamped
 // (evaluation.py:16) — or clean alone when p is null.  Never materialised.
 __device__ __forceinline__ float in_sample(const Conv0Args& a, int b, int i) {
     float v = a.clean[(size_t)b * a.L + i];
     if (a.p) {
-        v += a.p[i];
+        v += a.p[(size_t)b * a.p_ld + i];
         if (a.clamp) v = fminf(fmaxf(v, -1.f), 1.f);
     }
     return v;

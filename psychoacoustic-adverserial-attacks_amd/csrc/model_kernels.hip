@@ -595,11 +595,13 @@ __global__ __launch_bounds__(256) void k_conv0_rows(Conv0Args a) {
 }
 
 // grad[l] = sum_b mask_b[l] * sum_{(t, j): t*stride + j = l} G[b][t][j]    (fixed summation order over b)
+// ROWS (per-clip perturbation, a.p_ld = L): grad[b][l] = mask_b[l] * sum_{(t, j)} G[b][t][j], no sum over clips.
+template <bool ROWS>
 __global__ void k_input_grad(Conv0Args a, float* __restrict__ grad) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= a.L) return;
     float total = 0.f;
-    const float pv = a.p ? a.p[l] : 0.f;
+    const float pv = (!ROWS && a.p) ? a.p[l] : 0.f;
     for (int b = 0; b < a.B; ++b) {
         float gsum = 0.f;
         // taps j = l - t*stride in [0, k)  =>  t in [ceil((l-k+1)/stride), floor(l/stride)]
@@ -609,12 +611,13 @@ __global__ void k_input_grad(Conv0Args a, float* __restrict__ grad) {
         if (t_hi > a.T - 1) t_hi = a.T - 1;
         for (int t = t_lo; t <= t_hi; ++t) gsum += a.G[((size_t)b * a.P + t) * a.k + (l - t * a.stride)];
         if (a.p && a.clamp) {
-            const float u = a.clean[(size_t)b * a.L + l] + pv;
+            const float u = a.clean[(size_t)b * a.L + l] + (ROWS ? a.p[(size_t)b * a.p_ld + l] : pv);
             if (!(u >= -1.f && u <= 1.f)) gsum = 0.f;           // clamp backward: pass-through inside [-1, 1]
         }
-        total += gsum;
+        if (ROWS) grad[(size_t)b * a.L + l] = gsum;
+        else total += gsum;
     }
-    grad[l] = total;
+    if (!ROWS) grad[l] = total;
 }
 
 // GroupNorm backward of conv0 without touching the (B, T, C) gradient row by row:
@@ -684,7 +687,9 @@ __global__ __launch_bounds__(256) void k_conv0_bwd_prep(Conv0Args a, int mode) {
 // dependent global round trips — input window / Mx / kc into LDS, then G1 — so four clips in flight per workgroup and
 // four times as many workgroups hide what a single walk over all clips exposed).  Per clip the input window, Mx_b and
 // kc_b are staged in LDS once instead of being recomputed / re-read per (frame, tap).  Fixed summation order.
+// ROWS (per-clip perturbation, a.p_ld = L): each wave writes its clip's row grad[b][l]; the sum over clips is dropped.
 constexpr int IG_S = 64;
+template <bool ROWS>
 __global__ __launch_bounds__(256) void k_input_grad_gn(Conv0Args a, float* __restrict__ grad) {
     __shared__ float xs[4][IG_S + 2 * 10 + 4];
     __shared__ float smx[4][10 * 10], skc[4][16];
@@ -722,11 +727,13 @@ __global__ __launch_bounds__(256) void k_input_grad_gn(Conv0Args a, float* __res
             gsum += g;
         }
         if (a.p && a.clamp) {
-            const float u = a.clean[(size_t)b * a.L + lc] + a.p[lc];
+            const float u = a.clean[(size_t)b * a.L + lc] + a.p[(ROWS ? (size_t)b * a.p_ld : 0) + lc];
             if (!(u >= -1.f && u <= 1.f)) gsum = 0.f;           // clamp backward: pass-through inside [-1, 1]
         }
-        total += gsum;
+        if (ROWS) { if (l < a.L) grad[(size_t)b * a.L + l] = gsum; }
+        else total += gsum;
     }
+    if (ROWS) return;
     part[cg][ls] = total;
     __syncthreads();
     if (cg == 0 && l < a.L) grad[l] = (part[0][ls] + part[1][ls]) + (part[2][ls] + part[3][ls]);
@@ -758,6 +765,13 @@ paa_status conv0_ln_forward(const Conv0Args& a, hipStream_t st) {
     return PAA_OK;
 }
 
+static paa_status launch_input_grad_gn(const Conv0Args& a, float* grad, hipStream_t st) {
+    if (a.grad_rows) hipLaunchKernelGGL(k_input_grad_gn<true>, dim3(cdiv(a.L, IG_S)), dim3(256), 0, st, a, grad);
+    else hipLaunchKernelGGL(k_input_grad_gn<false>, dim3(cdiv(a.L, IG_S)), dim3(256), 0, st, a, grad);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
 static bool g_conv0_two_pass = false;
 void set_conv0_two_pass(bool on) { g_conv0_two_pass = on; }
 
@@ -766,7 +780,8 @@ paa_status conv0_backward(const Conv0Args& a, int layer_norm, int precision, flo
     if (layer_norm) {
         hipLaunchKernelGGL(k_conv0_rows<C0_BWD_LN>, dim3(std::min(cdiv(a.P, 4), 512), a.B), dim3(256), 0, st, a);
         PAA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_input_grad, dim3(cdiv(a.L, 256)), dim3(256), 0, st, a, grad);
+        if (a.grad_rows) hipLaunchKernelGGL(k_input_grad<true>, dim3(cdiv(a.L, 256)), dim3(256), 0, st, a, grad);
+        else hipLaunchKernelGGL(k_input_grad<false>, dim3(cdiv(a.L, 256)), dim3(256), 0, st, a, grad);
         PAA_LAUNCH_CHECK();
         return PAA_OK;
     }
@@ -779,9 +794,7 @@ paa_status conv0_backward(const Conv0Args& a, int layer_norm, int precision, flo
         PAA_TRY(conv0_dgrad_fused(a, part, st));
         hipLaunchKernelGGL(k_conv0_bwd_prep, dim3(a.B), dim3(256), 0, st, a, 2);
         PAA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_input_grad_gn, dim3(cdiv(a.L, IG_S)), dim3(256), 0, st, a, grad);
-        PAA_LAUNCH_CHECK();
-        return PAA_OK;
+        return launch_input_grad_gn(a, grad, st);
     }
     const int nchunk = cdiv(a.T, C0_TCH);
     const size_t lds = sizeof(float) * ((C0_TCH - 1) * a.stride + 10 + 8);
@@ -803,9 +816,7 @@ paa_status conv0_backward(const Conv0Args& a, int layer_norm, int precision, flo
     d.a_kcontig = 1; d.b_kcontig = 1; d.alpha = 1.f;
     d.batch = a.B; d.batch2 = 1; d.a_s1 = (int64_t)a.P * a.C; d.b_s1 = (int64_t)16 * a.C; d.c_s1 = (int64_t)a.P * 16;
     PAA_TRY(gemm(d, st));
-    hipLaunchKernelGGL(k_input_grad_gn, dim3(cdiv(a.L, IG_S)), dim3(256), 0, st, a, grad);
-    PAA_LAUNCH_CHECK();
-    return PAA_OK;
+    return launch_input_grad_gn(a, grad, st);
 }
 
 // ===================================================================================== CTC ===

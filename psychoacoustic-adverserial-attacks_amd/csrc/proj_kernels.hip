@@ -192,7 +192,9 @@ __global__ __launch_bounds__(FFT_NT) void k_frame(FrameArgs a) {
 }
 
 // Overlap-add + envelope division + trim + _align_to (train.py:27-35): out (rows, out_len).
-// Samples >= hop*(T-1) are zero (right zero-pad).  scal[0] (if non-null) is a uniform scale factor.
+// Samples >= hop*(T-1) are zero (right zero-pad).  scal[0] (if non-null) is a uniform scale factor; ROWS: scal[row] is
+// the scale of row `row` (per-row projections, paa_project_rows).
+template <bool ROWS>
 __global__ void k_ola(const float* __restrict__ frames, const float* __restrict__ win, const float* __restrict__ scal,
                       float* __restrict__ out, int T, int N, int hop, int out_len) {
     const int row = blockIdx.y;
@@ -214,31 +216,47 @@ __global__ void k_ola(const float* __restrict__ frames, const float* __restrict_
             env += w * w;
         }
         v = sum / env;
-        if (scal) v *= scal[0];
+        if (scal) v *= scal[ROWS ? row : 0];
     }
     out[(size_t)row * out_len + m] = v;
 }
 
 // projections.py:116-133 project_fm_norm: scale = eps / max(norm, 1e-8) if norm > eps else 1
+// ROWS: one workgroup per row, row r sums part[r * n, (r + 1) * n) and writes its scale to scal[r] (no norm slot).
+template <bool ROWS>
 __global__ __launch_bounds__(RED_NT) void k_fm_finalize(const double* __restrict__ part, int n, float eps,
                                                       float* __restrict__ scal) {
     __shared__ double red[RED_NT / 64];
+    if (ROWS) part += (size_t)blockIdx.x * n;
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += RED_NT) s += part[i];
     s = block_sum<double, RED_NT>(s, red);
     if (threadIdx.x == 0) {
         const float norm = sqrtf((float)s);
-        scal[0] = (norm <= eps) ? 1.f : eps / fmaxf(norm, 1e-8f);
-        scal[1] = norm;
+        const float scale = (norm <= eps) ? 1.f : eps / fmaxf(norm, 1e-8f);
+        if (ROWS) {
+            scal[blockIdx.x] = scale;
+        } else {
+            scal[0] = scale;
+            scal[1] = norm;
+        }
     }
 }
 
 // Second launch of a fused spectral projection: dst = src * scale, the scale being the predicated FM factor computed from
 // the per-workgroup partial sums of the first launch (every block re-sums the few hundred partials: no third launch);
 // npart = 0: plain copy (min_max_freqs / max_phon, in-place form only).
+// ROWS: blockIdx.y is the row; n and npart are per row, and each row is scaled by the norm of its own partials.
+template <bool ROWS>
 __global__ __launch_bounds__(RED_NT) void k_spec_finish(const float* __restrict__ src, float* __restrict__ dst, int64_t n,
                                                       const double* __restrict__ part, int npart, float eps, float* __restrict__ scal) {
     __shared__ double red[RED_NT / 64];
+    if (ROWS) {
+        src += (size_t)blockIdx.y * n;
+        dst += (size_t)blockIdx.y * n;
+        part += (size_t)blockIdx.y * npart;
+        if (blockIdx.y != 0) scal = nullptr;
+    }
     float scale = 1.f;
     if (npart > 0) {
         double s = 0.0;
@@ -267,11 +285,18 @@ __global__ __launch_bounds__(RED_NT) void k_spec_finish(const float* __restrict_
 enum RedMode { RED_SQ = 0, RED_TV = 1 };
 
 // Blocks [0, g1) reduce x1 (n1 elements, rows of length L1), blocks [g1, g1+g2) reduce x2.
-template <int MODE>
+// ROWS: blockIdx.y is the row; x1 / x2 point at row blockIdx.y (n1 = L1, n2 = L2) and the row's g1 + g2 partials go to
+// part[blockIdx.y * (g1 + g2) + ...]: each row is reduced exactly as a one-row call reduces it.
+template <int MODE, bool ROWS>
 __global__ __launch_bounds__(RED_NT) void k_reduce2(const float* __restrict__ x1, int64_t n1, int L1, int g1,
                                                   const float* __restrict__ x2, int64_t n2, int L2, int g2,
                                                   double* __restrict__ part) {
     __shared__ double red[RED_NT / 64];
+    if (ROWS) {
+        if (x1) x1 += (size_t)blockIdx.y * L1;
+        x2 += (size_t)blockIdx.y * L2;
+        part += (size_t)blockIdx.y * (g1 + g2);
+    }
     const bool first = (int)blockIdx.x < g1;
     const float* x = first ? x1 : x2;
     const int64_t n = first ? n1 : n2;
@@ -308,9 +333,16 @@ struct ApplyArgs {
 };
 
 // p = src * scale (src == p: in place; otherwise the out-of-place form reads the caller's source directly — no copy in front)
-template <int NORM>
+// ROWS: blockIdx.y is the row; n is the row length and the row's scale comes from its own g1 + g2 partials (k_reduce2 ROWS).
+template <int NORM, bool ROWS>
 __global__ __launch_bounds__(RED_NT) void k_apply_scale(const float* src, float* p, int64_t n, ApplyArgs a) {
     __shared__ double red[RED_NT / 64];
+    if (ROWS) {
+        src += (size_t)blockIdx.y * n;
+        p += (size_t)blockIdx.y * n;
+        a.part += (size_t)blockIdx.y * (a.g1 + a.g2);
+        if (blockIdx.y != 0) a.scal = nullptr;
+    }
     double s1 = 0.0, s2 = 0.0;
     for (int i = threadIdx.x; i < a.g1; i += RED_NT) s1 += a.part[i];
     for (int i = threadIdx.x; i < a.g2; i += RED_NT) s2 += a.part[a.g1 + i];
@@ -425,6 +457,12 @@ __global__ void k_compose_clamp(const float* __restrict__ x, const float* __rest
     const int64_t n = (int64_t)B * L;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         out[i] = fminf(fmaxf(x[i] + p[i % L], -1.f), 1.f);
+}
+
+// out[b][i] = clamp(x[b][i] + p[b][i], -1, 1): one perturbation row per clip
+__global__ void k_compose_clamp_rows(const float* __restrict__ x, const float* __restrict__ p, float* __restrict__ out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = fminf(fmaxf(x[i] + p[i], -1.f), 1.f);
 }
 
 }  // namespace paa
@@ -601,7 +639,7 @@ extern "C" paa_status paa_istft(paa_proj* h, const float* d_S, int B, int T, flo
     a.S_in = d_S;
     PAA_TRY(launch_frames<OP_ISTFT>(h, a, B, st));
     const int out_len = h->hop * (T - 1);
-    hipLaunchKernelGGL(k_ola, dim3(cdiv(out_len, 256), B), dim3(256), 0, st, h->d_frames, h->d_win, (const float*)nullptr,
+    hipLaunchKernelGGL(k_ola<false>, dim3(cdiv(out_len, 256), B), dim3(256), 0, st, h->d_frames, h->d_win, (const float*)nullptr,
                        d_out, T, h->n_fft, h->hop, out_len);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
@@ -630,7 +668,7 @@ static paa_status project_impl(paa_proj* h, const paa_params* prm, float* d_p, i
         PAA_TRY(spec_project(a, spec_op_of(nt), rows_p, &npart, st));
         const bool fm = nt == PAA_NORM_FLETCHER_MUNSON;
         if (fm || !d_src) {
-            hipLaunchKernelGGL(k_spec_finish, dim3(std::min(cdiv(n, (int64_t)RED_NT * 4), 1024)), dim3(RED_NT), 0, st,
+            hipLaunchKernelGGL(k_spec_finish<false>, dim3(std::min(cdiv(n, (int64_t)RED_NT * 4), 1024)), dim3(RED_NT), 0, st,
                                (const float*)a.out, d_p, n, (const double*)a.part, fm ? npart : 0, prm->fm_epsilon, h->d_scal);
             PAA_LAUNCH_CHECK();
         }
@@ -655,12 +693,12 @@ static paa_status project_impl(paa_proj* h, const paa_params* prm, float* d_p, i
             else if (nt == PAA_NORM_MAX_PHON) PAA_TRY(launch_frames<OP_PHON>(h, a, rows_p, st));
             else {
                 PAA_TRY(launch_frames<OP_FM>(h, a, rows_p, st));
-                hipLaunchKernelGGL(k_fm_finalize, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, rows_p * T,
+                hipLaunchKernelGGL(k_fm_finalize<false>, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, rows_p * T,
                                    prm->fm_epsilon, h->d_scal);
                 PAA_LAUNCH_CHECK();
                 scal = h->d_scal;
             }
-            hipLaunchKernelGGL(k_ola, dim3(cdiv(L, 256), rows_p), dim3(256), 0, st, h->d_frames, h->d_win, scal, d_p, T,
+            hipLaunchKernelGGL(k_ola<false>, dim3(cdiv(L, 256), rows_p), dim3(256), 0, st, h->d_frames, h->d_win, scal, d_p, T,
                                h->n_fft, h->hop, L);
             PAA_LAUNCH_CHECK();
             return PAA_OK;
@@ -682,10 +720,10 @@ static paa_status project_impl(paa_proj* h, const paa_params* prm, float* d_p, i
             const int g1 = nc ? std::min(cdiv(nc, (int64_t)RED_NT * 16), 2048) : 0;
             const int g2 = std::min(cdiv(n, (int64_t)RED_NT * 8), 1024);
             if (nt == PAA_NORM_TV)
-                hipLaunchKernelGGL(k_reduce2<RED_TV>, dim3(g1 + g2), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_in,
+                hipLaunchKernelGGL((k_reduce2<RED_TV, false>), dim3(g1 + g2), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_in,
                                    n, L, g2, h->d_part);
             else
-                hipLaunchKernelGGL(k_reduce2<RED_SQ>, dim3(g1 + g2), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_in,
+                hipLaunchKernelGGL((k_reduce2<RED_SQ, false>), dim3(g1 + g2), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_in,
                                    n, L, g2, h->d_part);
             PAA_LAUNCH_CHECK();
             ApplyArgs a{};
@@ -695,9 +733,9 @@ static paa_status project_impl(paa_proj* h, const paa_params* prm, float* d_p, i
             a.snr_db = prm->snr_db; a.snr_linear = (float)pow(10.0, (double)prm->snr_db / 10.0);
             a.eps = (nt == PAA_NORM_L2) ? prm->l2_size : prm->tv_epsilon;
             const int ga = std::min(cdiv(n, 256), 1024);
-            if (nt == PAA_NORM_L2) hipLaunchKernelGGL(k_apply_scale<PAA_NORM_L2>, dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
-            else if (nt == PAA_NORM_SNR) hipLaunchKernelGGL(k_apply_scale<PAA_NORM_SNR>, dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
-            else hipLaunchKernelGGL(k_apply_scale<PAA_NORM_TV>, dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
+            if (nt == PAA_NORM_L2) hipLaunchKernelGGL((k_apply_scale<PAA_NORM_L2, false>), dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
+            else if (nt == PAA_NORM_SNR) hipLaunchKernelGGL((k_apply_scale<PAA_NORM_SNR, false>), dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
+            else hipLaunchKernelGGL((k_apply_scale<PAA_NORM_TV, false>), dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
             PAA_LAUNCH_CHECK();
             return PAA_OK;
         }
@@ -718,6 +756,123 @@ extern "C" paa_status paa_project_to(paa_proj* h, const paa_params* prm, const f
     const float* hi = d_src < d_dst ? d_dst : d_src;
     if (rows_p > 0 && L > 0 && lo + (int64_t)rows_p * L > hi) PAA_FAIL(PAA_ERR_ARG, "paa_project_to: source and destination overlap");
     return project_impl(h, prm, d_dst, rows_p, d_clean, B, L, nullptr, 0.0, stream, d_src);
+}
+
+// Per-row form (per-clip perturbations): row r of d_src (rows, L) is projected exactly as the one-row call
+// perturbation_constraint(src[r][None], clean[r][None], args) projects it (train.py:69-99) — l2 / fletcher_munson from the
+// row's own norm, snr from clean row r's own mean power (clean.numel() = L), tv from TV(clean[r]).  The launch sequence
+// is the one of a one-row projection with a row grid dimension; no launch per row.
+static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
+                                    const float* d_clean, int L, hipStream_t st) {
+    const int nt = prm->norm_type;
+    const int64_t n = (int64_t)rows * L;
+    const bool in_place = d_src == d_dst;
+    switch (nt) {
+        case PAA_NORM_LINF:
+            hipLaunchKernelGGL(k_clamp, dim3(std::min(cdiv(n, 256), 2048)), dim3(256), 0, st, d_src, d_dst, n, -prm->linf_size,
+                               prm->linf_size);
+            PAA_LAUNCH_CHECK();
+            return PAA_OK;
+        case PAA_NORM_L2:
+        case PAA_NORM_SNR:
+        case PAA_NORM_TV: {
+            if (nt != PAA_NORM_L2 && !d_clean) {
+                if (nt == PAA_NORM_SNR) PAA_FAIL(PAA_ERR_NEED_CLEAN, "SNR projection requires clean_audio ro compare to");
+                PAA_FAIL(PAA_ERR_NEED_CLEAN, "TV projection can benefit from clean_audio for bounds");
+            }
+            // the reduction geometry of a one-row call on each row: the same partials, summed in the same order
+            const int64_t nc = nt == PAA_NORM_L2 ? 0 : L;
+            const int g1 = nc ? std::min(cdiv(nc, (int64_t)RED_NT * 16), 2048) : 0;
+            const int g2 = std::min(cdiv((int64_t)L, (int64_t)RED_NT * 8), 1024);
+            if ((size_t)rows * (g1 + g2) * 2 > h->frames_floats)
+                PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d L=%d exceeds the workspace", rows, L);
+            double* part = reinterpret_cast<double*>(h->d_frames);     // the frame workspace is idle for these norms
+            if (nt == PAA_NORM_TV)
+                hipLaunchKernelGGL((k_reduce2<RED_TV, true>), dim3(g1 + g2, rows), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_src,
+                                   (int64_t)L, L, g2, part);
+            else
+                hipLaunchKernelGGL((k_reduce2<RED_SQ, true>), dim3(g1 + g2, rows), dim3(RED_NT), 0, st, nc ? d_clean : nullptr, nc, L,
+                                   g1, d_src, (int64_t)L, L, g2, part);
+            PAA_LAUNCH_CHECK();
+            ApplyArgs a{};
+            a.part = part; a.g1 = g1; a.g2 = g2; a.scal = h->d_scal;
+            a.numel_clean = (double)nc; a.numel_p = (double)L; a.clip_len = (double)L;
+            a.snr_db = prm->snr_db; a.snr_linear = (float)pow(10.0, (double)prm->snr_db / 10.0);
+            a.eps = (nt == PAA_NORM_L2) ? prm->l2_size : prm->tv_epsilon;
+            const dim3 grid(std::min(cdiv((int64_t)L, (int64_t)RED_NT * 4), 128), rows);
+            if (nt == PAA_NORM_L2) hipLaunchKernelGGL((k_apply_scale<PAA_NORM_L2, true>), grid, dim3(RED_NT), 0, st, d_src, d_dst, (int64_t)L, a);
+            else if (nt == PAA_NORM_SNR) hipLaunchKernelGGL((k_apply_scale<PAA_NORM_SNR, true>), grid, dim3(RED_NT), 0, st, d_src, d_dst, (int64_t)L, a);
+            else hipLaunchKernelGGL((k_apply_scale<PAA_NORM_TV, true>), grid, dim3(RED_NT), 0, st, d_src, d_dst, (int64_t)L, a);
+            PAA_LAUNCH_CHECK();
+            return PAA_OK;
+        }
+        case PAA_NORM_FLETCHER_MUNSON:
+        case PAA_NORM_MIN_MAX_FREQS:
+        case PAA_NORM_MAX_PHON: {
+            PAA_TRY(check_rows(h, rows, L, "paa_project_rows"));
+            const bool fm = nt == PAA_NORM_FLETCHER_MUNSON;
+            const int T = 1 + L / h->hop;
+            if (fused_geometry(h)) {
+                SpecArgs a = spec_args(h, L, T, L);
+                a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
+                a.x = d_src;
+                a.out = in_place ? h->d_frames : d_dst;
+                int npart = 0;
+                PAA_TRY(spec_project(a, spec_op_of(nt), rows, &npart, st));
+                if (fm) {                                      // each row re-sums only its own partials
+                    hipLaunchKernelGGL(k_spec_finish<true>, dim3(std::min(cdiv((int64_t)L, (int64_t)RED_NT * 4), 128), rows),
+                                       dim3(RED_NT), 0, st, (const float*)a.out, d_dst, (int64_t)L, (const double*)a.part,
+                                       npart / rows, prm->fm_epsilon, h->d_scal);
+                    PAA_LAUNCH_CHECK();
+                } else if (in_place) {
+                    hipLaunchKernelGGL(k_spec_finish<false>, dim3(std::min(cdiv(n, (int64_t)RED_NT * 4), 1024)), dim3(RED_NT), 0, st,
+                                       (const float*)a.out, d_dst, n, (const double*)nullptr, 0, prm->fm_epsilon, h->d_scal);
+                    PAA_LAUNCH_CHECK();
+                }
+                return PAA_OK;
+            }
+            if (!in_place) PAA_HIP(hipMemcpyAsync(d_dst, d_src, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+            if (fm && rows > 2 * MAX_PART) PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d exceeds %d", rows, 2 * MAX_PART);
+            FrameArgs a = frame_args(h, L, T);
+            a.x = d_dst;
+            a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
+            float* scal = nullptr;
+            if (nt == PAA_NORM_MIN_MAX_FREQS) PAA_TRY(launch_frames<OP_MINMAX>(h, a, rows, st));
+            else if (nt == PAA_NORM_MAX_PHON) PAA_TRY(launch_frames<OP_PHON>(h, a, rows, st));
+            else {
+                PAA_TRY(launch_frames<OP_FM>(h, a, rows, st));
+                scal = reinterpret_cast<float*>(h->d_part);           // rows scales, below the frame partials
+                hipLaunchKernelGGL(k_fm_finalize<true>, dim3(rows), dim3(RED_NT), 0, st, (const double*)a.part, T, prm->fm_epsilon,
+                                   scal);
+                PAA_LAUNCH_CHECK();
+            }
+            hipLaunchKernelGGL(k_ola<true>, dim3(cdiv(L, 256), rows), dim3(256), 0, st, h->d_frames, h->d_win, (const float*)scal,
+                               d_dst, T, h->n_fft, h->hop, L);
+            PAA_LAUNCH_CHECK();
+            return PAA_OK;
+        }
+        default:
+            PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", nt);
+    }
+}
+
+extern "C" paa_status paa_project_rows(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
+                                       const float* d_clean, int L, void* stream) {
+    if (!h || !prm || !d_src || !d_dst) PAA_FAIL(PAA_ERR_ARG, "paa_project_rows: null argument");
+    if (rows < 1 || L < 2) PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d L=%d", rows, L);
+    if (rows > h->max_batch || L > h->max_len)
+        PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d L=%d exceeds max_batch=%d / max_len=%d", rows, L, h->max_batch, h->max_len);
+    if (prm->norm_type < PAA_NORM_L2 || prm->norm_type > PAA_NORM_MAX_PHON) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", prm->norm_type);
+    if (d_src != d_dst) {
+        const float* lo = d_src < d_dst ? d_src : d_dst;
+        const float* hi = d_src < d_dst ? d_dst : d_src;
+        if (lo + (int64_t)rows * L > hi) PAA_FAIL(PAA_ERR_ARG, "paa_project_rows: source and destination overlap");
+    }
+    if (rows == 1) {              // one row: the universal projection of that row, the same launches
+        if (d_src == d_dst) return project_impl(h, prm, d_dst, 1, d_clean, d_clean ? 1 : 0, L, nullptr, 0.0, stream);
+        return project_impl(h, prm, d_dst, 1, d_clean, d_clean ? 1 : 0, L, nullptr, 0.0, stream, d_src);
+    }
+    return project_rows_impl(h, prm, d_src, d_dst, rows, d_clean, L, (hipStream_t)stream);
 }
 
 // core/projections.py:68-159 called directly on a spectrum (the reference's project_min_max_freqs / project_fm_norm /
@@ -743,7 +898,7 @@ extern "C" paa_status paa_spectrum_project(paa_proj* h, const paa_params* prm, c
     int npart = 0;
     a.S_out = nullptr;                                       // pass 1: weighted power only
     PAA_TRY(spec_apply(a, SOP_FM, B, nullptr, &npart, st));
-    hipLaunchKernelGGL(k_fm_finalize, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, npart, prm->fm_epsilon, h->d_scal);
+    hipLaunchKernelGGL(k_fm_finalize<false>, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, npart, prm->fm_epsilon, h->d_scal);
     PAA_LAUNCH_CHECK();
     a.S_out = d_S_out; a.part = nullptr;                     // pass 2: S * predicated scale
     return spec_apply(a, SOP_NONE, B, h->d_scal, nullptr, st);
@@ -760,7 +915,7 @@ extern "C" paa_status paa_fm_weighted_norm(paa_proj* h, const float* d_S, int B,
     a.S_in = d_S; a.S_out = nullptr;
     int npart = 0;
     PAA_TRY(spec_apply(a, SOP_FM, B, nullptr, &npart, st));
-    hipLaunchKernelGGL(k_fm_finalize, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, npart, 0.f, h->d_scal);
+    hipLaunchKernelGGL(k_fm_finalize<false>, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, npart, 0.f, h->d_scal);
     PAA_LAUNCH_CHECK();
     PAA_HIP(hipMemcpyAsync(d_out, h->d_scal + 1, sizeof(float), hipMemcpyDeviceToDevice, st));
     return PAA_OK;
@@ -792,10 +947,10 @@ extern "C" paa_status paa_batch_stats(paa_proj* h, const float* d_clean, int B, 
     hipStream_t st = (hipStream_t)stream;
     const int64_t nc = (int64_t)B * L;
     const int g = std::min(cdiv(nc, (int64_t)RED_NT * 16), 2048);
-    hipLaunchKernelGGL(k_reduce2<RED_SQ>, dim3(g), dim3(RED_NT), 0, st, d_clean, nc, L, g, (const float*)nullptr, (int64_t)0, L, 0,
+    hipLaunchKernelGGL((k_reduce2<RED_SQ, false>), dim3(g), dim3(RED_NT), 0, st, d_clean, nc, L, g, (const float*)nullptr, (int64_t)0, L, 0,
                        h->d_part);
     PAA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_reduce2<RED_TV>, dim3(g), dim3(RED_NT), 0, st, d_clean, nc, L, g, (const float*)nullptr, (int64_t)0, L, 0,
+    hipLaunchKernelGGL((k_reduce2<RED_TV, false>), dim3(g), dim3(RED_NT), 0, st, d_clean, nc, L, g, (const float*)nullptr, (int64_t)0, L, 0,
                        h->d_part + g);
     PAA_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(RED_NT), 0, st, (const double*)h->d_part, g, g, d_out2, d_clip_count, (float)B);
@@ -840,6 +995,20 @@ extern "C" paa_status paa_compose_clamp(const float* d_clean, const float* d_p, 
     if (!d_clean || !d_p || !d_out) PAA_FAIL(PAA_ERR_ARG, "paa_compose_clamp: null argument");
     hipLaunchKernelGGL(k_compose_clamp, dim3(std::min(cdiv((int64_t)B * L, 256), 4096)), dim3(256), 0, (hipStream_t)stream,
                        d_clean, d_p, d_out, B, L);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
+// train.py:136 with one perturbation row per clip: out[b] = clamp(clean[b] + p[b], -1, 1).  p_rows = 1 is paa_compose_clamp.
+extern "C" paa_status paa_compose_clamp_rows(const float* d_clean, const float* d_p, int p_rows, float* d_out, int B, int L,
+                                             void* stream) {
+    if (!d_clean || !d_p || !d_out) PAA_FAIL(PAA_ERR_ARG, "paa_compose_clamp_rows: null argument");
+    if (B < 1 || L < 1) PAA_FAIL(PAA_ERR_SIZE, "paa_compose_clamp_rows: B=%d L=%d", B, L);
+    if (p_rows != 1 && p_rows != B) PAA_FAIL(PAA_ERR_SIZE, "paa_compose_clamp_rows: p_rows=%d must be 1 or B=%d", p_rows, B);
+    if (p_rows == 1) return paa_compose_clamp(d_clean, d_p, d_out, B, L, stream);
+    const int64_t n = (int64_t)B * L;
+    hipLaunchKernelGGL(k_compose_clamp_rows, dim3(std::min(cdiv(n, 256), 4096)), dim3(256), 0, (hipStream_t)stream, d_clean, d_p,
+                       d_out, n);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }

@@ -202,7 +202,8 @@ class PaaModel:
 
     def _checked(self, clean, p):
         """Raw pointers cross the C ABI: refuse anything that is not a contiguous float32 tensor on this model's GPU
-        with the configured length (a float64 / CPU / strided batch would be read as garbage device memory)."""
+        with the configured length (a float64 / CPU / strided batch would be read as garbage device memory).
+        Returns (clean, p, p_rows): p_rows = 1 for the universal perturbation ((1, L) / (L,)), B for one row per clip."""
         clean = runtime.as_f32_cuda(clean, "clean_audio")
         if clean.dim() != 2:
             raise ValueError(f"clean_audio must be (B, L), got {tuple(clean.shape)}")
@@ -212,18 +213,24 @@ class PaaModel:
             raise ValueError(f"Loaded perturbation length {clean.shape[1]} != expected {self.length}")
         if clean.shape[0] < 1 or clean.shape[0] > self.max_batch:
             raise ValueError(f"batch {clean.shape[0]} exceeds the model's max_batch {self.max_batch}")
+        p_rows = 1
         if p is not None:
             p = runtime.as_f32_cuda(p, "p")
-            if p.numel() != self.length:
+            if p.dim() == 2 and p.shape[0] > 1 and p.shape[1] == self.length:
+                if p.shape[0] != clean.shape[0]:
+                    raise ValueError(f"per-clip perturbation has {p.shape[0]} rows, the batch {clean.shape[0]} clips")
+                p_rows = p.shape[0]
+            elif p.numel() != self.length:
                 raise ValueError(f"Loaded perturbation length {p.numel()} != expected {self.length}")
             if p.device != clean.device:
                 raise RuntimeError(f"p lives on {p.device}, clean_audio on {clean.device}")
-        return clean, p
+        return clean, p, p_rows
 
     def fwd_bwd(self, clean, p, labels, direction=+1, want_grad=True, want_logits=True, out=None):
-        """clean (B, L) f32 cuda; p (1, L) or None; labels (B, S) integer tensor, negatives = padding.
-        Returns dict(loss=0-d tensor, logits=(B, T_e, V) | None, grad=(1, L) | None, stats=(8,))."""
-        clean, p = self._checked(clean, p)
+        """clean (B, L) f32 cuda; p (1, L), (L,), (B, L) (one row per clip) or None; labels (B, S) integer tensor,
+        negatives = padding.  Returns dict(loss=0-d tensor, logits=(B, T_e, V) | None, grad=(1, L) | (B, L) | None,
+        stats=(8,)); with a per-clip p the gradient has one row per clip (no sum over the clips)."""
+        clean, p, p_rows = self._checked(clean, p)
         B, L = clean.shape
         dev = self.device
         lab = None if labels is None else labels.to(device=dev, dtype=torch.int32).contiguous()
@@ -231,7 +238,9 @@ class PaaModel:
         out = out or {}
         grad = out.get("grad") if want_grad else None
         if want_grad and grad is None:
-            grad = torch.empty(1, L, dtype=torch.float32, device=dev)
+            grad = torch.empty(p_rows, L, dtype=torch.float32, device=dev)
+        if grad is not None and grad.numel() != p_rows * L:
+            raise ValueError(f"gradient buffer holds {grad.numel()} floats, expected {p_rows} x {L}")
         logits = out.get("logits") if want_logits else None
         if want_logits and logits is None:
             logits = torch.empty(B, self.frames, self.arch.vocab_size, dtype=torch.float32, device=dev)
@@ -239,23 +248,33 @@ class PaaModel:
         if stats is None:
             stats = torch.zeros(8, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().paa_model_fwd_bwd(self.h, _lib.ptr(clean), _lib.ptr(p), _lib.ptr(lab), B, S, int(direction),
-                                                    _lib.ptr(grad), _lib.ptr(logits), _lib.ptr(stats), _lib.stream_ptr()))
+            if p_rows == 1:
+                _lib.check(_lib.lib().paa_model_fwd_bwd(self.h, _lib.ptr(clean), _lib.ptr(p), _lib.ptr(lab), B, S, int(direction),
+                                                        _lib.ptr(grad), _lib.ptr(logits), _lib.ptr(stats), _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().paa_model_fwd_bwd_rows(self.h, _lib.ptr(clean), _lib.ptr(p), p_rows, _lib.ptr(lab), B, S,
+                                                             int(direction), _lib.ptr(grad), _lib.ptr(logits), _lib.ptr(stats),
+                                                             _lib.stream_ptr()))
         return dict(loss=stats[0], logits=logits, grad=grad, stats=stats, labels=lab)
 
     def forward(self, clean, p, labels, clamp=False, want_logits=True):
         """Forward + CTC loss only.  ``clamp=False`` composes ``clean + p`` as the reference's evaluation does
-        (evaluation.py:16); ``p=None`` evaluates the clean batch.  Returns dict(loss, logits)."""
-        clean, p = self._checked(clean, p)
+        (evaluation.py:16); ``p=None`` evaluates the clean batch; p (B, L) holds one row per clip.  Returns dict(loss, logits)."""
+        clean, p, p_rows = self._checked(clean, p)
         B, L = clean.shape
         dev = self.device
         lab = None if labels is None else labels.to(device=dev, dtype=torch.int32).contiguous()
         logits = torch.empty(B, self.frames, self.arch.vocab_size, dtype=torch.float32, device=dev) if want_logits else None
         stats = torch.zeros(8, dtype=torch.float32, device=dev)
+        S = 0 if lab is None else lab.shape[1]
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().paa_model_forward(self.h, _lib.ptr(clean), _lib.ptr(p), int(bool(clamp)), _lib.ptr(lab), B,
-                                                    0 if lab is None else lab.shape[1], _lib.ptr(logits), _lib.ptr(stats),
-                                                    _lib.stream_ptr()))
+            if p_rows == 1:
+                _lib.check(_lib.lib().paa_model_forward(self.h, _lib.ptr(clean), _lib.ptr(p), int(bool(clamp)), _lib.ptr(lab), B,
+                                                        S, _lib.ptr(logits), _lib.ptr(stats), _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().paa_model_forward_rows(self.h, _lib.ptr(clean), _lib.ptr(p), p_rows, int(bool(clamp)),
+                                                             _lib.ptr(lab), B, S, _lib.ptr(logits), _lib.ptr(stats),
+                                                             _lib.stream_ptr()))
         return dict(loss=stats[0], logits=logits)
 
     def debug_read(self, name: str, B: int) -> np.ndarray:

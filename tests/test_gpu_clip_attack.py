@@ -1,0 +1,397 @@
+"""-m gpu: per-clip attacks (one perturbation row delta_b per clip).  The oracle is "a per-clip step on B clips is B independent
+universal steps at batch 1": every row is checked against oracle.projections / oracle.pgd run on that clip alone."""
+import json
+import os
+import socket
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from gpu_util import rel_err
+from oracle import pgd as opgd, projections as OP, wav2vec2 as OW
+from oracle.gen_cases import PGD_TEXTS, cli_to_args
+from paa_amd import _lib, arch as A, runtime, synth
+from paa_amd.model import PaaModel
+from paa_amd.training_utils import build
+from paa_amd.training_utils.clip_attack import ClipStepper, compose_rows
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NORMS = ["l2", "linf", "snr", "tv", "fletcher_munson", "min_max_freqs", "max_phon"]
+SCALE_NORMS = ("l2", "snr", "tv", "fletcher_munson")
+ROW_LOCAL = ("linf", "min_max_freqs", "max_phon")
+PROJ_ARGS = ["--snr_db", "40", "--linf_size", "0.01"]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _fresh_projection_contexts():
+    """These tests load max_phon contours into the process-wide projection contexts (runtime.get_proj); drop the contexts
+    afterwards so that later test modules start from fresh ones, as they would without this module."""
+    yield
+    torch.cuda.synchronize()
+    runtime._PROJ.clear()
+
+
+def _rows_input(rows, L, seed=5):
+    """Rows whose amplitudes differ by up to 100x (1, 0.1, 0.01, 1, ...) and clean clips of their own."""
+    amp = np.array([10.0 ** -(r % 3) for r in range(rows)], dtype=np.float32)[:, None]
+    src = np.stack([synth.normal(synth.key_of(f"rowsrc{r}", seed), L) for r in range(rows)]).astype(np.float32) * amp
+    clean = synth.clean_audio(rows, L, seed=seed)
+    return src, clean
+
+
+def _proj_rows(pr, prm, src, clean, rows, L):
+    out = torch.empty_like(src)
+    _lib.check(_lib.lib().paa_project_rows(pr.h, prm, _lib.ptr(src), _lib.ptr(out), rows, _lib.ptr(clean), L, _lib.stream_ptr()))
+    return out
+
+
+def _proj_one(pr, prm, src_row, clean_row, L):
+    out = torch.empty_like(src_row)
+    _lib.check(_lib.lib().paa_project_to(pr.h, prm, _lib.ptr(src_row), _lib.ptr(out), 1, _lib.ptr(clean_row), 1, L,
+                                         _lib.stream_ptr()))
+    return out
+
+
+@pytest.mark.parametrize("norm", NORMS + ["min_max_freqs+tv"])
+def test_project_rows_vs_oracle(norm):
+    args = cli_to_args(norm, PROJ_ARGS)
+    spl = OP.spl_thresh_tensor(args)
+    parts = norm.split("+")
+    for L in (16000, 160000, 24001):
+        for rows in (1, 3, 32):
+            src_np, clean_np = _rows_input(rows, L)
+            src, clean = torch.from_numpy(src_np).cuda(), torch.from_numpy(clean_np).cuda()
+            pr = runtime.get_proj(args, src.device, rows, L)
+            pr.set_spl_thresh(spl.cuda())
+            got = src.clone()
+            inplace = src.clone()
+            for n in parts:
+                a = types.SimpleNamespace(**{**vars(args), "norm_type": n})
+                got = _proj_rows(pr, runtime.params_of(a), got, clean, rows, L)
+                _lib.check(_lib.lib().paa_project_rows(pr.h, runtime.params_of(a), _lib.ptr(inplace), _lib.ptr(inplace), rows,
+                                                       _lib.ptr(clean), L, _lib.stream_ptr()))
+            torch.cuda.synchronize()
+            assert torch.equal(inplace, got), (norm, L, rows)              # in place == out of place
+            g = got.cpu().numpy()
+            worst = 0.0
+            for r in range(rows):
+                ref = torch.from_numpy(src_np[r:r + 1])
+                with torch.no_grad():
+                    for n in parts:
+                        ref = OP.perturbation_constraint(ref, torch.from_numpy(clean_np[r:r + 1]),
+                                                         types.SimpleNamespace(**{**vars(args), "norm_type": n}), spl)
+                worst = max(worst, rel_err(g[r], ref.numpy()[0]))
+            # every row against the one-row universal projection of that row alone
+            same = []
+            for r in range(rows):
+                one = src[r:r + 1].clone()
+                for n in parts:
+                    a = types.SimpleNamespace(**{**vars(args), "norm_type": n})
+                    one = _proj_one(pr, runtime.params_of(a), one, clean[r:r + 1].contiguous(), L)
+                same.append(torch.equal(one[0], got[r]))
+            print(f"{norm} L={L} rows={rows}: max row rel err vs oracle {worst:.2e}; rows bit-equal to the one-row call "
+                  f"{sum(same)}/{rows}")
+            assert worst < 2e-5, (norm, L, rows, worst)
+            if rows == 1 or all(n in ROW_LOCAL for n in parts) or all(n in ("l2", "snr", "tv") for n in parts):
+                assert all(same), (norm, L, rows)
+            if rows >= 3 and parts[-1] in SCALE_NORMS:
+                # the scale factor of each row is its own: 100x amplitudes -> scale factors far apart
+                s0 = float((got[0].abs().max() / src[0].abs().max()).item())
+                s2 = float((got[2].abs().max() / src[2].abs().max()).item())
+                assert s0 > 0 and s2 > 0 and max(s0, s2) / min(s0, s2) > 10, (norm, L, s0, s2)
+
+
+def test_project_rows_needs_clean():
+    args = cli_to_args("snr", PROJ_ARGS)
+    pr = runtime.get_proj(args, "cuda", 2, 16000)
+    src = torch.zeros(2, 16000, device="cuda")
+    for n in ("snr", "tv"):
+        a = types.SimpleNamespace(**{**vars(args), "norm_type": n})
+        with pytest.raises(ValueError, match="clean_audio"):
+            _lib.check(_lib.lib().paa_project_rows(pr.h, runtime.params_of(a), _lib.ptr(src), _lib.ptr(src), 2, None, 16000,
+                                                   _lib.stream_ptr()))
+
+
+def _model_case(a, B, L, dtype, texts, args):
+    sdn = A.rule_weights(a)
+    m = PaaModel(a, sdn, B, L, dtype)
+    clean = torch.from_numpy(synth.clean_audio(B, L)).cuda()
+    labels = opgd.make_labels(texts, args, B)
+    return m, clean, labels
+
+
+@pytest.mark.parametrize("variant", ["group", "layer", "large-lv60"])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_model_rows(variant, dtype):
+    args = cli_to_args("snr", [])
+    if variant == "large-lv60":
+        a, B, L = A.LARGE_LV60, 3, 32000
+    else:
+        a, B, L = (A.tiny("group", False) if variant == "group" else A.tiny("layer", True)), 3, 8000
+    m, clean, labels = _model_case(a, B, L, dtype, PGD_TEXTS[:B], args)
+    p = (torch.from_numpy(synth.perturbation(L)) * np.float32(1e-2)).cuda()
+    # every row equal to p: the universal call, bit for bit, and the rows sum to the universal gradient
+    u = m.fwd_bwd(clean, p, labels, +1)
+    rr = m.fwd_bwd(clean, p.expand(B, L).contiguous(), labels, +1)
+    torch.cuda.synchronize()
+    assert rr["grad"].shape == (B, L) and u["grad"].shape == (1, L)
+    assert torch.equal(rr["logits"], u["logits"]) and torch.equal(rr["loss"], u["loss"])
+    e_sum = rel_err(rr["grad"].double().sum(0).cpu().numpy(), u["grad"].double()[0].cpu().numpy())
+    assert e_sum < 1e-6, e_sum
+    # distinct rows: row b equals the batch-1 universal call on clip b
+    d = torch.from_numpy(np.stack([synth.normal(synth.key_of(f"d{b}", 5), L) for b in range(B)]).astype(np.float32) * 1e-2).cuda()
+    rd = m.fwd_bwd(clean, d, labels, +1)
+    fw = m.forward(clean, d, labels, clamp=True)
+    torch.cuda.synchronize()
+    assert torch.equal(fw["logits"], rd["logits"])
+    bit = []
+    for b in range(B):
+        r1 = m.fwd_bwd(clean[b:b + 1].contiguous(), d[b:b + 1].contiguous(), labels[b:b + 1], +1)
+        torch.cuda.synchronize()
+        e = rel_err(rd["grad"][b].cpu().numpy(), r1["grad"][0].cpu().numpy())
+        bit.append(torch.equal(rd["grad"][b], r1["grad"][0]))
+        assert e < 1e-5, (b, e)
+    print(f"{variant} {dtype}: per-clip gradient rows bit-equal to the batch-1 call: {bit}; row sum vs universal {e_sum:.2e}")
+    with pytest.raises(ValueError, match="rows"):
+        m.fwd_bwd(clean, d[:2].contiguous(), labels, +1)
+
+
+def test_clamp_mask_per_clip():
+    """Clean samples near +-1 where only row 1's delta leaves [-1, 1]: row 1's gradient is exactly 0 there, the other rows' is not."""
+    a = A.tiny()
+    B, L = 3, 8000
+    args = cli_to_args("snr", [])
+    m, clean, labels = _model_case(a, B, L, "fp32", PGD_TEXTS[:B], args)
+    idx = torch.arange(1000, 7000, 7, device="cuda")
+    clean[:, idx] = 0.999
+    d = torch.full((B, L), 1e-4, device="cuda")
+    d[1, idx] = 0.01                       # 0.999 + 0.01 > 1: clamped in clip 1 only
+    r = m.fwd_bwd(clean, d, labels, +1)
+    torch.cuda.synchronize()
+    g = r["grad"]
+    assert torch.all(g[1, idx] == 0)
+    assert torch.count_nonzero(g[0, idx]) > 0.9 * idx.numel() and torch.count_nonzero(g[2, idx]) > 0.9 * idx.numel()
+    x_adv = compose_rows(clean, d)
+    assert torch.equal(x_adv, torch.clamp(clean + d, -1.0, 1.0))
+    assert float(x_adv[1, idx].max()) == 1.0 and float(x_adv[0, idx].max()) < 1.0
+    mask = torch.ones(L, dtype=torch.bool, device="cuda")
+    mask[idx] = False
+    assert torch.count_nonzero(g[1, mask]) > 0.9 * int(mask.sum())
+
+
+def _clip_step_vs_oracle(a, L, B, args, texts):
+    args.device = "cuda"
+    sdn = A.rule_weights(a)
+    sd = OW.to_torch(sdn)
+    clean = torch.from_numpy(synth.clean_audio(B, L))
+    d0 = torch.from_numpy(np.stack([synth.normal(synth.key_of(f"d{b}", 5), L) for b in range(B)]).astype(np.float32) * 1e-3)
+    labels = opgd.make_labels(texts, args, B)
+    spl = OP.spl_thresh_tensor(args)
+    m = PaaModel(a, sdn, B, L, "fp32")
+    st = ClipStepper(m, args, L, None, build.init_phon_threshold_tensor(args))
+    d = d0.cuda()
+    r = st.step(d, clean.cuda(), labels)
+    torch.cuda.synchronize()
+    g = r["grad"].cpu().numpy()
+    loss_ref = 0.0
+    for b in range(B):
+        ref = opgd.pgd_step(sd, a, args, clean[b:b + 1], labels[b:b + 1], d0[b:b + 1], spl)
+        loss_ref += float(ref["loss"])
+        gref = ref["grad"].numpy()[0]
+        e_g = rel_err(g[b], gref)
+        flips = float((np.sign(g[b]) != np.sign(gref)).mean())
+        with torch.no_grad():
+            pexp = OP.perturbation_constraint(d0[b:b + 1] + args.lr * torch.from_numpy(g[b:b + 1]).sign(), clean[b:b + 1], args, spl)
+        e_p = rel_err(d[b].cpu().numpy(), pexp.numpy()[0])
+        print(f"clip {b}: grad rel {e_g:.2e} flips {flips:.2e} delta' rel {e_p:.2e}")
+        assert e_g < 5e-3 and flips < 5e-3 and e_p < 5e-5, (b, e_g, flips, e_p)
+    e_loss = abs(float(r["loss"]) - loss_ref) / abs(loss_ref)
+    print(f"loss rel {e_loss:.2e}")
+    assert np.isfinite(loss_ref) and e_loss < 2e-4
+
+
+@pytest.mark.parametrize("norm", ["snr", "fletcher_munson", "max_phon"])
+def test_clip_step_vs_oracle_base(norm):
+    args = cli_to_args(norm, ["--snr_db", "40"] if norm == "snr" else [])
+    _clip_step_vs_oracle(A.BASE, 16000, 2, args, PGD_TEXTS[:2])
+
+
+def test_clip_step_vs_oracle_large_targeted_max_phon():
+    args = cli_to_args("max_phon", ["--attack_mode", "targeted", "--target", "delete", "--target_reps", "5", "--max_phon_level", "20"])
+    _clip_step_vs_oracle(A.LARGE_LV60, 32000, 2, args, ["ignored", "ignored"])
+
+
+def test_replay_equals_eager_pgd():
+    a = A.tiny()
+    B, L = 3, 8000
+    args = cli_to_args("max_phon", [])
+    args.device = "cuda"
+    m, clean, labels = _model_case(a, B, L, "fp32", PGD_TEXTS[:B], args)
+    st = ClipStepper(m, args, L, None, build.init_phon_threshold_tensor(args))
+    d0 = torch.from_numpy(np.stack([synth.normal(synth.key_of(f"d{b}", 5), L) for b in range(B)]).astype(np.float32) * 1e-2).cuda()
+    de = d0.clone()
+    for _ in range(3):
+        st.step(de, clean, labels)
+    dg = d0.clone()
+    g, r = st.capture(dg, clean, labels)
+    dg.copy_(d0)
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(dg, de)
+    assert torch.isfinite(r["loss"]).item()
+
+
+def test_adam_replay_and_torch_adam():
+    a = A.tiny()
+    B, L = 3, 8000
+    args = cli_to_args("snr", ["--snr_db", "40"])
+    args.device = "cuda"
+    args.lr = 1e-3
+    m, clean, labels = _model_case(a, B, L, "fp32", PGD_TEXTS[:B], args)
+    d0 = torch.from_numpy(np.stack([synth.normal(synth.key_of(f"d{b}", 5), L) for b in range(B)]).astype(np.float32) * 1e-2).cuda()
+    # eager device Adam vs torch.optim.Adam fed the same gradients, 5 steps, with a StepLR in between
+    de = torch.nn.Parameter(d0.clone())
+    opt = torch.optim.Adam([de], lr=args.lr)
+    sched = torch.optim.lr_scheduler.StepLR(opt, step_size=2, gamma=0.5)
+    st = ClipStepper(m, args, L, optimizer=opt)
+    dt = torch.nn.Parameter(d0.clone())
+    ot = torch.optim.Adam([dt], lr=args.lr)
+    stt = torch.optim.lr_scheduler.StepLR(ot, step_size=2, gamma=0.5)
+    proj = runtime.get_proj(args, "cuda", B, L)
+    prm = runtime.params_of(args)
+    for _ in range(5):
+        r = st.step(de.data, clean, labels)
+        torch.cuda.synchronize()
+        ot.zero_grad()
+        dt.grad = -r["grad"].clone()
+        ot.step()
+        with torch.no_grad():
+            _lib.check(_lib.lib().paa_project_rows(proj.h, prm, _lib.ptr(dt.data), _lib.ptr(dt.data), B, _lib.ptr(clean), L,
+                                                   _lib.stream_ptr()))
+            de_ref = dt.data
+        torch.cuda.synchronize()
+        assert torch.equal(de.data, de_ref)
+        # keep the two trajectories on the same delta so that the gradients stay equal
+        sched.step()
+        stt.step()
+    s, t = opt.state[de], ot.state[dt]
+    assert torch.equal(s["exp_avg"], t["exp_avg"]) and torch.equal(s["exp_avg_sq"], t["exp_avg_sq"]) and float(s["step"]) == 5
+    # captured Adam replay == eager Adam steps, bit for bit
+    dr = torch.nn.Parameter(d0.clone())
+    o2 = torch.optim.Adam([dr], lr=args.lr)
+    st2 = ClipStepper(m, args, L, optimizer=o2)
+    g, _ = st2.capture(dr.data, clean, labels)
+    dq = torch.nn.Parameter(d0.clone())
+    o3 = torch.optim.Adam([dq], lr=args.lr)
+    st3 = ClipStepper(m, args, L, optimizer=o3)
+    for _ in range(3):
+        g.replay()
+        st3.step(dq.data, clean, labels)
+    torch.cuda.synchronize()
+    assert torch.equal(dr.data, dq.data)
+    assert torch.equal(o2.state[dr]["exp_avg_sq"], o3.state[dq]["exp_avg_sq"])
+
+
+@pytest.mark.parametrize("case", ["base_32x10s", "base_16x30s"])
+def test_full_size_rows(case):
+    if case == "base_32x10s":
+        B, L = 32, 160000
+        args = cli_to_args("snr", ["--snr_db", "40"])
+        texts = [PGD_TEXTS[b % 4] for b in range(B)]
+    else:
+        B, L = 16, 480000
+        args = cli_to_args("min_max_freqs+tv", [])
+        texts = [("the quick brown fox jumps over a lazy dog and runs " * 10)[:450] for _ in range(B)]
+    args.device = "cuda"
+    m, clean, labels = _model_case(A.BASE, B, L, "fp32", texts, args)
+    d0 = (torch.from_numpy(synth.perturbation(L, seed=7)) * np.float32(2e-3)).cuda().repeat(B, 1)
+    d0 *= torch.linspace(0.5, 1.5, B, device="cuda")[:, None]
+    st = ClipStepper(m, args, L)
+    d = d0.clone()
+    r = st.step(d, clean, labels)
+    torch.cuda.synchronize()
+    g = r["grad"].clone()
+    assert torch.isfinite(g).all() and torch.isfinite(d).all() and torch.isfinite(r["logits"]).all()
+    assert float(g[-1].abs().max()) > 0 and float(d[-1].abs().max()) > 0
+    for b in (0, B - 1):
+        r1 = m.fwd_bwd(clean[b:b + 1].contiguous(), d0[b:b + 1].contiguous(), labels[b:b + 1], +1)
+        torch.cuda.synchronize()
+        e = rel_err(g[b].cpu().numpy(), r1["grad"][0].cpu().numpy())
+        print(f"{case}: clip {b} gradient row vs the clip alone {e:.2e} (bit-equal {torch.equal(g[b], r1['grad'][0])})")
+        # at full size the batch of B and the single clip take different GEMM / attention tilings (~1e-5 apart, as the
+        # universal step's logits are, test_gpu_model._full_batch_checks); a wrapped offset or a short workspace is O(1)
+        assert e < 1e-4, (b, e)
+
+
+def _run_entry(extra, env_extra=None, batch_size=4):
+    """A fresh child process per rank (no exec of a process that has initialised the GPU)."""
+    env = dict(os.environ, **(env_extra or {}))
+    cmd = [sys.executable, "-m", "paa_amd.attack_clips", "--arch", "tiny", "--device", "cuda", "--audio_seconds", "0.5",
+           "--batch_size", str(batch_size), "--steps_per_epoch", "2", "--small_data", "--silent", *extra]
+    return subprocess.Popen(cmd, cwd=ROOT, env=env)
+
+
+def _results(logs):
+    path = None
+    for d, _, files in os.walk(logs):
+        if "clip_results.json" in files:
+            path = os.path.join(d, "clip_results.json")
+    assert path, logs
+    return path, json.load(open(path))
+
+
+def test_entry_point_end_to_end(tmp_path):
+    logs = str(tmp_path / "logs")
+    p = _run_entry(["--norm_type", "snr", "--snr_db", "40", "--pgd_steps", "20", "--optimizer_type", "pgd", "--lr", "1e-3",
+                    "--num_items_to_inspect", "2", "--logs_dir", logs])
+    assert p.wait(900) == 0
+    path, res = _results(logs)
+    clips = res["clips"]
+    assert len(clips) >= 2 and [c["index"] for c in clips] == list(range(len(clips)))
+    for c in clips:
+        assert np.isfinite(c["final_ctc"]) and c["l2"] > 0 and c["snr_db"] > 39.0
+    s = res["summary"]
+    print(json.dumps(s))
+    assert s["final_ctc"] > sum(c["clean_ctc"] for c in clips) / len(clips)          # untargeted: the loss went up
+    assert s["adv_wer"] >= s["clean_wer"]
+    wavs = sorted(f for f in os.listdir(os.path.dirname(path)) if f.endswith(".wav"))
+    assert wavs == ["adv_clip0.wav", "adv_clip1.wav"]
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+def test_entry_point_two_ranks_equal_one(tmp_path):
+    common = ["--norm_type", "snr", "--snr_db", "40", "--pgd_steps", "3", "--optimizer_type", "pgd", "--lr", "1e-3",
+              "--num_items_to_inspect", "0"]
+    one = str(tmp_path / "one")
+    p = _run_entry(common + ["--logs_dir", one])
+    assert p.wait(900) == 0
+    two = str(tmp_path / "two")
+    port = str(_free_port())
+    # --batch_size is per rank: 2 ranks x 2 clips = the same global batches (and the same split) as 1 rank x 4 clips
+    ps = [_run_entry(common + ["--logs_dir", two], dict(WORLD_SIZE="2", RANK=str(r), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
+                                                        MASTER_PORT=port, PAA_DIST_BACKEND="gloo"), batch_size=2) for r in range(2)]
+    codes = [q.wait(900) for q in ps]
+    assert codes == [0, 0]
+    _, r1 = _results(one)
+    _, r2 = _results(two)
+    assert [c["index"] for c in r1["clips"]] == [c["index"] for c in r2["clips"]]
+    exact = r1["clips"] == r2["clips"]
+    print(f"two ranks vs one: records identical: {exact}")
+    for c1, c2 in zip(r1["clips"], r2["clips"]):
+        assert c1["clean_wer"] == c2["clean_wer"] and c1["adv_wer"] == c2["adv_wer"]
+        for k in ("clean_ctc", "final_ctc", "l2", "linf", "snr_db"):
+            assert abs(c1[k] - c2[k]) <= 1e-5 * max(abs(c1[k]), 1e-6), (k, c1[k], c2[k])
