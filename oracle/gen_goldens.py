@@ -43,7 +43,7 @@ from training_utils import build, parser, train  # noqa: E402  (reference)
 from paa_amd import arch as A  # noqa: E402
 from paa_amd import synth  # noqa: E402
 from oracle import pgd as opgd  # noqa: E402
-from oracle.gen_cases import AMPS, LENGTHS, NORM_CASES, PGD_CASES, PGD_TEXTS, case_name  # noqa: E402
+from oracle.gen_cases import AMPS, LENGTHS, NORM_CASES, PGD_CASES, PGD_SAMPLED, PGD_TEXTS, case_name  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -185,7 +185,7 @@ def gen_pgd(proc):
         res = train.train_epoch(args=args, train_data_loader=[(clean, texts)], p=p0.clone(), model=model, epoch=0,
                                 processor=proc, interp=interp, wer_metric=_Wer(), spl_thresh=spl, optimizer=None)
         out = dict(loss=np.array([float(loss)]), avg_ctc=np.array([res.avg_ctc]), avg_wer=np.array([res.avg_wer]))
-        if a is A.BASE:
+        if name in PGD_SAMPLED:
             out["grad_samples"] = grad[0, ::13].copy()
             out["p_new_samples"] = res.p.detach().numpy()[0, ::13].copy()
             out["logits_samples"] = logits.detach().numpy()[:, ::7, :].copy()

@@ -395,3 +395,65 @@ def test_entry_point_two_ranks_equal_one(tmp_path):
         assert c1["clean_wer"] == c2["clean_wer"] and c1["adv_wer"] == c2["adv_wer"]
         for k in ("clean_ctc", "final_ctc", "l2", "linf", "snr_db"):
             assert abs(c1[k] - c2[k]) <= 1e-5 * max(abs(c1[k]), 1e-6), (k, c1[k], c2[k])
+
+
+# ---- clip lengths off the 8000-sample grid (oracle.gen_cases.ODD_LENGTHS): per-clip rows that start mid-vector ---------------------
+def test_clip_step_vs_oracle_base_odd_length():
+    """Per-clip step on the base architecture at L = 10563 (T_e = 32, three uncovered samples, L % 4 = 3: row 1 starts 12 bytes
+    past a 16-byte boundary)."""
+    _clip_step_vs_oracle(A.BASE, 10563, 2, cli_to_args("snr", ["--snr_db", "40"]), PGD_TEXTS[:2])
+
+
+def test_replay_equals_eager_odd_length():
+    """test_replay_equals_eager_pgd at L = 8737 (L % 4 = 1)."""
+    a = A.tiny()
+    B, L = 3, 8737
+    args = cli_to_args("max_phon", [])
+    args.device = "cuda"
+    m, clean, labels = _model_case(a, B, L, "fp32", PGD_TEXTS[:B], args)
+    st = ClipStepper(m, args, L, None, build.init_phon_threshold_tensor(args))
+    d0 = torch.from_numpy(np.stack([synth.normal(synth.key_of(f"d{b}", 5), L) for b in range(B)]).astype(np.float32) * 1e-2).cuda()
+    de = d0.clone()
+    for _ in range(3):
+        st.step(de, clean, labels)
+    dg = d0.clone()
+    g, r = st.capture(dg, clean, labels)
+    dg.copy_(d0)
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(dg, de)
+    assert torch.isfinite(r["loss"]).item()
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_batch_independence_misaligned_rows(dtype):
+    """Tiny model, B = 5 clips of L = 8737 samples (L % 4 = 1: no row after the first is 16-byte aligned).  Every clip run alone
+    gives the logits and the CTC loss it has inside the batch, and every per-clip gradient row of paa_model_fwd_bwd_rows equals
+    the one-clip call bit for bit; samples no conv0 window covers get an exact 0 in every row."""
+    a = A.tiny()
+    B, L = 5, 8737
+    args = cli_to_args("snr", [])
+    texts = (PGD_TEXTS * 2)[:B]
+    m, clean, labels = _model_case(a, B, L, dtype, texts, args)
+    d = torch.from_numpy(np.stack([synth.normal(synth.key_of(f"d{b}", 5), L) for b in range(B)]).astype(np.float32) * 1e-2).cuda()
+    r = m.fwd_bwd(clean, d, labels, +1)
+    torch.cuda.synchronize()
+    logits, grad = r["logits"].clone(), r["grad"].clone()
+    nll = m.debug_read("nll", B).copy()
+    assert np.isfinite(nll).all() and abs(float(r["loss"]) - float(nll.astype(np.float64).sum())) < 1e-4 * abs(float(r["loss"]))
+    tail = (a.feat_lengths(L)[0] - 1) * a.conv_stride[0] + a.conv_kernel[0]
+    assert torch.all(grad[:, tail:] == 0)
+    tol = {"fp32": 3e-4, "bf16": 6e-2}[dtype]
+    for b in range(B):
+        one = (clean[b:b + 1].contiguous(), d[b:b + 1].contiguous(), labels[b:b + 1])
+        f1 = m.forward(*one, clamp=True)
+        torch.cuda.synchronize()
+        e = rel_err(f1["logits"].cpu().numpy(), logits[b:b + 1].cpu().numpy())
+        e_l = abs(float(f1["loss"]) - float(nll[b])) / abs(float(nll[b]))
+        r1 = m.fwd_bwd(*one, +1)
+        torch.cuda.synchronize()
+        print(f"{dtype} clip {b}: logits {e:.2e} nll {e_l:.2e} grad row bit-equal {torch.equal(r1['grad'][0], grad[b])}")
+        assert e < tol and e_l < tol, (b, e, e_l)
+        assert float(grad[b].abs().max()) > 0
+        assert torch.equal(r1["grad"][0], grad[b]), (b, rel_err(r1["grad"][0].cpu().numpy(), grad[b].cpu().numpy()))
