@@ -28,10 +28,11 @@ typedef enum {
     PAA_ERR_MISSING = 6      /* a required weight tensor was not supplied */
 } paa_status;
 
-/* args.norm_type (training_utils/parser.py:38-40), in the parser's order of choices */
+/* args.norm_type (training_utils/parser.py:38-40), in the parser's order of choices.  PAA_NORM_MASKING (extension): clip every
+ * bin of the perturbation's STFT to the clean clip's frequency-masking threshold (paa_masking_threshold), default geometry only */
 typedef enum {
     PAA_NORM_L2 = 0, PAA_NORM_LINF = 1, PAA_NORM_SNR = 2, PAA_NORM_TV = 3,
-    PAA_NORM_FLETCHER_MUNSON = 4, PAA_NORM_MIN_MAX_FREQS = 5, PAA_NORM_MAX_PHON = 6
+    PAA_NORM_FLETCHER_MUNSON = 4, PAA_NORM_MIN_MAX_FREQS = 5, PAA_NORM_MAX_PHON = 6, PAA_NORM_MASKING = 7
 } paa_norm;
 
 /* The fields of the reference's argparse namespace that the hot path reads (parser.py:10-66). */
@@ -41,10 +42,11 @@ typedef struct {
     float min_freq_attack, max_freq_attack, phon_reference_db;
     float lr;                 /* args.lr, PGD step size (train.py:161) */
     int32_t direction;        /* +1 untargeted, -1 targeted (train.py:124) */
+    float masking_margin_db;  /* masking norm: dB added to the threshold (args.masking_margin_db, extension) */
 } paa_params;
 
 const char* paa_last_error(void);
-/* 300 = this header; 301 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
+/* 310 = this header; 311 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
  * tools/ only).  Bindings refuse other values. */
 int paa_version(void);
 /* sizeof(paa_params), sizeof(paa_arch), sizeof(paa_tensor), sizeof(paa_gemm_desc): layout check for bindings */
@@ -101,6 +103,22 @@ paa_status paa_batch_stats(paa_proj* h, const float* d_clean, int B, int L, floa
 paa_status paa_project_ext(paa_proj* h, const paa_params* prm, float* d_p, int rows_p,
                            const float* d_clean_stats /* device [2] */, const float* d_clip_count /* device [1] or NULL */,
                            double clean_numel /* used when d_clip_count is NULL */, int L, void* stream);
+
+/* ---- masking norm (PAA_NORM_MASKING, extension) -------------------------------------------------------
+ * MPEG-1 psychoacoustic model 1 threshold of each clean clip on the default frame geometry (n_fft = win = 1024, hop = 256;
+ * any other geometry: PAA_ERR_ARG).  P = 10 log10(|STFT(clean_b)|^2 + 1e-20), Pmax_b its maximum over the clip, and
+ * P' = P - Pmax_b + 96; tonal maskers are the strict local maxima of P' at or above the threshold in quiet that no louder masker
+ * within 0.5 Bark suppresses; theta(t, k) = 10 log10(sum_j 10^(T_j(k) / 10) + [z_k > 1] 10^(ATH_k / 10)) (dB, -inf where the
+ * sum is 0).  The projection clips S = STFT(delta) to A = 10^((theta + masking_margin_db - 96 + Pmax_b) / 20) per bin, phase
+ * kept, then iSTFT with the _align_to tail rule.  paa_project / paa_project_to: rows of d_p under min_b A_b (the universal
+ * perturbation hides under every clip of the batch); paa_project_rows: row b under A_b.  d_clean is required
+ * (PAA_ERR_NEED_CLEAN); paa_project_ext and paa_spectrum_project refuse the norm (PAA_ERR_BAD_NORM).  The threshold is
+ * recomputed from d_clean inside every projection call (a captured step follows the clean buffer); the workspace is
+ * allocated by paa_proj_create (B <= max_batch).
+ * paa_masking_threshold: d_theta (B, T, F) theta in dB, frame-major like paa_stft; d_psd (B, T, F) P' (nullable);
+ * d_pmax (B) Pmax_b (nullable). */
+paa_status paa_masking_threshold(paa_proj* h, const float* d_clean, int B, int L, float* d_psd, float* d_theta, float* d_pmax,
+                                 void* stream);
 
 /* core/fourier_transforms.py:4-29 compute_stft: (B, L) -> d_out (B, T, F) complex64 interleaved,
  * T = 1 + L / hop; the (B, F, T) tensor the reference returns is the transpose-view of this. */

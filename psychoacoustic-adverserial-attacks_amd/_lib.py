@@ -9,18 +9,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PAA_EXTRA_HIPCC_FLAGS (tools/ only: diagnostic builds, see build_ext.py) selects the diagnostic library built next to the shipped one
 LIB_PATH = os.path.join(HERE, "libpaa_hip_exp.so" if os.environ.get("PAA_EXTRA_HIPCC_FLAGS", "").strip() else "libpaa_hip.so")
 
-ABI_VERSIONS = (300, 301)      # include/paa_hip.h paa_version: 301 = the same ABI built with -DPAA_EXPERIMENTS
+ABI_VERSIONS = (310, 311)      # include/paa_hip.h paa_version: 311 = the same ABI built with -DPAA_EXPERIMENTS
 
 PAA_OK, PAA_ERR_BAD_NORM, PAA_ERR_NEED_CLEAN, PAA_ERR_SIZE, PAA_ERR_HIP, PAA_ERR_ARG, PAA_ERR_MISSING = range(7)
 
-NORM_IDS = {"l2": 0, "linf": 1, "snr": 2, "tv": 3, "fletcher_munson": 4, "min_max_freqs": 5, "max_phon": 6}
+NORM_IDS = {"l2": 0, "linf": 1, "snr": 2, "tv": 3, "fletcher_munson": 4, "min_max_freqs": 5, "max_phon": 6, "masking": 7}
 
 
 class PaaParams(C.Structure):
     _fields_ = [("norm_type", C.c_int32), ("l2_size", C.c_float), ("linf_size", C.c_float), ("snr_db", C.c_float),
                 ("tv_epsilon", C.c_float), ("fm_epsilon", C.c_float), ("min_freq_attack", C.c_float),
                 ("max_freq_attack", C.c_float), ("phon_reference_db", C.c_float), ("lr", C.c_float),
-                ("direction", C.c_int32)]
+                ("direction", C.c_int32), ("masking_margin_db", C.c_float)]
 
 
 class PaaArch(C.Structure):
@@ -72,6 +72,8 @@ _SIGS = {
     "paa_project_ext": (C.c_int, [C.c_void_p, C.POINTER(PaaParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
                                   C.c_int, C.c_void_p]),
     "paa_batch_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "paa_masking_threshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "paa_stft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "paa_istft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "paa_sign_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "paa_common.h"
+#include "mask_kernels.h"
 #include "spec_kernels.h"
 
 namespace paa {
@@ -480,15 +481,22 @@ struct paa_proj {
     double* d_part = nullptr;
     float* d_scal = nullptr;
     size_t frames_floats = 0;
+    // masking norm (default geometry only): bound / threshold workspace (max_batch, Tmax, F), pass 1's per-workgroup maxima,
+    // and the per-bin tables [z | quiet | ath] (3 F floats) + packed windows (F ints)
+    float* d_mask = nullptr;
+    float* d_mpart = nullptr;
+    float* d_mtab = nullptr;
+    int* d_mwin = nullptr;
+    int mask_kA = 0;
 };
 
 extern "C" const char* paa_last_error(void) { return paa::g_err.c_str(); }
-// 300 + 1 if the library was built with -DPAA_EXPERIMENTS (diagnostic configurations and environment switches present)
+// 310 + 1 if the library was built with -DPAA_EXPERIMENTS (diagnostic configurations and environment switches present)
 extern "C" int paa_version(void) {
 #ifdef PAA_EXPERIMENTS
-    return 301;
+    return 311;
 #else
-    return 300;
+    return 310;
 #endif
 }
 
@@ -546,6 +554,17 @@ extern "C" paa_status paa_proj_create(paa_proj** out, int n_fft, int hop, int wi
     PC(hipMemcpy(h->d_win, w.data(), sizeof(float) * n_fft, hipMemcpyHostToDevice));
     PC(hipMemcpy(h->d_fm, fm.data(), sizeof(float) * 10 * F, hipMemcpyHostToDevice));
     PC(hipMemset(h->d_scal, 0, sizeof(float) * 8));
+    if (n_fft == 1024 && hop == 256 && win == 1024) {
+        std::vector<float> mt(3 * F);
+        std::vector<int> mw(F);
+        mask_tables(sr, mt.data(), mt.data() + F, mt.data() + 2 * F, mw.data(), &h->mask_kA);
+        PC(hipMalloc(&h->d_mask, sizeof(float) * (size_t)max_batch * Tmax * F));
+        PC(hipMalloc(&h->d_mpart, sizeof(float) * (size_t)max_batch * spec_psd_groups(Tmax)));
+        PC(hipMalloc(&h->d_mtab, sizeof(float) * 3 * F));
+        PC(hipMalloc(&h->d_mwin, sizeof(int) * F));
+        PC(hipMemcpy(h->d_mtab, mt.data(), sizeof(float) * 3 * F, hipMemcpyHostToDevice));
+        PC(hipMemcpy(h->d_mwin, mw.data(), sizeof(int) * F, hipMemcpyHostToDevice));
+    }
 #undef PC
     if (spl_thresh) {
         paa_status s = paa_proj_set_spl_thresh(h, spl_thresh);
@@ -569,7 +588,8 @@ extern "C" paa_status paa_debug_spec_stamps(paa_proj* h, long long* host, int n)
 
 extern "C" void paa_proj_destroy(paa_proj* h) {
     if (!h) return;
-    void* ptrs[] = {h->d_tw, h->d_win, h->d_fm, h->d_thr, h->d_thr_max, h->d_frames, h->d_part, h->d_scal};
+    void* ptrs[] = {h->d_tw, h->d_win, h->d_fm, h->d_thr, h->d_thr_max, h->d_frames, h->d_part, h->d_scal,
+                    h->d_mask, h->d_mpart, h->d_mtab, h->d_mwin};
     for (void* q : ptrs) if (q) (void)hipFree(q);
     delete h;
 }
@@ -600,7 +620,30 @@ static SpecArgs spec_args(const paa_proj* h, int L, int T, int out_len) {
     return a;
 }
 static int spec_op_of(int norm) {
-    return norm == PAA_NORM_MIN_MAX_FREQS ? SOP_MINMAX : norm == PAA_NORM_MAX_PHON ? SOP_PHON : norm == PAA_NORM_FLETCHER_MUNSON ? SOP_FM : SOP_NONE;
+    return norm == PAA_NORM_MIN_MAX_FREQS ? SOP_MINMAX : norm == PAA_NORM_MAX_PHON ? SOP_PHON : norm == PAA_NORM_FLETCHER_MUNSON ? SOP_FM
+         : norm == PAA_NORM_MASKING ? SOP_MASK : SOP_NONE;
+}
+
+// Masking threshold of the clean clips (B, L) into h->d_mask (passes 1 and 2 of mask_kernels.hip): theta (dB) into d_theta when
+// given, else the magnitude bound A in place in h->d_mask; with min_rows, pass 3 leaves min_b A_b in row 0.
+static paa_status masking_pass(paa_proj* h, const float* d_clean, int B, int L, float margin, float* d_psd, float* d_theta,
+                               float* d_pmax, bool min_rows, hipStream_t st) {
+    if (!d_clean || B < 1) PAA_FAIL(PAA_ERR_NEED_CLEAN, "masking projection requires clean_audio");
+    if (!fused_geometry(h) || !h->d_mask)
+        PAA_FAIL(PAA_ERR_ARG, "masking needs n_fft = win_length = 1024, hop_length = 256 (got %d / %d / %d)", h->n_fft, h->win, h->hop);
+    PAA_TRY(check_rows(h, B, L, "masking"));
+    const int T = 1 + L / h->hop;
+    SpecArgs sa = spec_args(h, L, T, 0);
+    sa.x = d_clean; sa.psd = h->d_mask; sa.pmax_part = h->d_mpart;
+    PAA_TRY(spec_psd(sa, B, st));
+    MaskArgs ma{};
+    ma.P = h->d_mask; ma.part = h->d_mpart; ma.nparts = spec_psd_groups(T);
+    ma.out = d_theta ? d_theta : h->d_mask; ma.psd = d_psd; ma.pmax = d_pmax;
+    ma.tab = MaskTables{h->d_mtab, h->d_mtab + h->F, h->d_mtab + 2 * h->F, h->d_mwin, h->mask_kA};
+    ma.T = T; ma.bound = d_theta ? 0 : 1; ma.margin = margin;
+    PAA_TRY(mask_threshold(ma, B, st));
+    if (min_rows && !d_theta) PAA_TRY(mask_min_rows(h->d_mask, B, (int64_t)T * h->F, st));
+    return PAA_OK;
 }
 
 template <int OP>
@@ -654,13 +697,20 @@ static paa_status project_impl(paa_proj* h, const paa_params* prm, float* d_p, i
     const int nt = prm->norm_type;
     const int64_t n = (int64_t)rows_p * L;
     if (rows_p < 1 || L < 2) PAA_FAIL(PAA_ERR_SIZE, "paa_project: rows_p=%d L=%d", rows_p, L);
-    if (nt < PAA_NORM_L2 || nt > PAA_NORM_MAX_PHON) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", nt);
-    const bool spectral = nt == PAA_NORM_FLETCHER_MUNSON || nt == PAA_NORM_MIN_MAX_FREQS || nt == PAA_NORM_MAX_PHON;
+    if (nt < PAA_NORM_L2 || nt > PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", nt);
+    if (nt == PAA_NORM_MASKING && d_ext) PAA_FAIL(PAA_ERR_BAD_NORM, "masking projection needs the clean clips, not their statistics");
+    const bool spectral = nt == PAA_NORM_FLETCHER_MUNSON || nt == PAA_NORM_MIN_MAX_FREQS || nt == PAA_NORM_MAX_PHON ||
+                          nt == PAA_NORM_MASKING;
+    if (nt == PAA_NORM_MASKING) {      // the bound of every clip, then its minimum over the clips (the universal perturbation hides under all)
+        PAA_TRY(check_rows(h, rows_p, L, "paa_project"));
+        PAA_TRY(masking_pass(h, d_clean, B, L, prm->masking_margin_db, nullptr, nullptr, nullptr, true, st));
+    }
     if (spectral && fused_geometry(h)) {
         // one fused launch STFT -> per-bin op -> iSTFT + overlap-add (spec_kernels.hip), then the scale / copy-back launch
         PAA_TRY(check_rows(h, rows_p, L, "paa_project"));
         const int T = 1 + L / h->hop;
         SpecArgs a = spec_args(h, L, T, L);
+        a.mask = h->d_mask; a.mask_rs = 0;
         a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
         a.x = d_src ? d_src : d_p;
         a.out = d_src ? d_p : h->d_frames;                     // in place: through the workspace (neighbouring workgroups re-read the halo)
@@ -808,12 +858,16 @@ static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const fl
         }
         case PAA_NORM_FLETCHER_MUNSON:
         case PAA_NORM_MIN_MAX_FREQS:
-        case PAA_NORM_MAX_PHON: {
+        case PAA_NORM_MAX_PHON:
+        case PAA_NORM_MASKING: {
             PAA_TRY(check_rows(h, rows, L, "paa_project_rows"));
             const bool fm = nt == PAA_NORM_FLETCHER_MUNSON;
             const int T = 1 + L / h->hop;
+            if (nt == PAA_NORM_MASKING)        // row r under its own clip's bound
+                PAA_TRY(masking_pass(h, d_clean, rows, L, prm->masking_margin_db, nullptr, nullptr, nullptr, false, st));
             if (fused_geometry(h)) {
                 SpecArgs a = spec_args(h, L, T, L);
+                a.mask = h->d_mask; a.mask_rs = (int64_t)T * h->F;
                 a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
                 a.x = d_src;
                 a.out = in_place ? h->d_frames : d_dst;
@@ -862,7 +916,7 @@ extern "C" paa_status paa_project_rows(paa_proj* h, const paa_params* prm, const
     if (rows < 1 || L < 2) PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d L=%d", rows, L);
     if (rows > h->max_batch || L > h->max_len)
         PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d L=%d exceeds max_batch=%d / max_len=%d", rows, L, h->max_batch, h->max_len);
-    if (prm->norm_type < PAA_NORM_L2 || prm->norm_type > PAA_NORM_MAX_PHON) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", prm->norm_type);
+    if (prm->norm_type < PAA_NORM_L2 || prm->norm_type > PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", prm->norm_type);
     if (d_src != d_dst) {
         const float* lo = d_src < d_dst ? d_src : d_dst;
         const float* hi = d_src < d_dst ? d_dst : d_src;
@@ -885,7 +939,7 @@ extern "C" paa_status paa_spectrum_project(paa_proj* h, const paa_params* prm, c
     if (h->F != 513) PAA_FAIL(PAA_ERR_ARG, "paa_spectrum_project: n_fft=%d (only 1024 is built)", h->n_fft);
     const int nt = prm->norm_type;
     const int op = spec_op_of(nt);
-    if (op == SOP_NONE) PAA_FAIL(PAA_ERR_BAD_NORM, "paa_spectrum_project: norm_type %d is not a frequency-domain projection", nt);
+    if (op == SOP_NONE || op == SOP_MASK) PAA_FAIL(PAA_ERR_BAD_NORM, "paa_spectrum_project: norm_type %d is not a frequency-domain projection", nt);
     hipStream_t st = (hipStream_t)stream;
     SpecArgs a = spec_args(h, 0, T, 0);
     a.part = h->d_part;
@@ -902,6 +956,13 @@ extern "C" paa_status paa_spectrum_project(paa_proj* h, const paa_params* prm, c
     PAA_LAUNCH_CHECK();
     a.S_out = d_S_out; a.part = nullptr;                     // pass 2: S * predicated scale
     return spec_apply(a, SOP_NONE, B, h->d_scal, nullptr, st);
+}
+
+// The masking threshold of the clean clips d_clean (B, L): theta (B, T, F) dB, optionally P - Pmax + 96 (B, T, F) and Pmax (B).
+extern "C" paa_status paa_masking_threshold(paa_proj* h, const float* d_clean, int B, int L, float* d_psd, float* d_theta,
+                                            float* d_pmax, void* stream) {
+    if (!h || !d_theta) PAA_FAIL(PAA_ERR_ARG, "paa_masking_threshold: null argument");
+    return masking_pass(h, d_clean, B, L, 0.f, d_psd, d_theta, d_pmax, false, (hipStream_t)stream);
 }
 
 // core/projections.py:83-113 compute_fm_weighted_norm_interp: sqrt(sum |S|^2 w(10 log10(|S|^2 + 1e-10), f)) -> d_out[0]
@@ -923,6 +984,7 @@ extern "C" paa_status paa_fm_weighted_norm(paa_proj* h, const float* d_S, int B,
 
 extern "C" paa_status paa_project_ext(paa_proj* h, const paa_params* prm, float* d_p, int rows_p, const float* d_clean_stats,
                                       const float* d_clip_count, double clean_numel, int L, void* stream) {
+    if (prm && prm->norm_type == PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "paa_project_ext: the masking norm needs the clean clips (paa_project)");
     if (!d_clean_stats) PAA_FAIL(PAA_ERR_NEED_CLEAN, "paa_project_ext: clean statistics are required");
     if (!d_clip_count && !(clean_numel > 0.0)) PAA_FAIL(PAA_ERR_ARG, "paa_project_ext: neither a device clip count nor a positive clean_numel");
     return project_impl(h, prm, d_p, rows_p, nullptr, 0, L, d_clean_stats, clean_numel, stream, nullptr, d_clip_count);

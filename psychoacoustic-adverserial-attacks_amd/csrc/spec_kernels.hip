@@ -102,6 +102,7 @@ struct BinCtx {
     int fs = F;             // row stride of the FM table (the run kernel's LDS copy pads its rows to FM_LS)
     unsigned inb = 0;       // run kernel, FM: bit `slot` set = the lane's bin of that slot lies inside the interpolator (fm[k] >= 0), read once per run
     bool have_inb = false;
+    const float* mask = nullptr;   // MASK: the bound of the frame being projected, [F]
 };
 constexpr int FM_LS = 576;  // 9 x 64: the two table rows of a lerp are then ONE ds_read2st64_b32
 
@@ -142,6 +143,11 @@ __device__ __forceinline__ float2 bin_op(float2 v, int k, const BinCtx& c, float
         }
         wsum += pw * w;
         return v;
+    } else if (OP == SOP_MASK) {                 // masking norm: S min(1, A / |S|), phase kept, a zero bin stays zero
+        const float pw = v.x * v.x + v.y * v.y;
+        const float r = c.mask[k] * __builtin_amdgcn_rsqf(pw);
+        const float sc = (pw > 0.f && r < 1.f) ? r : 1.f;
+        return make_float2(v.x * sc, v.y * sc);
     }
     return v;
 }
@@ -215,6 +221,26 @@ __device__ __forceinline__ float wave_frame(const SpecArgs& a, const BinCtx& c, 
         }
         X256 = pk_v(S[N2 / 2]);
     }
+    if (DST_SPEC && OP == SOP_PSD) {
+        // masking threshold pass 1: P = 10 log10(|X|^2 + 1e-20) via the hardware log2; returns the lane's maximum
+        float* P = a.psd + ((size_t)row * a.T + t) * F;
+        auto lv = [](v2f v) { return 3.01029995663981195f * __builtin_amdgcn_logf(v.x * v.x + v.y * v.y + 1e-20f); };
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = lane + 64 * j;
+            const float pk = lv(Xk[j]), pm = lv(Xm[j]);
+            P[k] = pk;
+            P[N2 - k] = pm;
+            mx = fmaxf(mx, fmaxf(pk, pm));
+        }
+        if (l0) {
+            const float p256 = lv(X256);
+            P[N2 / 2] = p256;
+            mx = fmaxf(mx, p256);
+        }
+        return mx;
+    }
     if (DST_SPEC) {
         float2* S = reinterpret_cast<float2*>(a.S_out) + ((size_t)row * a.T + t) * F;
 #pragma unroll
@@ -227,15 +253,17 @@ __device__ __forceinline__ float wave_frame(const SpecArgs& a, const BinCtx& c, 
         return 0.f;
     }
     // ---- per-bin projection: 8 bins per lane + bin 256 (evaluated by every lane, kept and counted by lane 0) ----
+    BinCtx cf = c;
+    if (OP == SOP_MASK) cf.mask = a.mask + (size_t)row * a.mask_rs + (size_t)t * F;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int k = lane + 64 * j;
-        Xk[j] = pk_v(bin_op<OP>(pk_f(Xk[j]), k, c, wsum, j));
-        Xm[j] = pk_v(bin_op<OP>(pk_f(Xm[j]), N2 - k, c, wsum, 4 + j));
+        Xk[j] = pk_v(bin_op<OP>(pk_f(Xk[j]), k, cf, wsum, j));
+        Xm[j] = pk_v(bin_op<OP>(pk_f(Xm[j]), N2 - k, cf, wsum, 4 + j));
     }
     {
         float w256 = 0.f;
-        X256 = pk_v(bin_op<OP>(pk_f(X256), N2 / 2, c, w256, 8));
+        X256 = pk_v(bin_op<OP>(pk_f(X256), N2 / 2, cf, w256, 8));
         if (l0) wsum += w256;
     }
     // ---- inverse pre-pass: Z'[k] = Ee + i Oo, Z'[512 - k] = conj(Ee - i Oo), Ee = X[k] + conj X[512-k], i Oo = 2 (X[k] - conj X[512-k]) conj(pm_k)
@@ -529,6 +557,30 @@ __global__ __launch_bounds__(256) void k_spec_stft(SpecArgs a) {
     wave_frame<SOP_NONE, false, true>(a, c, tw, xbuf + wave * XB, row, t, lane, raw);
 }
 
+// Masking threshold pass 1: the STFT of k_spec_stft with a level epilogue: P (rows, T, F) f32 dB and one maximum per workgroup
+// (order-free, so the row maximum needs no atomics).  grid: (ceil(T / 4), rows)
+__global__ __launch_bounds__(256) void k_spec_psd(SpecArgs a) {
+    __shared__ __attribute__((aligned(16))) float2 xbuf[4 * XB];
+    __shared__ float wmax[4];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t = blockIdx.x * 4 + wave, row = blockIdx.y;
+    float mx = -INFINITY;
+    if (t < a.T) {
+        LaneTw tw;
+        lane_tw(tw, a.tw, a.win, lane);
+        BinCtx c{};
+        float2 raw[8];
+        frame_load(a, a.x + (size_t)row * a.L, t, lane, raw);
+        mx = wave_frame<SOP_PSD, false, true>(a, c, tw, xbuf + wave * XB, row, t, lane, raw);
+    }
+    mx = wave_max(mx);
+    if (lane == 0) wmax[wave] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        a.pmax_part[(size_t)row * gridDim.x + blockIdx.x] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+}
+
 // per-bin op on a spectrum in memory (frame-major (rows, T, F) complex64), optional uniform scale
 template <int OP>
 __global__ __launch_bounds__(256) void k_spec_apply(SpecArgs a, int64_t n, const float* __restrict__ scale) {
@@ -644,12 +696,19 @@ paa_status spec_project(const SpecArgs& a, int op, int rows, int* n_part, hipStr
         case SOP_MINMAX: return launch_fused<SOP_MINMAX, false>(a, rows, st);
         case SOP_PHON: return launch_fused<SOP_PHON, false>(a, rows, st);
         case SOP_FM: return launch_fused<SOP_FM, false>(a, rows, st);
+        case SOP_MASK: return launch_fused<SOP_MASK, false>(a, rows, st);
         default: PAA_FAIL(PAA_ERR_BAD_NORM, "spec_project: op %d", op);
     }
 }
 
 paa_status spec_stft(const SpecArgs& a, int rows, hipStream_t st) {
     hipLaunchKernelGGL(k_spec_stft, dim3(cdiv(a.T, 4), rows), dim3(256), 0, st, a);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
+paa_status spec_psd(const SpecArgs& a, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(k_spec_psd, dim3(spec_psd_groups(a.T), rows), dim3(256), 0, st, a);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }

@@ -12,7 +12,7 @@ import sys
 import torch
 
 from .core import iso
-from .training_utils import build, evaluation, parser, save, scoring_helpers, train
+from .training_utils import build, evaluation, parser, pgd, save, scoring_helpers, train
 
 
 def main(args) -> int:
@@ -23,6 +23,7 @@ def main(args) -> int:
     # launched by torch.distributed.run with several ranks: one process per GPU, RCCL ("nccl") over xGMI, utterances
     # sharded over ranks; every rank keeps the same p, rank 0 writes the files
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    pgd.masking_route(args.norm_type, world)          # before any collective: every rank raises
     if world > 1:
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
         torch.cuda.set_device(local)

@@ -94,7 +94,8 @@ def params_of(args) -> _lib.PaaParams:
     return _lib.PaaParams(_lib.NORM_IDS[nt], g("l2_size", 0.05), g("linf_size", 1e-4), g("snr_db", 64), g("tv_epsilon", 1e-3),
                           g("fm_epsilon", 2), g("min_freq_attack", 120), g("max_freq_attack", 20000),
                           g("phon_reference_db", 65), g("lr", 1e-4),
-                          +1 if getattr(args, "attack_mode", "untargeted") == "untargeted" else -1)
+                          +1 if getattr(args, "attack_mode", "untargeted") == "untargeted" else -1,
+                          g("masking_margin_db", 0.0))
 
 
 def as_f32_cuda(t: torch.Tensor, name: str) -> torch.Tensor:

@@ -86,7 +86,8 @@ def attack_size_string(args) -> str:
     """build.py:235-247: the epsilon that names the run directory."""
     sizes = {"min_max_freqs": f"{args.min_freq_attack}", "fletcher_munson": f"{args.fm_epsilon}",
              "max_phon": f"{args.max_phon_level}", "l2": f"{args.l2_size}", "linf": f"{args.linf_size}",
-             "snr": f"{args.snr_db}", "tv": f"{args.tv_epsilon}"}
+             "snr": f"{args.snr_db}", "tv": f"{args.tv_epsilon}",
+             "masking": f"{getattr(args, 'masking_margin_db', 0.0)}"}
     first = str(args.norm_type).split("+")[0]
     if first not in sizes:
         raise ValueError(f"Unsupported norm_type: {args.norm_type}")

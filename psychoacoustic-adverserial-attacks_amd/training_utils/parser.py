@@ -2,7 +2,7 @@
 defaults — SURVEY §5.6) plus the non-breaking additions of SURVEY §8b."""
 import argparse
 
-NORM_CHOICES = ["l2", "linf", "snr", "tv", "fletcher_munson", "min_max_freqs", "max_phon"]
+NORM_CHOICES = ["l2", "linf", "snr", "tv", "fletcher_munson", "min_max_freqs", "max_phon", "masking"]
 
 
 def _norm_type(v: str) -> str:
@@ -41,6 +41,8 @@ def create_arg_parser():
     parser.add_argument('--max_freq_attack', type=float, default=20_000)
     parser.add_argument('--tv_epsilon', type=float, default=0.001)
     parser.add_argument('--max_phon_level', type=float, default=20)
+    parser.add_argument('--masking_margin_db', type=float, default=0.0,
+                        help='masking norm (extension): dB added to the clean clip\'s masking threshold')
     # sound properties (parser.py:57-63)
     parser.add_argument('--phon_reference_db', type=float, default=65)
     parser.add_argument('--sr', type=int, default=16000)

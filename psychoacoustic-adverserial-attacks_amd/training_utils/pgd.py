@@ -57,6 +57,16 @@ def adam_unsupported(optimizer):
     return None
 
 
+def masking_route(norm_type, world: int) -> None:
+    """The masking norm bounds the universal perturbation by the minimum of every clip's bound: with several ranks that is a
+    MIN over the ranks' shards, which the step's one SUM all-reduce does not carry.  Raises NotImplementedError (on every
+    rank, before any collective) for a data-parallel masking run; one rank, force_collective included, is fine."""
+    if world > 1 and "masking" in str(norm_type).split("+"):
+        raise NotImplementedError("the masking norm is not implemented for data-parallel universal perturbations (world "
+                                  f"size {world}): the bound would need a MIN-reduction across ranks; use one rank, or "
+                                  "per-clip perturbations (paa_amd.attack_clips)")
+
+
 def adam_scalars(lr, beta1, beta2, step):
     """[-lr / (1 - beta1^t), sqrt(1 - beta2^t)] in double, as torch/optim/adam.py _multi_tensor_adam (capturable=False)
     computes step_size and bias_correction2_sqrt; the foreach kernels round them to f32."""
@@ -88,6 +98,8 @@ class PgdStepper:
         self.world = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.world = torch.distributed.get_world_size(group)
+        masking_route(args.norm_type, self.world)
+        self.interp = interp
         self.collective = self.world > 1 or bool(force_collective)
         if self.collective and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
             raise RuntimeError("force_collective needs an initialised torch.distributed process group")
@@ -205,8 +217,15 @@ class PgdStepper:
         if p.numel() != self.L or clean.shape[-1] != self.L:
             raise ValueError(f"Loaded perturbation length {p.numel()} / clip length {clean.shape[-1]} != expected {self.L}")
         self._check_p(p)
+        self._fit_proj(clean.shape[0])
         self._pre_step()
         return self._body(p, clean, labels, want_logits, logits_out)
+
+    def _fit_proj(self, B):
+        """The masking norm keeps one bound per clip of the batch: grow the projection workspace to the batch (allocates, so
+        it happens in an eager step; capture() runs one first)."""
+        if "masking" in self.norms and self.proj.max_batch < B:
+            self.proj = runtime.get_proj(self.args, self.dev, B, self.L, self.interp)
 
     def _check_p(self, p):
         if self.optimizer is not None and p.data_ptr() != self.adam_p.data_ptr():

@@ -54,13 +54,17 @@ def perturbation_constraint(p: torch.Tensor, clean_audio, args, interp, spl_thre
             raise ValueError("SNR projection requires clean_audio ro compare to")           # train.py:91
         if n == "tv" and clean_audio is None:
             raise ValueError("TV projection can benefit from clean_audio for bounds")       # train.py:95
+        if n == "masking" and clean_audio is None:
+            raise ValueError("masking projection requires clean_audio")
     src = runtime.as_f32_cuda(p.detach(), "p")
     q = torch.empty_like(src)
     rows, L = (q.shape[0], q.shape[1]) if q.dim() == 2 else (1, q.shape[0])
     clean = None if clean_audio is None else runtime.as_f32_cuda(clean_audio, "clean_audio")
     if clean is not None and clean.shape[-1] != L:
         raise ValueError(f"clean_audio length {clean.shape[-1]} != perturbation length {L}")
-    pr = runtime.get_proj(args, q.device, rows, L, interp)
+    # the masking norm keeps one bound per clean clip before their minimum: the workspace holds the whole batch
+    nb_ws = clean.shape[0] if clean is not None and clean.dim() == 2 and "masking" in norms else 0
+    pr = runtime.get_proj(args, q.device, max(rows, nb_ws), L, interp)
     out_len = L
     with torch.cuda.device(q.device):
         for i, n in enumerate(norms):
