@@ -46,7 +46,7 @@ typedef struct {
 } paa_params;
 
 const char* paa_last_error(void);
-/* 310 = this header; 311 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
+/* 320 = this header; 321 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
  * tools/ only).  Bindings refuse other values. */
 int paa_version(void);
 /* sizeof(paa_params), sizeof(paa_arch), sizeof(paa_tensor), sizeof(paa_gemm_desc): layout check for bindings */
@@ -119,6 +119,26 @@ paa_status paa_project_ext(paa_proj* h, const paa_params* prm, float* d_p, int r
  * d_pmax (B) Pmax_b (nullable). */
 paa_status paa_masking_threshold(paa_proj* h, const float* d_clean, int B, int L, float* d_psd, float* d_theta, float* d_pmax,
                                  void* stream);
+
+/* ---- masking-threshold loss term (Qin et al. 2019 stage 2, extension) ----------------------------------
+ * With theta_b, Pmax_b and A_b of clean clip b as above (margin = prm->masking_margin_db, the only field read), S = STFT(delta),
+ * c_b = 10^((96 - Pmax_b) / 10), T = 1 + L / 256, F = 513:
+ *   l_b(delta) = 1 / (T F) sum_{t,k} max(c_b |S(t,k)|^2 - 10^((theta_b(t,k) + margin) / 10), 0) = c_b / (T F) sum max(|S|^2 - A_b^2, 0)
+ * (strict hinge: a bin is active iff |S|^2 > A_b^2).  d_p (p_rows, L): p_rows = 1 holds the one row against all B clips,
+ * p_rows = B holds row b against clip b; any other p_rows is PAA_ERR_ARG.  With W(t,k) = 1 / (T F) sum_b c_b [active_b(t,k)] and
+ * H = W S, DC and Nyquist doubled, the gradient of sum_b l_b is the adjoint of the STFT applied to H: the windowed frames
+ * w 1024 irfft(H(t,:)) overlap-added with no envelope division, the reflect padding folded back onto the samples it mirrors.
+ *   d_alpha     device [1], read on the stream (a captured graph follows it); NULL = 1.0
+ *   d_grad      (p_rows, L): d_grad -= alpha * grad(sum_b l_b) (the step's convention: grad = d(direction * CTC), the term is
+ *               subtracted from the objective); NULL = losses only
+ *   d_loss_rows (B) l_b, not weighted by alpha; nullable
+ *   d_loss_sum  [1] = (float) sum_b (double) d_loss_rows[b] in clip order, WRITTEN, not accumulated; nullable
+ *   d_weight    (p_rows, T, F) W, a diagnostic for tests; nullable
+ * No atomics: two calls give the same bits.  d_clean is required (PAA_ERR_NEED_CLEAN); default frame geometry only
+ * (PAA_ERR_ARG); B <= max_batch of the context (PAA_ERR_SIZE).  The threshold is recomputed from d_clean in every call. */
+paa_status paa_masking_loss(paa_proj* h, const paa_params* prm, const float* d_p, int p_rows, const float* d_clean, int B, int L,
+                            const float* d_alpha, float* d_grad, float* d_loss_rows, float* d_loss_sum, float* d_weight,
+                            void* stream);
 
 /* core/fourier_transforms.py:4-29 compute_stft: (B, L) -> d_out (B, T, F) complex64 interleaved,
  * T = 1 + L / hop; the (B, F, T) tensor the reference returns is the transpose-view of this. */
@@ -204,7 +224,8 @@ int paa_model_frames(const paa_model* m);     /* T_e for the configured length *
  *   d_stats  (8) out: [0] loss (sum over the batch, HF ctc_loss_reduction='sum').  Slots [1..7] are NOT written by
  *            this call: they belong to the caller's data-parallel bookkeeping (paa_amd/training_utils/pgd.py packs
  *            [1] sum clean^2 and [2] TV(clean) from paa_batch_stats, [3] WER word errors, [4] WER reference words,
- *            [5] the local clip count B (paa_batch_stats), behind the gradient, so that ONE all-reduce carries everything
+ *            [5] the local clip count B (paa_batch_stats), [6] sum_b l_b of paa_masking_loss (masking_loss_alpha > 0, else 0),
+ *            behind the gradient, so that ONE all-reduce carries everything
  *            and the global clean.numel() = L * sum_r B_r needs no collective of its own).
  */
 paa_status paa_model_fwd_bwd(paa_model* m, const float* d_clean, const float* d_p, const int32_t* d_labels,

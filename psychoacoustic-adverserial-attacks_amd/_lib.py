@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PAA_EXTRA_HIPCC_FLAGS (tools/ only: diagnostic builds, see build_ext.py) selects the diagnostic library built next to the shipped one
 LIB_PATH = os.path.join(HERE, "libpaa_hip_exp.so" if os.environ.get("PAA_EXTRA_HIPCC_FLAGS", "").strip() else "libpaa_hip.so")
 
-ABI_VERSIONS = (310, 311)      # include/paa_hip.h paa_version: 311 = the same ABI built with -DPAA_EXPERIMENTS
+ABI_VERSIONS = (320, 321)      # include/paa_hip.h paa_version: 321 = the same ABI built with -DPAA_EXPERIMENTS
 
 PAA_OK, PAA_ERR_BAD_NORM, PAA_ERR_NEED_CLEAN, PAA_ERR_SIZE, PAA_ERR_HIP, PAA_ERR_ARG, PAA_ERR_MISSING = range(7)
 
@@ -74,6 +74,8 @@ _SIGS = {
     "paa_batch_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "paa_masking_threshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "paa_masking_loss": (C.c_int, [C.c_void_p, C.POINTER(PaaParams), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "paa_stft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "paa_istft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "paa_sign_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),

@@ -20,12 +20,14 @@ import sys
 import torch
 
 from .core import iso, loss_helpers
+from .core.masking import masking_loss
 from .training_utils import build, parser, save
 from .training_utils.clip_attack import ClipStepper, clip_nll, compose_rows, init_rows, project_rows
 
 SPLITS = ("test", "val", "train")
 RECORD_FIELDS = ("index", "clean_wer", "adv_wer", "clean_ctc", "final_ctc", "l2", "linf", "snr_db")
 TARGET_FIELD = "target_wer"
+MASK_FIELD = "final_masking_loss"          # l_b(delta_b) of the finished perturbation (masking_loss_alpha > 0 only)
 SUMMARY_FIELDS = ("clean_wer", "adv_wer", "final_ctc", "l2", "linf", "snr_db")
 
 
@@ -118,6 +120,8 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
     linf = delta.abs().amax(dim=1).cpu()
     sig = x.double().pow(2).sum(dim=1).cpu()
     noise = delta.double().pow(2).sum(dim=1).cpu()
+    mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
+    mloss = masking_loss(delta, x, args)[0].cpu() if mask_alpha > 0 else None
     records = []
     for b in range(B):
         rec = {"index": int(idx[b]), "clean_wer": _wer(clean_pred[b], refs[b].lower()), "adv_wer": _wer(adv_pred[b], refs[b].lower()),
@@ -125,6 +129,8 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
                "snr_db": float(10.0 * math.log10(float(sig[b]) / float(noise[b]))) if float(noise[b]) > 0 else float("inf")}
         if args.attack_mode == "targeted":
             rec[TARGET_FIELD] = _wer(adv_pred[b], target.lower())
+        if mloss is not None:
+            rec[MASK_FIELD] = float(mloss[b])
         records.append(rec)
     return records, delta, compose_rows(x, delta), stepper
 
@@ -148,7 +154,8 @@ def main(args) -> int:
     args.attack_size_string = build.attack_size_string(args)
     root = getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"clips_{args.norm_type}_{args.attack_size_string}_{args.attack_mode}_{args.optimizer_type}")
+                                 f"clips_{args.norm_type}_{args.attack_size_string}{build.masking_loss_suffix(args)}_"
+                                 f"{args.attack_mode}_{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)
     interp = iso.build_weight_interpolator()
     spl_thresh = build.init_phon_threshold_tensor(args)

@@ -28,3 +28,29 @@ def masking_threshold(clean: torch.Tensor, args, psd: bool = False):
         _lib.check(_lib.lib().paa_masking_threshold(pr.h, _lib.ptr(x), B, L, _lib.ptr(pb), _lib.ptr(theta), _lib.ptr(pmax),
                                                     _lib.stream_ptr()))
     return (theta, pmax, pb) if psd else (theta, pmax)
+
+
+def masking_loss(delta: torch.Tensor, clean: torch.Tensor, args, grad: bool = False):
+    """The masking-threshold loss term of ``delta`` against the clean clips ``clean`` (B, L):
+    l_b = 1 / (T F) sum_{t,k} max(c_b |STFT(delta)|^2 - 10^((theta_b + masking_margin_db) / 10), 0).  ``delta`` is (1, L) or
+    (L,) (the one row against every clip) or (B, L) (row b against clip b).  Returns (loss_rows (B,), grad or None): with
+    ``grad=True`` the gradient of sum_b l_b itself, shaped like ``delta`` (alpha = 1, positive, not subtracted)."""
+    x = runtime.as_f32_cuda(clean, "clean_audio")
+    d = runtime.as_f32_cuda(delta, "delta")
+    if x.dim() == 1:
+        x = x[None]
+    d2 = d[None] if d.dim() == 1 else d
+    if x.dim() != 2 or d2.dim() != 2 or d2.shape[1] != x.shape[1] or d2.shape[0] not in (1, x.shape[0]):
+        raise ValueError(f"delta {tuple(d.shape)} must be (1, L) or (B, L) for clean_audio {tuple(x.shape)}")
+    B, L = x.shape
+    pr = runtime.get_proj(args, x.device, B, L)
+    rows = torch.empty(B, dtype=torch.float32, device=x.device)
+    g = torch.zeros_like(d2) if grad else None
+    a = type("A", (), dict(vars(args)))()
+    a.norm_type = "masking"
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().paa_masking_loss(pr.h, runtime.params_of(a), _lib.ptr(d2), d2.shape[0], _lib.ptr(x), B, L, None,
+                                               _lib.ptr(g), _lib.ptr(rows), None, None, _lib.stream_ptr()))
+    if g is not None:
+        g = g.neg_().view_as(d)
+    return rows, g

@@ -491,12 +491,12 @@ struct paa_proj {
 };
 
 extern "C" const char* paa_last_error(void) { return paa::g_err.c_str(); }
-// 310 + 1 if the library was built with -DPAA_EXPERIMENTS (diagnostic configurations and environment switches present)
+// 320 + 1 if the library was built with -DPAA_EXPERIMENTS (diagnostic configurations and environment switches present)
 extern "C" int paa_version(void) {
 #ifdef PAA_EXPERIMENTS
-    return 311;
+    return 321;
 #else
-    return 310;
+    return 320;
 #endif
 }
 
@@ -959,6 +959,33 @@ extern "C" paa_status paa_spectrum_project(paa_proj* h, const paa_params* prm, c
 }
 
 // The masking threshold of the clean clips d_clean (B, L): theta (B, T, F) dB, optionally P - Pmax + 96 (B, T, F) and Pmax (B).
+// Masking-threshold loss: passes 1 and 2 leave every clip's bound A_b in h->d_mask and Pmax_b in the idle frame
+// workspace, then ONE fused launch (k_spec_mloss) and the loss partials' finishing launch.  Frame workspace: [B x parts doubles:
+// loss partials | B doubles: finishing scratch | B floats: Pmax].
+extern "C" paa_status paa_masking_loss(paa_proj* h, const paa_params* prm, const float* d_p, int p_rows, const float* d_clean, int B,
+                                       int L, const float* d_alpha, float* d_grad, float* d_loss_rows, float* d_loss_sum,
+                                       float* d_weight, void* stream) {
+    if (!h || !prm || !d_p) PAA_FAIL(PAA_ERR_ARG, "paa_masking_loss: null argument");
+    if (!d_clean || B < 1) PAA_FAIL(PAA_ERR_NEED_CLEAN, "the masking loss requires clean_audio");
+    if (p_rows != 1 && p_rows != B) PAA_FAIL(PAA_ERR_ARG, "paa_masking_loss: p_rows=%d must be 1 or B=%d", p_rows, B);
+    hipStream_t st = (hipStream_t)stream;
+    const int T = 1 + L / h->hop;
+    const int parts = spec_mloss_parts(T);
+    double* lpart = reinterpret_cast<double*>(h->d_frames);
+    double* scratch = lpart + (size_t)B * parts;
+    float* pmax = reinterpret_cast<float*>(scratch + B);
+    if (B <= h->max_batch && ((size_t)B * (parts + 1)) * 2 + B > h->frames_floats)
+        PAA_FAIL(PAA_ERR_SIZE, "paa_masking_loss: workspace too small");
+    PAA_TRY(masking_pass(h, d_clean, B, L, prm->masking_margin_db, nullptr, nullptr, pmax, false, st));
+    SpecArgs a = spec_args(h, L, T, L);
+    a.x = d_p; a.mask = h->d_mask; a.mask_rs = (int64_t)T * h->F;
+    a.pmax = pmax; a.alpha = d_alpha; a.grad = d_grad; a.wout = d_weight; a.lpart = lpart;
+    a.nclip = p_rows == 1 ? B : 1; a.per_clip = p_rows == 1 ? 0 : 1; a.lstride = parts;
+    PAA_TRY(spec_mloss(a, p_rows, st));
+    if (d_loss_rows || d_loss_sum) PAA_TRY(spec_mloss_finish(lpart, parts, B, scratch, d_loss_rows, d_loss_sum, st));
+    return PAA_OK;
+}
+
 extern "C" paa_status paa_masking_threshold(paa_proj* h, const float* d_clean, int B, int L, float* d_psd, float* d_theta,
                                             float* d_pmax, void* stream) {
     if (!h || !d_theta) PAA_FAIL(PAA_ERR_ARG, "paa_masking_threshold: null argument");

@@ -6,8 +6,9 @@
 namespace paa {
 
 // SOP_MASK: clip each bin to a per-(row, frame, bin) magnitude bound (masking norm); SOP_PSD: the forward half only, writing
-// 10 log10(|X|^2 + 1e-20) per bin (the masking threshold's first pass)
-enum SpecOp { SOP_NONE = 0, SOP_MINMAX = 1, SOP_PHON = 2, SOP_FM = 3, SOP_MASK = 4, SOP_PSD = 5 };
+// 10 log10(|X|^2 + 1e-20) per bin (the masking threshold's first pass); SOP_MLOSS: the masking-threshold loss term (k_spec_mloss:
+// hinge weight per bin against the clips' bounds, then the ADJOINT of the STFT instead of its inverse)
+enum SpecOp { SOP_NONE = 0, SOP_MINMAX = 1, SOP_PHON = 2, SOP_FM = 3, SOP_MASK = 4, SOP_PSD = 5, SOP_MLOSS = 6 };
 
 struct SpecArgs {
     const float* x;        // (rows, L) waveform in                       [waveform source]
@@ -26,6 +27,14 @@ struct SpecArgs {
     int64_t mask_rs;
     float* psd;            // PSD: (rows, T, F) f32 level in dB
     float* pmax_part;      // PSD: the maximum level of each (row, workgroup), (rows, gridDim.x)
+    // MLOSS (spec_mloss): x = the perturbation rows, mask / mask_rs = every clip's bound A_b; a row is held against `nclip` clips
+    // starting at clip (per_clip ? row : 0)
+    const float* pmax;     // (clips) Pmax_b of the clean clips
+    const float* alpha;    // device [1], nullable (1.0)
+    float* grad;           // (rows, L): grad -= alpha * dloss; nullable (losses only)
+    float* wout;           // (rows, T, F) hinge weight W; nullable
+    double* lpart;         // loss partials, (clips, lstride): one double per (clip, workgroup, wave)
+    int nclip, per_clip, lstride;
 };
 
 // rows x (L) waveform -> per-bin op -> waveform (train.py:38-66 _project_frequency_domain with _align_to), in place allowed
@@ -38,6 +47,15 @@ paa_status spec_apply(const SpecArgs& a, int op, int rows, const float* scale, i
 // masking threshold pass 1 (k_spec_psd): a.x (rows, L) -> a.psd (rows, T, F) and a.pmax_part (rows, spec_psd_groups(T))
 paa_status spec_psd(const SpecArgs& a, int rows, hipStream_t st);
 inline int spec_psd_groups(int T) { return cdiv(T, 4); }
+// masking-threshold loss of `rows` perturbation rows (SpecArgs: MLOSS fields): grad -= alpha * d(sum_b l_b), W and the loss
+// partials a.lpart[clip * a.lstride + i], i < spec_mloss_parts(T) (a.lstride must be that number); then spec_mloss_finish sums
+// them in a fixed order: loss_rows[b] (nullable), loss_sum[0] = sum_b (double)loss_rows[b] (nullable); scratch: `clips` doubles
+constexpr int MLOSS_NW = 8;                                       // waves = frames per workgroup of k_spec_mloss
+inline int spec_mloss_groups(int T) { return T <= MLOSS_NW ? 1 : cdiv(T, MLOSS_NW - 3); }
+inline int spec_mloss_parts(int T) { return spec_mloss_groups(T) * MLOSS_NW; }
+paa_status spec_mloss(const SpecArgs& a, int rows, hipStream_t st);
+paa_status spec_mloss_finish(const double* lpart, int lstride, int clips, double* scratch, float* loss_rows, float* loss_sum,
+                             hipStream_t st);
 int spec_groups(int T, int rows, int op, bool src_spec);        // workgroups per row spec_project / spec_istft launch (size of the FM partial array / rows)
 
 }  // namespace paa

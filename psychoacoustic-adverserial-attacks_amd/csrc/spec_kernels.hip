@@ -103,6 +103,8 @@ struct BinCtx {
     unsigned inb = 0;       // run kernel, FM: bit `slot` set = the lane's bin of that slot lies inside the interpolator (fm[k] >= 0), read once per run
     bool have_inb = false;
     const float* mask = nullptr;   // MASK: the bound of the frame being projected, [F]
+    int lslot = 0;                 // MLOSS: index of this (workgroup, wave) in a clip's loss partials
+    bool own = false;              // MLOSS: the workgroup owns the frame (its loss and W are counted / written here)
 };
 constexpr int FM_LS = 576;  // 9 x 64: the two table rows of a lerp are then ONE ds_read2st64_b32
 
@@ -150,6 +152,66 @@ __device__ __forceinline__ float2 bin_op(float2 v, int k, const BinCtx& c, float
         return make_float2(v.x * sc, v.y * sc);
     }
     return v;
+}
+
+// Masking-threshold loss on one frame's bins.  In: the lane's nine bins of S = STFT(delta).  For every clip b that
+// bounds this row: active = |S|^2 > A_b^2 (strict), W += c_b / (T F) on active bins, and the clip's loss share
+// c_b / (T F) sum_active (|S|^2 - A_b^2) goes, summed over the wave in f32, into the clip's partial of this (workgroup, wave) as a
+// double (0 for a frame the workgroup does not own: every slot is written on every call).  Out: H = W S with DC and Nyquist doubled
+// (the adjoint of the real transform counts them once, every other bin twice).  The bound reads of a clip are nine independent
+// loads; the clip loop is unrolled so that two clips' reads are in flight together.
+__device__ __forceinline__ void mloss_bins(const SpecArgs& a, const BinCtx& c, int row, int t, int lane, v2f (&Xk)[4], v2f (&Xm)[4],
+                                           v2f& X256) {
+    const bool l0 = lane == 0;
+    int kb[9];
+    float pw[9], W[9];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        kb[j] = lane + 64 * j;
+        kb[4 + j] = N2 - kb[j];
+        pw[j] = Xk[j].x * Xk[j].x + Xk[j].y * Xk[j].y;
+        pw[4 + j] = Xm[j].x * Xm[j].x + Xm[j].y * Xm[j].y;
+    }
+    kb[8] = N2 / 2;
+    pw[8] = X256.x * X256.x + X256.y * X256.y;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) W[i] = 0.f;
+    const int cb = a.per_clip ? row : 0;
+    const float itf = 1.f / ((float)a.T * (float)F);
+    const float* A0 = a.mask + (size_t)cb * a.mask_rs + (size_t)t * F;
+#pragma unroll 2
+    for (int ci = 0; ci < a.nclip; ++ci) {
+        const float* Ab = A0 + (size_t)ci * a.mask_rs;
+        float A[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) A[i] = Ab[kb[i]];
+        const float cc = __builtin_amdgcn_exp2f((96.f - a.pmax[cb + ci]) * 0.332192809488736235f) * itf;   // 10^((96 - Pmax) / 10) / (T F)
+        float ls = 0.f;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const float A2 = A[i] * A[i];
+            const bool act = (pw[i] > A2) && (i < 8 || l0);           // bin 256 is lane 0's alone
+            W[i] += act ? cc : 0.f;
+            ls += act ? pw[i] - A2 : 0.f;
+        }
+        ls = wave_sum(ls * cc);
+        if (l0) a.lpart[(size_t)(cb + ci) * a.lstride + c.lslot] = c.own ? (double)ls : 0.0;
+    }
+    if (a.wout && c.own) {
+        float* Wo = a.wout + ((size_t)row * a.T + t) * F;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) Wo[kb[i]] = W[i];
+        if (l0) Wo[kb[8]] = W[8];
+    }
+    const float w0 = l0 ? 2.f * W[0] : W[0], w4 = l0 ? 2.f * W[4] : W[4];         // lane 0, pair 0: DC and Nyquist
+    Xk[0] = v2f{Xk[0].x * w0, Xk[0].y * w0};
+    Xm[0] = v2f{Xm[0].x * w4, Xm[0].y * w4};
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+        Xk[j] = v2f{Xk[j].x * W[j], Xk[j].y * W[j]};
+        Xm[j] = v2f{Xm[j].x * W[4 + j], Xm[j].y * W[4 + j]};
+    }
+    X256 = v2f{X256.x * W[8], X256.y * W[8]};
 }
 
 // Raw samples of frame t of one row: raw[n2] = (x[2m], x[2m + 1]), m = lane + 64 n2 (center=True: reflect pad 512).
@@ -253,18 +315,22 @@ __device__ __forceinline__ float wave_frame(const SpecArgs& a, const BinCtx& c, 
         return 0.f;
     }
     // ---- per-bin projection: 8 bins per lane + bin 256 (evaluated by every lane, kept and counted by lane 0) ----
-    BinCtx cf = c;
-    if (OP == SOP_MASK) cf.mask = a.mask + (size_t)row * a.mask_rs + (size_t)t * F;
+    if (OP == SOP_MLOSS) {
+        mloss_bins(a, c, row, t, lane, Xk, Xm, X256);
+    } else {
+        BinCtx cf = c;
+        if (OP == SOP_MASK) cf.mask = a.mask + (size_t)row * a.mask_rs + (size_t)t * F;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int k = lane + 64 * j;
-        Xk[j] = pk_v(bin_op<OP>(pk_f(Xk[j]), k, cf, wsum, j));
-        Xm[j] = pk_v(bin_op<OP>(pk_f(Xm[j]), N2 - k, cf, wsum, 4 + j));
-    }
-    {
-        float w256 = 0.f;
-        X256 = pk_v(bin_op<OP>(pk_f(X256), N2 / 2, cf, w256, 8));
-        if (l0) wsum += w256;
+        for (int j = 0; j < 4; ++j) {
+            const int k = lane + 64 * j;
+            Xk[j] = pk_v(bin_op<OP>(pk_f(Xk[j]), k, cf, wsum, j));
+            Xm[j] = pk_v(bin_op<OP>(pk_f(Xm[j]), N2 - k, cf, wsum, 4 + j));
+        }
+        {
+            float w256 = 0.f;
+            X256 = pk_v(bin_op<OP>(pk_f(X256), N2 / 2, cf, w256, 8));
+            if (l0) wsum += w256;
+        }
     }
     // ---- inverse pre-pass: Z'[k] = Ee + i Oo, Z'[512 - k] = conj(Ee - i Oo), Ee = X[k] + conj X[512-k], i Oo = 2 (X[k] - conj X[512-k]) conj(pm_k)
     {
@@ -287,6 +353,11 @@ __device__ __forceinline__ float wave_frame(const SpecArgs& a, const BinCtx& c, 
     }
     wave_fft512<+1>(x, xb, tw, lane);
     // x[k2] = 1024 z[lane + 64 k2]: samples 2m, 2m + 1 of the frame; window again (istft), keep in LDS
+    if (OP == SOP_MLOSS) {                                    // the adjoint keeps the 1024: w 1024 irfft(H)
+#pragma unroll
+        for (int k2 = 0; k2 < 8; ++k2) xb[lane + 64 * k2] = pk_mul(x[k2], tw.w[k2]);
+        return 0.f;
+    }
     const v2f inv = {1.f / (float)N, 1.f / (float)N};
 #pragma unroll
     for (int k2 = 0; k2 < 8; ++k2) xb[lane + 64 * k2] = pk_mul(pk_mul(x[k2], inv), tw.w[k2]);
@@ -581,6 +652,97 @@ __global__ __launch_bounds__(256) void k_spec_psd(SpecArgs a) {
         a.pmax_part[(size_t)row * gridDim.x + blockIdx.x] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
 }
 
+// Masking-threshold loss: STFT of delta -> hinge weight per bin (mloss_bins) -> ADJOINT of the STFT, subtracted from
+// the gradient.  The slab shape of k_spec_fused: MLOSS_NW waves, one frame each, the windowed frames w 1024 irfft(H) left in LDS.
+// The adjoint tail differs from the iSTFT tail three ways: no division by the window envelope, no trimming — the reflect padding's
+// gradient is FOLDED onto the samples it mirrors (padded index 512 - i onto sample i, L + 511 + i onto L - 1 - i, i = 1 .. 512) —
+// and the result is subtracted, times alpha, from grad (each sample is owned by one thread of one workgroup).
+// Output sample m lies in padded hop-block 2 + m / 256, blocks 2 .. T + 1; block j is the sum of frames j-3 .. j.  Workgroup g
+// holds frames c0 - 3 .. c0 + 4 and owns blocks [lo, hi):  T <= 8: ONE workgroup, c0 = 3 (slot f = frame f), all blocks;  else
+// c0 = 2 + 5 g and 5 blocks, but the LAST workgroup is shifted to c0 = T - 3 and owns T - 3 .. T + 1 (the one before it stops
+// there): every sample the end fold touches (blocks T - 2 .. T + 1) and every frame its mirror positions need (up to block T + 2,
+// i.e. frame T - 1) are then in ONE workgroup, as blocks 0 .. 4 and frames 0 .. 1 of the start fold are in workgroup 0 (T >= 9
+// gives it blocks 2 .. 5 at least).  Frame t's loss and W belong to the owner of block t + 2.  grid: (spec_mloss_groups(T), rows).
+__global__ __launch_bounds__(MLOSS_NW * 64) void k_spec_mloss(SpecArgs a) {
+    constexpr int NW = MLOSS_NW, NOUT = NW - 3;
+    __shared__ __attribute__((aligned(16))) float2 xbuf[NW * XB];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = blockIdx.x, row = blockIdx.y, G = gridDim.x;
+    int c0, lo, hi;
+    if (G == 1) { c0 = a.T <= NW ? 3 : 2; lo = 2; hi = a.T + 2; }
+    else if (g == G - 1) { c0 = a.T - 3; lo = c0; hi = a.T + 2; }
+    else { c0 = 2 + g * NOUT; lo = c0; hi = c0 + NOUT < a.T - 3 ? c0 + NOUT : a.T - 3; }
+    float2* xb = xbuf + wave * XB;
+    BinCtx c{};
+    c.lslot = g * NW + wave;
+    const int t = c0 - 3 + wave;                              // this wave's frame
+    c.own = t >= 0 && t < a.T && t + 2 >= lo && t + 2 < hi;
+    if (t >= 0 && t < a.T) {
+        LaneTw tw;
+        lane_tw(tw, a.tw, a.win, lane);
+        float2 raw[8];
+        frame_load(a, a.x + (size_t)row * a.L, t, lane, raw);
+        wave_frame<SOP_MLOSS, false, false>(a, c, tw, xb, row, t, lane, raw);
+    } else {
+#pragma unroll
+        for (int k2 = 0; k2 < 8; ++k2) xb[lane + 64 * k2] = make_float2(0.f, 0.f);
+        if (lane == 0) {
+            const int cb = a.per_clip ? row : 0;
+            for (int ci = 0; ci < a.nclip; ++ci) a.lpart[(size_t)(cb + ci) * a.lstride + c.lslot] = 0.0;
+        }
+    }
+    if (!a.grad) return;                                      // uniform: losses (and W) only
+    __syncthreads();                                          // every frame of the workgroup is in LDS
+    const float* fb = reinterpret_cast<const float*>(xbuf);
+    const int f0 = c0 - 3;                                    // frame of slot 0
+    // padded-signal sample n: the sum of the (up to four) frames that cover it
+    auto gp = [&](int n) -> float {
+        const int b = n >> 8, r = n & 255;
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int tq = b - 3 + q, sl = tq - f0;
+            if (tq >= 0 && tq < a.T && sl >= 0 && sl < NW) s += fb[sl * (2 * XB) + HOP * (3 - q) + r];
+        }
+        return s;
+    };
+    const float alpha = a.alpha ? a.alpha[0] : 1.f;
+    float* gr = a.grad + (size_t)row * a.L;
+    for (int i = tid; i < (hi - lo) * HOP; i += NW * 64) {
+        const int m = HOP * (lo - 2) + i;                     // sample of the row
+        if (m >= a.L) break;
+        float s = gp(N2 + m);
+        if (m >= 1 && m <= N2) s += gp(N2 - m);
+        const int e = a.L - 1 - m;
+        if (e >= 1 && e <= N2) s += gp(N2 + a.L - 1 + e);
+        if (s != 0.f) gr[m] -= alpha * s;                     // an all-inactive neighbourhood leaves the gradient's bits alone
+    }
+}
+
+// Fixed-order sum of the loss partials: wave w takes clips w, w + 16, ...: lane l adds partials l, l + 64, ... in order, then the
+// wave's butterfly; thread 0 adds the clips' (f32-rounded) losses in clip order.  One workgroup of 16 waves.
+__global__ __launch_bounds__(1024) void k_mloss_finish(const double* __restrict__ lpart, int lstride, int clips, double* scratch,
+                                                       float* loss_rows, float* loss_sum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = wave; b < clips; b += 16) {
+        double s = 0.0;
+        for (int i = lane; i < lstride; i += 64) s += lpart[(size_t)b * lstride + i];
+        s = wave_sum(s);
+        if (lane == 0) {
+            const float f = (float)s;
+            scratch[b] = (double)f;
+            if (loss_rows) loss_rows[b] = f;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && loss_sum) {
+        double s = 0.0;
+        for (int b = 0; b < clips; ++b) s += scratch[b];
+        loss_sum[0] = (float)s;
+    }
+}
+
 // per-bin op on a spectrum in memory (frame-major (rows, T, F) complex64), optional uniform scale
 template <int OP>
 __global__ __launch_bounds__(256) void k_spec_apply(SpecArgs a, int64_t n, const float* __restrict__ scale) {
@@ -709,6 +871,20 @@ paa_status spec_stft(const SpecArgs& a, int rows, hipStream_t st) {
 
 paa_status spec_psd(const SpecArgs& a, int rows, hipStream_t st) {
     hipLaunchKernelGGL(k_spec_psd, dim3(spec_psd_groups(a.T), rows), dim3(256), 0, st, a);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
+paa_status spec_mloss(const SpecArgs& a, int rows, hipStream_t st) {
+    if (a.T < 3) PAA_FAIL(PAA_ERR_SIZE, "spec_mloss: T=%d", a.T);
+    hipLaunchKernelGGL(k_spec_mloss, dim3(spec_mloss_groups(a.T), rows), dim3(MLOSS_NW * 64), 0, st, a);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
+paa_status spec_mloss_finish(const double* lpart, int lstride, int clips, double* scratch, float* loss_rows, float* loss_sum,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(k_mloss_finish, dim3(1), dim3(1024), 0, st, lpart, lstride, clips, scratch, loss_rows, loss_sum);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }

@@ -55,6 +55,8 @@ def main(args) -> int:
     writer = rank == 0
     optimizer, scheduler = (build.create_optimizer(args, p) if args.optimizer_type == "adam" else (None, None))
     hist = {k: [] for k in ("train_ctc", "train_wer", "clean_ctc", "clean_wer", "pert_ctc", "pert_wer")}
+    mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
+    extra = {}          # results.json keys of the masking-threshold loss term: present only when masking_loss_alpha > 0
     goal = scoring_helpers.Objective(args.attack_mode)      # targeted: perturbed WER down; untargeted: perturbed CTC up
     best_epoch, no_improve, best_eval = -1, 0, goal.worst
     pert_path = os.path.join(args.save_dir, "perturbation.pt")
@@ -71,12 +73,16 @@ def main(args) -> int:
             hist["pert_ctc"].append(pert.ctc); hist["pert_wer"].append(pert.wer)
             logger.info("[%d/%d] train ctc %.4f wer %.4f | eval clean ctc %.4f wer %.4f | eval perturbed ctc %.4f wer %.4f",
                         epoch + 1, args.num_epochs, res.avg_ctc, res.avg_wer, clean.ctc, clean.wer, pert.ctc, pert.wer)
+            if mask_alpha > 0:
+                extra = {"masking_loss_alpha": mask_alpha, "train_masking_loss": res.avg_masking_loss}
+                logger.info("[%d/%d] train masking loss %.6g (alpha %g)", epoch + 1, args.num_epochs, res.avg_masking_loss,
+                            mask_alpha)
             if writer:
                 save.save_json_results(
                     save_dir=args.save_dir, norm_type=args.norm_type, attack_size=args.attack_size_string, epoch=epoch,
                     finished_training=False, eval_score_clean={"ctc": clean.ctc, "wer": clean.wer},
                     eval_score_perturbed={"ctc": goal.best(hist["pert_ctc"]), "wer": goal.best(hist["pert_wer"])},
-                    train_score={"ctc": goal.best(hist["train_ctc"]), "wer": goal.best(hist["train_wer"])})
+                    train_score={"ctc": goal.best(hist["train_ctc"]), "wer": goal.best(hist["train_wer"])}, **extra)
             current = pert.wer if args.attack_mode == "targeted" else pert.ctc     # run_attack.py:153
             if goal.improves(current, best_eval):
                 no_improve, best_eval, best_epoch = 0, current, epoch
@@ -105,7 +111,7 @@ def main(args) -> int:
                 eval_score_clean={"ctc": clean_test.ctc, "wer": clean_test.wer},
                 eval_score_perturbed={"ctc": pert_test.ctc, "wer": pert_test.wer},
                 final_test_clean={"ctc": clean_test.ctc, "wer": clean_test.wer},
-                final_test_perturbed={"ctc": pert_test.ctc, "wer": pert_test.wer}, best_epoch=best_epoch)
+                final_test_perturbed={"ctc": pert_test.ctc, "wer": pert_test.wer}, best_epoch=best_epoch, **extra)
         logger.info("done: best epoch %d | test clean ctc %.4f wer %.4f | test perturbed ctc %.4f wer %.4f", best_epoch,
                     clean_test.ctc, clean_test.wer, pert_test.ctc, pert_test.wer)
         return 0

@@ -94,6 +94,13 @@ def attack_size_string(args) -> str:
     return sizes[first]
 
 
+def masking_loss_suffix(args) -> str:
+    """Run-directory suffix of the masking-threshold loss term: "_ml<alpha>" when masking_loss_alpha > 0, else empty, so a
+    run without the term keeps the directory it always had (and resumes from it)."""
+    alpha = float(getattr(args, "masking_loss_alpha", 0.0))
+    return f"_ml{alpha:g}" if alpha > 0 else ""
+
+
 def create_logger(args, logs_root=None):
     """build.py:233-286: derive save_dir = <logs>/<mode>/<dataset>/<norm>_<size>_<mode>_<opt>, set up the "asr_attack"
     logger (rotating file + console) and discover a resumable checkpoint: an existing perturbation.pt in save_dir makes
@@ -104,7 +111,8 @@ def create_logger(args, logs_root=None):
     args.attack_size_string = attack_size_string(args)
     root = logs_root or getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"{args.norm_type}_{args.attack_size_string}_{args.attack_mode}_{args.optimizer_type}")
+                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}_{args.attack_mode}_"
+                                 f"{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)
     logger = logging.getLogger("asr_attack")
     logger.setLevel(logging.INFO)

@@ -7,6 +7,9 @@ Semantics (a per-clip step on B clips is B independent universal steps at batch 
     delta_b += lr * sign(g_b)   |   torch.optim.Adam over the (B, L) tensor
     delta_b  = perturbation_constraint(delta_b[None], x_b[None], args)   for every norm of args.norm_type, in order
 
+With ``args.masking_loss_alpha`` = alpha > 0 clip b's objective is direction * CTC_b - alpha * l_b(delta_b):
+``paa_masking_loss`` with one row per clip subtracts alpha * grad l_b from row b of the gradient right after the backward pass.
+
 One launch sequence per step (``paa_model_fwd_bwd_rows`` -> ``paa_sign_step`` / ``paa_adam_step`` over B*L elements ->
 ``paa_project_rows`` per norm) and no collective: clips are independent, so ranks never exchange gradients.  The Adam
 bookkeeping (optimizer.state, the pinned ring of per-step scalars, replay of a captured graph) is PgdStepper's.
@@ -17,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import _lib, runtime, synth
-from .pgd import N_STATS, RING, ST_LOSS, PgdStepper, _AdamGraph, adam_unsupported
+from .pgd import N_STATS, RING, ST_LOSS, ST_MASK_LOSS, PgdStepper, _AdamGraph, adam_unsupported
 
 
 class ClipStepper(PgdStepper):
@@ -60,6 +63,8 @@ class ClipStepper(PgdStepper):
         self._ring = [torch.zeros(4, dtype=torch.float32).pin_memory() for _ in range(RING)] if optimizer is not None else None
         self._ring_ev = [None] * RING
         self._ring_i = 0
+        self.mask_rows = torch.zeros(self.max_batch, dtype=torch.float32, device=self.dev)      # l_b of the last step
+        self._init_masking_loss()
 
     def _checked(self, delta, clean):
         delta = runtime.as_f32_cuda(delta, "delta")
@@ -80,6 +85,9 @@ class ClipStepper(PgdStepper):
         if logits_out is not None:
             out["logits"] = logits_out
         r = self.model.fwd_bwd(clean, delta, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
+        if self.mask_alpha > 0:
+            self._masking_loss(delta, clean, grad, self.mask_rows[:B])
+            r["masking_loss"] = self.mask_rows[:B]
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr()
             if self.optimizer is None:
@@ -109,6 +117,7 @@ class ClipStepper(PgdStepper):
         first pushes the step's scalars, and the warm-up step is undone (delta, moments and step count as before the call)."""
         delta, clean = self._checked(delta, clean)
         lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
+        self._alpha_captured = self.mask_alpha > 0
         saved = None
         if self.optimizer is not None:
             self._check_p(delta)

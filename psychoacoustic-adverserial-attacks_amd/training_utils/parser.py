@@ -43,6 +43,9 @@ def create_arg_parser():
     parser.add_argument('--max_phon_level', type=float, default=20)
     parser.add_argument('--masking_margin_db', type=float, default=0.0,
                         help='masking norm (extension): dB added to the clean clip\'s masking threshold')
+    parser.add_argument('--masking_loss_alpha', type=float, default=0.0,
+                        help='masking-threshold loss term (extension): the step optimises direction * CTC - alpha * sum_b l_b; '
+                             '0 = off')
     # sound properties (parser.py:57-63)
     parser.add_argument('--phon_reference_db', type=float, default=65)
     parser.add_argument('--sr', type=int, default=16000)

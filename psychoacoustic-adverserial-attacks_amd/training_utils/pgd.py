@@ -7,7 +7,7 @@ utterances; because HF's CTC reduction is 'sum', the global gradient is the sum 
 gradients, so ONE all-reduce (RCCL over xGMI via torch.distributed's "nccl" backend) per step of the packed
 f32 vector
 
-    [ grad (L) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, 0, 0 ]
+    [ grad (L) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, masking loss, 0 ]
 
 suffices; every rank then applies the identical sign step and projection, so replicas stay bit-identical
 without a broadcast.  ``sum clean^2`` / ``TV(clean)`` are there because project_snr / project_tv use
@@ -23,6 +23,13 @@ after the collective changes (``paa_adam_step`` instead of ``paa_sign_step``); t
 ``optimizer.state[p]``, so ``optimizer.state_dict()`` and a later plain ``optimizer.step()`` see the steps taken here.  The
 per-step scalars (-lr / (1 - beta1^t), sqrt(1 - beta2^t)) are computed on the host as torch does and reach the device
 through the same pinned ring as the WER counters, so a captured graph picks up the step count and a StepLR lr on replay.
+
+Masking-threshold loss term (``args.masking_loss_alpha`` = alpha > 0): the step optimises
+direction * CTC(x + delta) - alpha * sum_b l_b(delta).  ``paa_masking_loss`` runs right after the backward pass and subtracts
+alpha * grad(sum_b l_b) from the gradient BEFORE the all-reduce (the term is additive over clips, so the SUM carries it), and
+writes sum_b l_b of this rank's clips into slot 6 (ST_MASK_LOSS), which the all-reduce sums like the CTC loss.  alpha lives in a
+one-float device tensor (``set_masking_alpha``), so captured graphs follow it.  alpha = 0 launches nothing: the step is the plain
+one, bit for bit, and slot 6 stays 0.
 """
 from __future__ import annotations
 
@@ -32,7 +39,7 @@ from .. import _lib, runtime
 
 FREQ_NORMS = ("fletcher_munson", "min_max_freqs", "max_phon")
 N_STATS = 8
-ST_LOSS, ST_SQ, ST_TV, ST_WER_ERR, ST_WER_REF, ST_CLIPS = 0, 1, 2, 3, 4, 5
+ST_LOSS, ST_SQ, ST_TV, ST_WER_ERR, ST_WER_REF, ST_CLIPS, ST_MASK_LOSS = 0, 1, 2, 3, 4, 5, 6
 RING = 4
 
 
@@ -126,6 +133,61 @@ class PgdStepper:
             if (self.collective or optimizer is not None) else None
         self._ring_ev = [None] * RING
         self._ring_i = 0
+        self._init_masking_loss()
+
+    # ---- masking-threshold loss term ---------------------------------------------------------------------------
+    def _init_masking_loss(self):
+        self.mask_alpha = 0.0
+        self.alpha_dev = None
+        self._alpha_captured = None          # capture() records whether the captured launch sequence holds the term
+        a = type("A", (), dict(vars(self.args)))()
+        a.norm_type = "masking"
+        self._mask_prm = runtime.params_of(a)                 # paa_masking_loss reads masking_margin_db only
+        alpha = float(getattr(self.args, "masking_loss_alpha", 0.0))
+        if alpha < 0:
+            raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
+        if alpha > 0:
+            self.set_masking_alpha(alpha)
+
+    def set_masking_alpha(self, alpha: float):
+        """Weight of the masking-threshold loss term from the next step on.  The value goes to a one-float device tensor by a
+        stream-ordered copy from pinned memory, so eager steps and captured graphs alike follow it without recapture.  Whether
+        the term is in the launch sequence at all (alpha > 0) is fixed by ``capture()``: switching it on or off afterwards
+        raises."""
+        alpha = float(alpha)
+        if alpha < 0:
+            raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
+        if self._alpha_captured is not None and (alpha > 0) != self._alpha_captured:
+            raise ValueError("masking_loss_alpha cannot switch between 0 and > 0 after capture(): the captured launch sequence "
+                             f"{'holds' if self._alpha_captured else 'does not hold'} the loss term; capture the step again")
+        if alpha > 0:
+            if self.alpha_dev is None:
+                self.alpha_dev = torch.zeros(1, dtype=torch.float32, device=self.dev)
+                self._aring = [torch.zeros(1, dtype=torch.float32).pin_memory() for _ in range(RING)]
+                self._aring_ev = [None] * RING
+                self._aring_i = 0
+            k = self._aring_i % RING
+            self._aring_i += 1
+            if self._aring_ev[k] is not None:
+                self._aring_ev[k].synchronize()
+            self._aring[k][0] = alpha
+            with torch.cuda.device(self.dev):
+                self.alpha_dev.copy_(self._aring[k], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.dev))
+            self._aring_ev[k] = ev
+        elif self.mask_alpha > 0:
+            self.stats[ST_MASK_LOSS] = 0.0
+        self.mask_alpha = alpha
+
+    def _masking_loss(self, p, clean, grad, loss_rows=None):
+        """grad -= alpha * grad(sum_b l_b); sum_b l_b -> slot 6.  p (rows, L), rows in {1, B}."""
+        B = clean.shape[0]
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().paa_masking_loss(self.proj.h, self._mask_prm, _lib.ptr(p), p.shape[0] if p.dim() == 2 else 1,
+                                                   _lib.ptr(clean), B, self.L, _lib.ptr(self.alpha_dev), _lib.ptr(grad),
+                                                   _lib.ptr(loss_rows), _lib.ptr(self.stats[ST_MASK_LOSS:ST_MASK_LOSS + 1]), None,
+                                                   _lib.stream_ptr()))
 
     # ---- bookkeeping carried by the packed vector -------------------------------------------------------------
     def set_wer_counts(self, errors: float, ref_words: float):
@@ -185,6 +247,9 @@ class PgdStepper:
         if logits_out is not None:
             out["logits"] = logits_out
         r = self.model.fwd_bwd(clean, p, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
+        if self.mask_alpha > 0:
+            self._masking_loss(p, clean, self.grad)
+            r["masking_loss"] = self.stats[ST_MASK_LOSS]
         if self.need_clean_stats:
             with torch.cuda.device(self.dev):
                 _lib.check(_lib.lib().paa_batch_stats(self.proj.h, _lib.ptr(clean), B, self.L, _lib.ptr(self.stats[ST_SQ:ST_TV + 1]),
@@ -222,9 +287,9 @@ class PgdStepper:
         return self._body(p, clean, labels, want_logits, logits_out)
 
     def _fit_proj(self, B):
-        """The masking norm keeps one bound per clip of the batch: grow the projection workspace to the batch (allocates, so
-        it happens in an eager step; capture() runs one first)."""
-        if "masking" in self.norms and self.proj.max_batch < B:
+        """The masking norm and the masking loss keep one bound per clip of the batch: grow the projection workspace to the
+        batch (allocates, so it happens in an eager step; capture() runs one first)."""
+        if ("masking" in self.norms or self.mask_alpha > 0) and self.proj.max_batch < B:
             self.proj = runtime.get_proj(self.args, self.dev, B, self.L, self.interp)
 
     def _check_p(self, p):
@@ -249,6 +314,7 @@ class PgdStepper:
         and eps are captured by value (``replay()`` raises ValueError once they change), and the warm-up step is undone:
         ``p``, the optimizer state and the step count are as before the call."""
         lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
+        self._alpha_captured = self.mask_alpha > 0
         saved = None
         if self.optimizer is not None:
             self._check_p(p)

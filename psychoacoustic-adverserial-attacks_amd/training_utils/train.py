@@ -23,6 +23,7 @@ class TrainEpochResult:          # train.py:15-19
     p: torch.Tensor
     avg_ctc: float
     avg_wer: float
+    avg_masking_loss: float = None        # mean over the steps of sum_b l_b (masking_loss_alpha > 0 only)
 
 
 def _avg(values: Iterable[float]) -> float:
@@ -114,6 +115,11 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
     # AMSGrad, ...): there it is what the reference runs, and the data-parallel machinery has nothing to add.
     eager_adam = args.optimizer_type == "adam" and adam_route(optimizer, world) == "eager"
     step_opt = optimizer if args.optimizer_type == "adam" and not eager_adam else None
+    mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
+    if eager_adam and mask_alpha > 0:
+        raise NotImplementedError("masking_loss_alpha > 0 needs the device step: use the defaults of torch.optim.Adam(lr=...) "
+                                  "or --optimizer_type pgd")
+    mask_scores = []
     stepper = getattr(model, "_stepper", None)
     if stepper is None or stepper.args is not args or stepper.L != L or stepper.optimizer is not step_opt:
         stepper = PgdStepper(model, args, L, interp, spl_thresh, optimizer=step_opt)
@@ -138,6 +144,8 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
             with torch.no_grad():
                 p.data = perturbation_constraint(p.data, clean_audio, args, interp, spl_thresh)   # train.py:172-175
         ctc_scores.append(float(r["loss"].item()))                                   # train.py:146
+        if mask_alpha > 0:
+            mask_scores.append(float(r["masking_loss"].item()))
         pred_texts, ref_texts = loss_helpers.wer_texts(r["logits"], target_texts, processor)       # train.py:149-153
         e, w = loss_helpers.wer_counts(pred_texts, ref_texts)
         wer_counts.append((e, w))
@@ -147,4 +155,5 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
         times.append(time.perf_counter() - t0)
     if stepper.world > 1:                     # the loss in stats[0] is already the global batch's; make the WER global too
         wer_scores = global_wer_per_step(wer_counts, stepper.dev, stepper.group)
-    return TrainEpochResult(p=p, avg_ctc=_avg(ctc_scores), avg_wer=_avg(wer_scores))
+    return TrainEpochResult(p=p, avg_ctc=_avg(ctc_scores), avg_wer=_avg(wer_scores),
+                            avg_masking_loss=_avg(mask_scores) if mask_alpha > 0 else None)
