@@ -726,6 +726,7 @@ static paa_status project_impl(paa_proj* h, const paa_params* prm, float* d_p, i
     }
     const bool scale_type = nt == PAA_NORM_L2 || nt == PAA_NORM_SNR || nt == PAA_NORM_TV || nt == PAA_NORM_LINF;
     if (d_src && !scale_type) {          // the generic frame kernels work in place: copy first
+        PAA_TRY(check_rows(h, rows_p, L, "paa_project"));      // a refused size must leave the destination untouched
         PAA_HIP(hipMemcpyAsync(d_p, d_src, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
     }
     const float* d_in = d_src ? d_src : d_p;      // scale-type norms and linf: the reduction and the scaling pass read the source directly

@@ -1,0 +1,429 @@
+"""-m gpu: the generic frame kernels (proj_kernels.hip: fft_lds, k_frame<OP>, k_ola, k_fm_finalize and the copy-then-in-place
+branches of the projections), which every frame geometry other than n_fft = 1024 / hop = 256 runs, against the float64
+restatement of stft_ref.py (pinned on the CPU by test_stft_ref_host.py) and, more coarsely, against the float32 oracle.
+
+The bounds are the ones the fused 1024 / 256 path is held to (test_gpu_projections.py): 5e-6 of max|ref| for STFT and iSTFT,
+TOL = 2e-5 for the projections; the float32 oracle itself sits at 1e-7 .. 5e-7 of the float64 reference at every geometry."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import stft_ref as R
+from gpu_util import rel_err
+from oracle import projections as OP
+from oracle.gen_cases import PGD_TEXTS
+from paa_amd import _lib, arch as A, runtime
+from paa_amd.core import fourier_transforms
+from paa_amd.training_utils import build
+
+pytestmark = pytest.mark.gpu
+STFT_TOL = 5e-6
+TOL = 2e-5
+GUARD = 256          # floats in front of and behind every guarded buffer
+CANARY = -1234.5
+MAX_L = 16001
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _fresh_projection_contexts():
+    """The sweep loads max_phon contours into the process-wide projection contexts (runtime.get_proj); drop them afterwards so
+    that later modules start from fresh ones."""
+    yield
+    torch.cuda.synchronize()
+    runtime._PROJ.clear()
+
+
+def _ctx(norm, n_fft, hop, rows=max(R.ROWS), L=MAX_L, **kw):
+    args = R.geometry_args(norm, n_fft, hop, **kw)
+    args.device = "cuda"
+    pr = runtime.get_proj(args, torch.device("cuda"), rows, L)
+    if norm == "max_phon":
+        pr.set_spl_thresh(build.init_phon_threshold_tensor(args))
+    return args, pr, runtime.params_of(args)
+
+
+def _guarded(rows, L, fill):
+    """(flat, view): ``view`` (rows, L) sits between two runs of GUARD canary floats."""
+    flat = torch.full((2 * GUARD + rows * L,), CANARY, device="cuda")
+    view = flat[GUARD:GUARD + rows * L].view(rows, L)
+    if isinstance(fill, torch.Tensor):
+        view.copy_(fill)
+    else:
+        view.fill_(fill)
+    return flat, view
+
+
+def _guards_intact(flat):
+    return bool((flat[:GUARD] == CANARY).all()) and bool((flat[-GUARD:] == CANARY).all())
+
+
+def _status(st):
+    return st, _lib.lib().paa_last_error().decode(errors="replace")
+
+
+def _project(pr, prm, x):
+    """paa_project: in place on a copy."""
+    q = x.clone()
+    _lib.check(_lib.lib().paa_project(pr.h, prm, _lib.ptr(q), q.shape[0], None, 0, q.shape[1], _lib.stream_ptr()))
+    return q
+
+
+def _project_to(pr, prm, src, dst=None):
+    dst = torch.full_like(src, float("nan")) if dst is None else dst
+    _lib.check(_lib.lib().paa_project_to(pr.h, prm, _lib.ptr(src), _lib.ptr(dst), src.shape[0], None, 0, src.shape[1],
+                                         _lib.stream_ptr()))
+    return dst
+
+
+def _project_rows(pr, prm, src, dst=None):
+    dst = torch.full_like(src, float("nan")) if dst is None else dst
+    _lib.check(_lib.lib().paa_project_rows(pr.h, prm, _lib.ptr(src), _lib.ptr(dst), src.shape[0], None, src.shape[1],
+                                           _lib.stream_ptr()))
+    return dst
+
+
+def _scale(norm, eps):
+    return eps / max(norm, 1e-8) if norm > eps else 1.0
+
+
+# ------------------------------------------------------------------------------------------------ STFT / iSTFT
+@pytest.mark.parametrize("n_fft,hop", R.GEOMETRIES)
+def test_stft_istft_vs_float64(n_fft, hop):
+    args, pr, _ = _ctx("max_phon", n_fft, hop)
+    F = n_fft // 2 + 1
+    worst = [0.0, 0.0]
+    for L in R.lengths(n_fft, hop):
+        x = R.signal(n_fft, hop, L)
+        T = 1 + L // hop
+        S_ref = R.stft(x, n_fft, hop)
+        # the inverse is checked on the SAME float32 spectrum the kernel reads; a second one has Im(DC), Im(Nyquist) != 0
+        S32 = S_ref.astype(np.complex64)
+        S32b = S32.copy()
+        S32b[..., 0] += np.complex64(0.7j)
+        S32b[..., -1] -= np.complex64(0.3j)
+        y_ref = R.istft(S32, n_fft, hop)
+        assert np.array_equal(y_ref, R.istft(S32b, n_fft, hop))
+        # ... and a third is no signal's STFT: overlapping frames disagree, so the overlap-add cannot hide behind its own
+        # envelope (frames of a true STFT all carry x * w: a frame dropped from sum AND envelope would still give x back)
+        S32c = R.random_spectrum(n_fft, hop, L)
+        y_refc = R.istft(S32c, n_fft, hop)
+        xc = torch.from_numpy(x).cuda()
+        for rows in R.ROWS:
+            S = fourier_transforms.compute_stft(xc[:rows].contiguous(), args)
+            assert tuple(S.shape) == (rows, F, T) and S.dtype == torch.complex64
+            assert tuple(S.transpose(1, 2).shape) == (rows, T, F) and S.transpose(1, 2).is_contiguous()
+            got = S.transpose(1, 2).cpu().numpy()
+            assert np.isfinite(got.view(np.float32)).all()
+            e = float(np.abs(got - S_ref[:rows]).max() / np.abs(S_ref[:rows]).max())
+            worst[0] = max(worst[0], e)
+            assert e <= STFT_TOL, ("stft", n_fft, hop, L, rows, e)
+            for spec, want in ((S32, y_ref), (S32b, y_ref), (S32c, y_refc)):
+                y = fourier_transforms.compute_istft(torch.from_numpy(spec[:rows]).cuda().transpose(1, 2), args)
+                assert tuple(y.shape) == (rows, hop * (T - 1))
+                e = rel_err(y.cpu().numpy(), want[:rows])
+                worst[1] = max(worst[1], e)
+                assert e <= STFT_TOL, ("istft", n_fft, hop, L, rows, e)
+    print(f"({n_fft}, {hop}): worst rel err stft {worst[0]:.2e} istft {worst[1]:.2e}")
+
+
+# ------------------------------------------------------------------------------------------------ projections
+def _check(got, ref64, ref32, valid, what, worst, rows32=None):
+    """Every element against the float64 reference; against the float32 oracle too (its rows ``rows32`` when given)."""
+    g = got.cpu().numpy()
+    g32 = g if rows32 is None else g[rows32]
+    assert g.shape == ref64.shape and g32.shape == ref32.shape, what
+    assert np.isfinite(g).all(), what
+    assert not g[:, valid:].any(), (what, "samples at and beyond hop * (T - 1) must be exactly zero")
+    e64, e32 = rel_err(g, ref64), rel_err(g32, ref32)
+    worst[0], worst[1] = max(worst[0], e64), max(worst[1], e32)
+    assert e64 <= TOL, (what, "float64 reference", e64)
+    assert e32 <= TOL, (what, "float32 oracle", e32)
+
+
+@pytest.mark.parametrize("n_fft,hop", R.GEOMETRIES)
+def test_projections_vs_float64_and_oracle(n_fft, hop):
+    """paa_project (in place), paa_project_to and paa_project_rows (out of place and in place) for the three spectral norms,
+    1 / 3 / 33 rows, every length of the sweep.  fletcher_munson runs with its bound a factor 2 under and a factor 2 over the
+    weighted norm (of the whole tensor for the universal calls; of row 0 for the per-row call, where the loud row is then
+    scaled and the quiet rows are not, and half the smallest row norm, where every row is)."""
+    sr = 16000
+    worst = {n: [0.0, 0.0] for n in R.SPECTRAL_NORMS}
+    for L in R.lengths(n_fft, hop):
+        x = R.signal(n_fft, hop, L)
+        xt = torch.from_numpy(x)
+        xc = xt.cuda()
+        valid = hop * (L // hop)
+        for norm in ("min_max_freqs", "max_phon"):           # row-local: one reference for all row counts
+            args, pr, prm = _ctx(norm, n_fft, hop)
+            spl = OP.spl_thresh_tensor(args)
+            ref64 = R.project(x, norm, args, spl.numpy())
+            ref32 = OP.perturbation_constraint(xt, xt, args, spl).numpy()
+            assert ref64.any()
+            for rows in R.ROWS:
+                src = xc[:rows].contiguous()
+                for name, got in (("project", _project(pr, prm, src)), ("project_to", _project_to(pr, prm, src)),
+                                  ("project_rows", _project_rows(pr, prm, src)),
+                                  ("project_rows in place", _rows_in_place(pr, prm, src))):
+                    _check(got, ref64[:rows], ref32[:rows], valid, (norm, name, n_fft, hop, L, rows), worst[norm])
+        # fletcher_munson: the per-bin op is one factor, so the float64 result is that factor times the STFT -> iSTFT identity
+        norm = "fletcher_munson"
+        a_inf = R.geometry_args(norm, n_fft, hop, fm_epsilon=float("inf"))
+        base = R.project(x, norm, a_inf)
+        pw = R.fm_row_power(R.stft(x, n_fft, hop), n_fft, sr)
+        for rows in R.ROWS:
+            src = xc[:rows].contiguous()
+            n_all = float(np.sqrt(pw[:rows].sum()))
+            for eps in (0.5 * n_all, 2.0 * n_all):
+                args, pr, prm = _ctx(norm, n_fft, hop, fm_epsilon=eps)
+                ref64 = base[:rows] * _scale(n_all, float(np.float32(eps)))
+                ref32 = OP.perturbation_constraint(xt[:rows], xt[:rows], args).numpy()
+                for name, got in (("project", _project(pr, prm, src)), ("project_to", _project_to(pr, prm, src))):
+                    _check(got, ref64, ref32, valid, (norm, name, n_fft, hop, L, rows, eps), worst[norm])
+            n_row = np.sqrt(pw[:rows])
+            for eps in (2.0 * float(n_row[0]), 0.5 * float(n_row.min())):
+                args, pr, prm = _ctx(norm, n_fft, hop, fm_epsilon=eps)
+                sc = np.array([_scale(float(n), float(np.float32(eps))) for n in n_row])
+                assert eps < n_row.min() or rows <= R.LOUD_ROW or (sc[R.LOUD_ROW] < 1 and sc[0] == 1)
+                ref64 = base[:rows] * sc[:, None]
+                # the oracle takes one row per call (each rebuilds its weight grid): every row at 1 and 3 rows, four of 33
+                pick = sorted({0, min(1, rows - 1), rows // 2, rows - 1})
+                ref32 = np.concatenate([OP.perturbation_constraint(xt[r:r + 1], xt[r:r + 1], args).numpy() for r in pick])
+                for name, got in (("project_rows", _project_rows(pr, prm, src)), ("project_rows in place", _rows_in_place(pr, prm, src))):
+                    _check(got, ref64, ref32, valid, (norm, name, n_fft, hop, L, rows, eps), worst[norm], pick)
+    print(f"({n_fft}, {hop}): worst rel err vs float64 / vs float32 oracle  " +
+          "  ".join(f"{n} {w[0]:.2e} / {w[1]:.2e}" for n, w in worst.items()))
+
+
+def _rows_in_place(pr, prm, src):
+    q = src.clone()
+    return _project_rows(pr, prm, q, q)
+
+
+# ------------------------------------------------------------------------------------------------ structure, bit for bit
+@pytest.mark.parametrize("n_fft,hop", R.GEOMETRIES)
+def test_structure_bit_for_bit(n_fft, hop):
+    """One workgroup per frame and one thread per output sample whatever the row count: out of place equals in place, a row of
+    a 33-row call equals that row alone, a call repeats itself — all bit for bit; nothing is written outside the buffers."""
+    rows = max(R.ROWS)
+    for L in (n_fft + 37, MAX_L):
+        x = torch.from_numpy(R.signal(n_fft, hop, L)).cuda()
+        for norm in R.SPECTRAL_NORMS:
+            kw = {}
+            if norm == "fletcher_munson":        # under the whole tensor's norm and under every row's
+                pw = R.fm_row_power(R.stft(x.cpu().numpy(), n_fft, hop), n_fft, 16000)
+                kw = dict(fm_epsilon=0.5 * float(np.sqrt(pw.min())))
+            args, pr, prm = _ctx(norm, n_fft, hop, **kw)
+            sflat, src = _guarded(rows, L, x)
+            dflat, dst = _guarded(rows, L, float("nan"))
+            a = _project(pr, prm, src)
+            _project_to(pr, prm, src, dst)
+            assert torch.isfinite(dst).all(), (norm, L)
+            assert torch.equal(a, dst), (norm, L, "paa_project_to != paa_project on a clone")
+            assert torch.equal(src, x), (norm, L, "the source must stay untouched")
+            assert _guards_intact(sflat) and _guards_intact(dflat), (norm, L)
+            assert float((a - x).abs().max()) > 0, (norm, L, "the projection did nothing")
+            again = _project_to(pr, prm, src)
+            assert torch.equal(again, dst), (norm, L, "two identical calls differ")
+            rflat, many = _guarded(rows, L, float("nan"))
+            _project_rows(pr, prm, src, many)
+            assert torch.isfinite(many).all() and _guards_intact(rflat) and _guards_intact(sflat) and torch.equal(src, x), (norm, L)
+            assert torch.equal(_project_rows(pr, prm, src), many), (norm, L, "two identical calls differ")
+            assert torch.equal(_rows_in_place(pr, prm, src), many), (norm, L, "paa_project_rows in place != out of place")
+            for r in range(rows):
+                one = _project_to(pr, prm, x[r:r + 1].contiguous())
+                if norm != "fletcher_munson":
+                    assert torch.equal(one[0], many[r]), (norm, L, r, "row of paa_project_rows != the row alone")
+                    assert torch.equal(one[0], dst[r]), (norm, L, r, "row of paa_project_to != the row alone")
+                else:
+                    # k_fm_finalize sums a row's frame partials in another order than the one-row call: same scale to TOL
+                    assert rel_err(many[r].cpu().numpy(), one[0].cpu().numpy()) <= TOL, (norm, L, r)
+
+
+# ------------------------------------------------------------------------------------------------ error contract
+def _create(n_fft, hop, win, max_batch=1, max_len=20000):
+    h = C.c_void_p()
+    st = _lib.lib().paa_proj_create(C.byref(h), n_fft, hop, win, 16000, None, None, max_batch, max_len)
+    msg = _lib.lib().paa_last_error().decode(errors="replace")
+    if st == _lib.PAA_OK:
+        _lib.lib().paa_proj_destroy(h)
+    return st, msg, h.value
+
+
+@pytest.mark.parametrize("n_fft,hop,win,text", [
+    (48, 12, 48, "n_fft=48 unsupported"), (32, 8, 32, "n_fft=32 unsupported"), (8192, 2048, 8192, "n_fft=8192 unsupported"),
+    (512, 128, 400, "win_length=400 != n_fft=512"), (512, 0, 512, "hop_length=0 out of range"),
+    (512, 513, 512, "hop_length=513 out of range"), (512, 512, 512, "envelope is zero")])
+def test_create_refuses(n_fft, hop, win, text):
+    st, msg, h = _create(n_fft, hop, win)
+    assert st == _lib.PAA_ERR_ARG and text in msg and not h, (st, msg)
+
+
+@pytest.mark.parametrize("n_fft,hop", R.GEOMETRIES)
+def test_create_accepts_the_sweep(n_fft, hop):
+    st, msg, _ = _create(n_fft, hop, n_fft)
+    assert st == _lib.PAA_OK, (st, msg)
+
+
+def test_size_errors_launch_nothing():
+    lib = _lib.lib()
+    n_fft, hop = 512, 128
+    args, pr, prm = _ctx("min_max_freqs", n_fft, hop)
+    F = n_fft // 2 + 1
+    L = n_fft // 2                                             # reflect padding needs L > n_fft / 2
+    x = torch.from_numpy(R.signal(n_fft, hop, L, 1)).cuda()
+    out = torch.full((1, 1 + L // hop, F, 2), float("nan"), device="cuda")
+    st, msg = _status(lib.paa_stft(pr.h, _lib.ptr(x), 1, L, _lib.ptr(out), _lib.stream_ptr()))
+    assert st == _lib.PAA_ERR_SIZE and "must exceed n_fft/2=256" in msg, (st, msg)
+    q = x.clone()
+    st, msg = _status(lib.paa_project(pr.h, prm, _lib.ptr(q), 1, None, 0, L, _lib.stream_ptr()))
+    assert st == _lib.PAA_ERR_SIZE and "must exceed n_fft/2=256" in msg, (st, msg)
+    dst = torch.full_like(x, float("nan"))
+    st, msg = _status(lib.paa_project_to(pr.h, prm, _lib.ptr(x), _lib.ptr(dst), 1, None, 0, L, _lib.stream_ptr()))
+    assert st == _lib.PAA_ERR_SIZE, (st, msg)
+    S = torch.zeros(1, 1, F, 2, device="cuda")
+    y = torch.full((1, hop), float("nan"), device="cuda")
+    st, msg = _status(lib.paa_istft(pr.h, _lib.ptr(S), 1, 1, _lib.ptr(y), _lib.stream_ptr()))
+    assert st == _lib.PAA_ERR_SIZE and "paa_istft: T=1" in msg, (st, msg)
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all() and torch.isnan(y).all() and torch.isnan(dst).all() and torch.equal(q, x)
+    with pytest.raises(ValueError):                            # the Python surface maps PAA_ERR_SIZE to ValueError
+        fourier_transforms.compute_stft(x, args)
+
+
+def test_one_frame_clip():
+    """L < hop: T = 1 and the iSTFT has hop * (T - 1) = 0 samples.  The reference's torch.istft RAISES on such a clip
+    (test_stft_ref_host.py), so there is no reference value to assert; the library answers with the _align_to rule alone (all
+    padding).  DESIGN.md §4 records the difference; here: the call succeeds, writes finite values and stays in its buffer."""
+    n_fft, hop, L = 512, 384, 257
+    assert 1 + L // hop == 1
+    x = torch.from_numpy(R.signal(n_fft, hop, L, 3)).cuda()
+    for norm in R.SPECTRAL_NORMS:
+        args, pr, prm = _ctx(norm, n_fft, hop, fm_epsilon=1e-3)
+        for call in (_project_to, _project_rows):
+            flat, dst = _guarded(3, L, float("nan"))
+            call(pr, prm, x, dst)
+            assert torch.isfinite(dst).all() and _guards_intact(flat), (norm, call.__name__)
+
+
+def test_spectrum_functions_need_513_bins_and_work_at_1024_200():
+    lib = _lib.lib()
+    _, pr, prm = _ctx("min_max_freqs", 512, 128)
+    S = torch.zeros(1, 4, 257, 2, device="cuda")
+    out = torch.full_like(S, float("nan"))
+    st, msg = _status(lib.paa_spectrum_project(pr.h, prm, _lib.ptr(S), _lib.ptr(out), 1, 4, _lib.stream_ptr()))
+    assert st == _lib.PAA_ERR_ARG and "only 1024 is built" in msg, (st, msg)
+    one = torch.full((1,), float("nan"), device="cuda")
+    st, msg = _status(lib.paa_fm_weighted_norm(pr.h, _lib.ptr(S), 1, 4, _lib.ptr(one), _lib.stream_ptr()))
+    assert st == _lib.PAA_ERR_ARG and "only 1024 is built" in msg, (st, msg)
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all() and torch.isnan(one).all()
+
+    n_fft, hop, L, rows = 1024, 200, 5 * 1024 + 3, 3
+    x = R.signal(n_fft, hop, L, rows)
+    S32 = R.stft(x, n_fft, hop).astype(np.complex64)
+    T = S32.shape[1]
+    Sc = torch.view_as_real(torch.from_numpy(S32)).contiguous().cuda()
+    n_all = R.fm_norm(S32, n_fft, 16000)
+    args, pr, _ = _ctx("fletcher_munson", n_fft, hop)
+    st, msg = _status(lib.paa_fm_weighted_norm(pr.h, _lib.ptr(Sc), rows, T, _lib.ptr(one), _lib.stream_ptr()))
+    assert st == _lib.PAA_OK, msg
+    print(f"(1024, 200) fm_weighted_norm {float(one):.6f} vs float64 {n_all:.6f}")
+    assert float(one) == pytest.approx(n_all, rel=TOL)
+    spl = OP.spl_thresh_tensor(args).numpy()
+    for norm, kw in (("min_max_freqs", {}), ("max_phon", {}), ("fletcher_munson", dict(fm_epsilon=0.5 * n_all)),
+                     ("fletcher_munson", dict(fm_epsilon=2.0 * n_all))):
+        args, pr, prm = _ctx(norm, n_fft, hop, **kw)
+        ref = R.spectrum_project(S32.astype(np.complex128), norm, args, spl)
+        out = torch.full_like(Sc, float("nan"))
+        st, msg = _status(lib.paa_spectrum_project(pr.h, prm, _lib.ptr(Sc), _lib.ptr(out), rows, T, _lib.stream_ptr()))
+        assert st == _lib.PAA_OK, msg
+        got = torch.view_as_complex(out).cpu().numpy()
+        e = float(np.abs(got - ref).max() / np.abs(ref).max())
+        print(f"(1024, 200) paa_spectrum_project {norm} {kw}: {e:.2e}")
+        assert np.isfinite(out.cpu().numpy()).all() and e <= TOL, (norm, e)
+
+
+# ------------------------------------------------------------------------------------------------ through the Python surface
+STEP_GEOMETRY = ["--n_fft", "512", "--hop_length", "128", "--win_length", "512"]
+
+
+def test_pgd_step_vs_oracle_512_128():
+    from oracle.gen_cases import cli_to_args
+    from test_gpu_model import _step_vs_oracle
+    args = cli_to_args("max_phon", STEP_GEOMETRY)
+    _step_vs_oracle(A.tiny(), 8000, 2, args, "fp32", PGD_TEXTS[:2], 5e-3, 5e-3)
+
+
+def test_clip_step_vs_oracle_fm_512_128():
+    from oracle.gen_cases import cli_to_args
+    from test_gpu_clip_attack import _clip_step_vs_oracle
+    args = cli_to_args("fletcher_munson", STEP_GEOMETRY + ["--fm_epsilon", "0.5"])
+    _clip_step_vs_oracle(A.tiny(), 8000, 3, args, PGD_TEXTS[:3])
+
+
+def test_clip_replay_equals_eager_fm_512_128():
+    from oracle import pgd as opgd
+    from oracle.gen_cases import cli_to_args
+    from paa_amd import synth
+    from paa_amd.model import PaaModel
+    from paa_amd.training_utils.clip_attack import ClipStepper
+    a = A.tiny()
+    B, L = 3, 8000
+    args = cli_to_args("fletcher_munson", STEP_GEOMETRY + ["--fm_epsilon", "0.5"])
+    args.device = "cuda"
+    m = PaaModel(a, A.rule_weights(a), B, L, "fp32")
+    clean = torch.from_numpy(synth.clean_audio(B, L)).cuda()
+    labels = opgd.make_labels(PGD_TEXTS[:B], args, B)
+    st = ClipStepper(m, args, L, None, build.init_phon_threshold_tensor(args))
+    d0 = torch.from_numpy(np.stack([synth.normal(synth.key_of(f"d{b}", 5), L) for b in range(B)]).astype(np.float32) * 1e-2).cuda()
+    de = d0.clone()
+    for _ in range(3):
+        st.step(de, clean, labels)
+    dg = d0.clone()
+    g, r = st.capture(dg, clean, labels)
+    dg.copy_(d0)
+    for _ in range(3):
+        g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(dg, de)
+    assert torch.isfinite(r["loss"]).item() and float((de - d0).abs().max()) > 0
+
+
+def test_full_size_rows_512_128():
+    """(32, 160000) at (512, 128): every row of the batched call against that row alone (bit for bit for the row-local norms,
+    the per-row scale to TOL for fletcher_munson), rows 0, 1, 16, 31 against the float32 oracle and the float64 reference."""
+    n_fft, hop, rows, L = 512, 128, 32, 160000
+    g = torch.Generator().manual_seed(rows * 1000003 + L)
+    x = torch.randn(rows, L, generator=g) * 0.05
+    x[1] *= 10.0
+    xc = x.cuda()
+    picked = [0, 1, 16, 31]
+    valid = hop * (L // hop)
+    # a fletcher_munson bound between the quiet rows' weighted norm and the loud row's: row 1 is scaled, row 0 is not
+    n0, n1 = np.sqrt(R.fm_row_power(R.stft(x[:2].numpy(), n_fft, hop), n_fft, 16000))
+    assert n1 > 4.0 * n0, (n0, n1)
+    for norm, kw in (("min_max_freqs", {}), ("max_phon", {}), ("fletcher_munson", dict(fm_epsilon=float(np.sqrt(n0 * n1))))):
+        args, pr, prm = _ctx(norm, n_fft, hop, rows, L, **kw)
+        spl = OP.spl_thresh_tensor(args)
+        many = _project_rows(pr, prm, xc)
+        assert bool(torch.isfinite(many).all()), norm
+        assert not bool(many[:, valid:].any()), norm
+        if norm != "fletcher_munson":
+            assert torch.equal(_project_to(pr, prm, xc), many), norm
+        worst = 0.0
+        for r in range(rows):
+            one = _project_to(pr, prm, xc[r:r + 1].contiguous())
+            if norm != "fletcher_munson":
+                assert torch.equal(one[0], many[r]), (norm, r, float((one[0] - many[r]).abs().max()))
+            else:
+                assert rel_err(many[r].cpu().numpy(), one[0].cpu().numpy()) <= TOL, (norm, r)
+        for r in picked:
+            ref32 = OP.perturbation_constraint(x[r:r + 1], x[r:r + 1], args, spl).numpy()
+            ref64 = R.project(x[r:r + 1].numpy(), norm, args, spl.numpy())
+            got = many[r:r + 1].cpu().numpy()
+            e32, e64 = rel_err(got, ref32), rel_err(got, ref64)
+            worst = max(worst, e32, e64)
+            assert e32 <= TOL and e64 <= TOL, (norm, r, e32, e64)
+        print(f"(32, 160000) at (512, 128) {norm}: worst picked-row rel err {worst:.2e}")
