@@ -46,7 +46,7 @@ typedef struct {
 } paa_params;
 
 const char* paa_last_error(void);
-/* 320 = this header; 321 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
+/* 330 = this header (320 + paa_wer_counts and paa_stats_push); 331 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
  * tools/ only).  Bindings refuse other values. */
 int paa_version(void);
 /* sizeof(paa_params), sizeof(paa_arch), sizeof(paa_tensor), sizeof(paa_gemm_desc): layout check for bindings */
@@ -223,7 +223,9 @@ int paa_model_frames(const paa_model* m);     /* T_e for the configured length *
  *   d_logits (B, T_e, V) out (may be NULL)
  *   d_stats  (8) out: [0] loss (sum over the batch, HF ctc_loss_reduction='sum').  Slots [1..7] are NOT written by
  *            this call: they belong to the caller's data-parallel bookkeeping (paa_amd/training_utils/pgd.py packs
- *            [1] sum clean^2 and [2] TV(clean) from paa_batch_stats, [3] WER word errors, [4] WER reference words,
+ *            [1] sum clean^2 and [2] TV(clean) from paa_batch_stats, [3] WER word errors, [4] WER reference words — the host's
+ *            counters of the PREVIOUS step by default, THIS step's own counters written by paa_wer_counts (d_sums) with
+ *            device_wer=True —,
  *            [5] the local clip count B (paa_batch_stats), [6] sum_b l_b of paa_masking_loss (masking_loss_alpha > 0, else 0),
  *            behind the gradient, so that ONE all-reduce carries everything
  *            and the global clean.numel() = L * sum_r B_r needs no collective of its own).
@@ -252,6 +254,29 @@ paa_status paa_model_forward_rows(paa_model* m, const float* d_clean, const floa
 /* core/loss_helpers.py:26,61  pred_ids = torch.argmax(logits, dim=-1): d_logits (rows, V) f32 -> d_ids (rows) int16
  * (first maximum wins; a NaN counts as the maximum, as in torch).  Feeds the host-side greedy CTC decode / WER. */
 paa_status paa_argmax_ids(const float* d_logits, int64_t rows, int V, int16_t* d_ids, void* stream);
+
+/* ---- on-device greedy CTC decode + word error counters (extension) -----------------------------------------
+ * core/loss_helpers.py greedy_decode_ids + wer_texts + wer_counts on integers, one clip per workgroup, no host round trip.
+ *   d_ids    (B, T) int16, what paa_argmax_ids writes
+ *   d_canon  (V) int32: -1 = drop (special token), 0 = word delimiter, > 0 = code point of the token's lower-cased character;
+ *            an id outside [0, V) is dropped
+ *   d_refs   (B, R_cap) int32 code points: the words of the cleaned, lower-cased reference one after another, each terminated
+ *            by 0, the row padded with -1 (a row ends at its first negative entry; entries behind an unterminated last word
+ *            are not a word)
+ * Frames whose id maps to -1 are dropped FIRST; a surviving frame is kept iff its id differs from the id of the previous
+ * surviving frame ("A <pad> A" is one A: transformers 5.15 batch_decode, tests/golden/labels.json).  Hypothesis words are the
+ * maximal runs of kept non-delimiter tokens; two words are equal iff length and every code point agree (compared in full);
+ * errors = unit-cost Levenshtein distance between the two word sequences (either may be empty).
+ *   d_counts (B, 3) int32 out: errors, reference words, hypothesis words of every clip
+ *   d_sums   [2] float out, nullable: sum_b errors, sum_b reference words — integer sums converted once: exact, and the same
+ *            bits in every run (no atomics)
+ * Caps: 1 <= T <= 4096, 1 <= R_cap <= 8192 and the clip's LDS image (10 R_cap + 6 T bytes) within 64 KiB, else
+ * PAA_ERR_SIZE; null pointers, B <= 0 or V outside [1, 32767]: PAA_ERR_ARG.  Nothing is truncated. */
+paa_status paa_wer_counts(const int16_t* d_ids, int B, int T, const int32_t* d_canon, int V, const int32_t* d_refs, int R_cap,
+                          int32_t* d_counts, float* d_sums, void* stream);
+/* Per-step stats log: copies d_stats[0..n) to row (*d_cursor mod cap) of d_log (cap, n) and increments *d_cursor ON THE DEVICE,
+ * so a captured graph appends a new row on every replay.  1 <= n <= 64, cap >= 1, else PAA_ERR_ARG. */
+paa_status paa_stats_push(const float* d_stats, int n, float* d_log, int32_t* d_cursor, int cap, void* stream);
 
 /* Diagnostics for tests: synchronous copy of a named internal activation to the host (see csrc/model.hip);
  * returns the number of floats the buffer holds for batch B (0 = unknown name, <0 = HIP error). */

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PAA_EXTRA_HIPCC_FLAGS (tools/ only: diagnostic builds, see build_ext.py) selects the diagnostic library built next to the shipped one
 LIB_PATH = os.path.join(HERE, "libpaa_hip_exp.so" if os.environ.get("PAA_EXTRA_HIPCC_FLAGS", "").strip() else "libpaa_hip.so")
 
-ABI_VERSIONS = (320, 321)      # include/paa_hip.h paa_version: 321 = the same ABI built with -DPAA_EXPERIMENTS
+ABI_VERSIONS = (330, 331)      # include/paa_hip.h paa_version: 331 = the same ABI built with -DPAA_EXPERIMENTS
 
 PAA_OK, PAA_ERR_BAD_NORM, PAA_ERR_NEED_CLEAN, PAA_ERR_SIZE, PAA_ERR_HIP, PAA_ERR_ARG, PAA_ERR_MISSING = range(7)
 
@@ -100,6 +100,9 @@ _SIGS = {
     "paa_model_forward_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "paa_argmax_ids": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "paa_wer_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    "paa_stats_push": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "paa_model_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int]),
     "paa_model_layout": (C.c_int, [C.c_void_p, C.c_int]),
     "paa_gemm": (C.c_int, [C.POINTER(PaaGemmDesc), C.c_void_p]),

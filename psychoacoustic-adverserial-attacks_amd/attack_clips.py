@@ -94,6 +94,20 @@ def _wer(pred, ref):
     return e / max(w, 1)
 
 
+def _device_wers(args, processor, logits, texts):
+    """Per-clip WER of ``logits`` against ``texts`` from the on-device counters (--device_wer): one (B, 3) readback.  None when
+    the device route does not apply (flag off, multi-character vocabulary, a reference over the row cap): host path."""
+    from .training_utils.train import device_wer_canon, log_host_route
+    canon = device_wer_canon(args, processor, None, "attack_clips")
+    if canon is None:
+        return None
+    refs = loss_helpers.encode_refs(texts)
+    if refs is None:
+        log_host_route("attack_clips", f"a reference needs more than {loss_helpers.R_CAP} entries")
+        return None
+    return [e / max(w, 1) for e, w, _ in loss_helpers.wer_counts_device(logits, refs, canon).cpu().tolist()]
+
+
 def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper=None):
     """Attack one batch of clips (x (B, L) on the device) and return (records, delta, adversarial waveforms)."""
     B, L = x.shape
@@ -113,9 +127,16 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
     clean_nll = clip_nll(model, clean_out["logits"], labels).cpu()
     adv_nll = clip_nll(model, adv_out["logits"], labels).cpu()
     refs = loss_helpers.clean_transcripts(texts)
-    clean_pred, _ = loss_helpers.wer_texts(clean_out["logits"], texts, processor)
-    adv_pred, _ = loss_helpers.wer_texts(adv_out["logits"], texts, processor)
     target = loss_helpers.clean_transcripts([" ".join([args.target] * args.target_reps)])[0]
+    targeted = args.attack_mode == "targeted"
+    clean_w, adv_w = _device_wers(args, processor, clean_out["logits"], texts), _device_wers(args, processor, adv_out["logits"], texts)
+    target_w = _device_wers(args, processor, adv_out["logits"], [target] * B) if targeted else None
+    if clean_w is None or adv_w is None or (targeted and target_w is None):
+        clean_pred, _ = loss_helpers.wer_texts(clean_out["logits"], texts, processor)
+        adv_pred, _ = loss_helpers.wer_texts(adv_out["logits"], texts, processor)
+        clean_w = [_wer(clean_pred[b], refs[b].lower()) for b in range(B)]
+        adv_w = [_wer(adv_pred[b], refs[b].lower()) for b in range(B)]
+        target_w = [_wer(adv_pred[b], target.lower()) for b in range(B)] if targeted else None
     l2 = delta.norm(dim=1).cpu()
     linf = delta.abs().amax(dim=1).cpu()
     sig = x.double().pow(2).sum(dim=1).cpu()
@@ -124,11 +145,11 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
     mloss = masking_loss(delta, x, args)[0].cpu() if mask_alpha > 0 else None
     records = []
     for b in range(B):
-        rec = {"index": int(idx[b]), "clean_wer": _wer(clean_pred[b], refs[b].lower()), "adv_wer": _wer(adv_pred[b], refs[b].lower()),
+        rec = {"index": int(idx[b]), "clean_wer": clean_w[b], "adv_wer": adv_w[b],
                "clean_ctc": float(clean_nll[b]), "final_ctc": float(adv_nll[b]), "l2": float(l2[b]), "linf": float(linf[b]),
                "snr_db": float(10.0 * math.log10(float(sig[b]) / float(noise[b]))) if float(noise[b]) > 0 else float("inf")}
-        if args.attack_mode == "targeted":
-            rec[TARGET_FIELD] = _wer(adv_pred[b], target.lower())
+        if targeted:
+            rec[TARGET_FIELD] = target_w[b]
         if mloss is not None:
             rec[MASK_FIELD] = float(mloss[b])
         records.append(rec)

@@ -143,3 +143,105 @@ def decode(logits, processor):
     if processor is not None:
         return processor.batch_decode(pred_ids.long().cpu())
     return greedy_decode_ids(pred_ids.tolist())
+
+
+# ---- on-device WER counters (paa_wer_counts) --------------------------------------------------------
+R_CAP = 1024          # reference entries per clip (code points + one terminator per word): the 450-character labels of the 30 s
+                      # configuration need at most 451
+
+
+def canon_table(processor=None):
+    """canon[V] int32 (CPU) for ``paa_wer_counts``: -1 = drop (special token), 0 = word delimiter, > 0 = the code point of the
+    token's lower-cased character — what ``greedy_decode_ids`` / ``processor.batch_decode(skip_special_tokens=True)`` followed by
+    ``.lower()`` make of each id.  ``processor=None``: the built-in ``VOCAB``.  Returns None when a non-special token is not a
+    single character or its lower-case form is not a single code point (BPE vocabularies, 'İ'), or when lower-casing depends
+    on the neighbours ('Σ'): callers then keep the host path."""
+    if processor is None:
+        vocab, special, delim = {t: i for i, t in enumerate(VOCAB)}, set(range(UNK_ID + 1)), "|"
+    else:
+        tok = getattr(processor, "tokenizer", processor)
+        try:
+            vocab = dict(tok.get_vocab())
+            special = {int(i) for i in tok.all_special_ids}
+            delim = getattr(tok, "word_delimiter_token", None)
+        except Exception:       # noqa: BLE001  (not a tokenizer this table can describe)
+            return None
+    if not vocab or min(vocab.values()) < 0 or max(vocab.values()) > 32766:
+        return None
+    canon = torch.full((max(vocab.values()) + 1,), -1, dtype=torch.int32)
+    for t, i in vocab.items():
+        if t == delim:          # listed among the special tokens by transformers 5, yet decoded to the word boundary
+            canon[i] = 0
+            continue
+        if i in special:
+            continue
+        if len(t) == 1 and t.isspace():
+            canon[i] = 0
+            continue
+        if len(t) != 1 or t == "\u03a3" or len(t.lower()) != 1:
+            return None
+        canon[i] = ord(t.lower())
+    return canon
+
+
+def encode_refs(target_texts, r_cap: int = None):
+    """Pinned int32 (B, r_cap) reference rows of ``paa_wer_counts``: the words of ``clean_transcripts(...).lower().split()`` —
+    the very call ``wer_texts`` + ``wer_counts`` make, so word boundaries agree by construction — as code points, each word
+    terminated by 0, the row padded with -1 (``r_cap`` defaults to ``R_CAP``).  None when a row does not fit."""
+    r_cap = R_CAP if r_cap is None else r_cap
+    rows = []
+    for t in clean_transcripts(target_texts):
+        row = []
+        for w in t.lower().split():
+            row.extend(ord(ch) for ch in w)
+            row.append(0)
+        if len(row) > int(r_cap):
+            return None
+        rows.append(row)
+    out = torch.full((len(rows), int(r_cap)), -1, dtype=torch.int32)
+    for r, row in enumerate(rows):
+        if row:
+            out[r, :len(row)] = torch.tensor(row, dtype=torch.int32)
+    return out.pin_memory() if torch.cuda.is_available() else out
+
+
+def wer_counts_device(logits_or_ids, refs, canon, out=None, sums=None, ids_out=None):
+    """Per-clip (errors, reference words, hypothesis words) as an int32 (B, 3) device tensor, with no host round trip:
+    ``paa_argmax_ids`` (when given (B, T, V) float logits; int16 (B, T) ids are used as they are) then ``paa_wer_counts``.
+    ``refs`` (B, r_cap) int32 and ``canon`` (V) int32 live on the device of the logits (a CPU tensor is copied there).
+    ``out`` / ``sums`` (2 floats: sum of errors, sum of reference words) / ``ids_out`` are caller-owned buffers: with all of them
+    given the call allocates nothing and is graph-capturable."""
+    from .. import _lib, runtime
+    x = logits_or_ids
+    dev = x.device
+    if x.dtype == torch.int16:
+        if x.dim() != 2 or not x.is_cuda or not x.is_contiguous():
+            raise TypeError(f"ids must be a contiguous (B, T) int16 tensor on the GPU, got {tuple(x.shape)} on {x.device}")
+        ids = x
+    else:
+        x = runtime.as_f32_cuda(x, "logits")
+        if x.dim() != 3:
+            raise ValueError(f"logits must be (B, T, V), got {tuple(x.shape)}")
+        ids = ids_out if ids_out is not None else torch.empty(x.shape[:2], dtype=torch.int16, device=dev)
+        if ids.dtype != torch.int16 or ids.numel() != x.shape[0] * x.shape[1] or ids.device != dev:
+            raise ValueError("ids_out must hold B x T int16 on the device of the logits")
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().paa_argmax_ids(_lib.ptr(x), ids.numel(), x.shape[-1], _lib.ptr(ids), _lib.stream_ptr()))
+    B, T = x.shape[0], x.shape[1]
+    refs = refs.to(dev, non_blocking=True)
+    canon = canon.to(dev, non_blocking=True)
+    for name, t in (("refs", refs), ("canon", canon)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous int32 tensor")
+    if refs.dim() != 2 or refs.shape[0] != B:
+        raise ValueError(f"refs must be ({B}, r_cap), got {tuple(refs.shape)}")
+    if out is None:
+        out = torch.empty(B, 3, dtype=torch.int32, device=dev)
+    if out.dtype != torch.int32 or out.numel() != B * 3 or out.device != dev or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (B, 3) int32 tensor on the device of the logits")
+    if sums is not None and (sums.dtype != torch.float32 or sums.numel() != 2 or sums.device != dev or not sums.is_contiguous()):
+        raise ValueError("sums must hold 2 contiguous float32 on the device of the logits")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().paa_wer_counts(_lib.ptr(ids), B, T, _lib.ptr(canon), canon.numel(), _lib.ptr(refs), refs.shape[1],
+                                             _lib.ptr(out), _lib.ptr(sums), _lib.stream_ptr()))
+    return out

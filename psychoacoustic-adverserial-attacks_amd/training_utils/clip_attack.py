@@ -26,7 +26,10 @@ from .pgd import N_STATS, RING, ST_LOSS, ST_MASK_LOSS, PgdStepper, _AdamGraph, a
 class ClipStepper(PgdStepper):
     """The per-clip step: ``step(delta, clean, labels)`` updates ``delta`` (B, L) in place, row b from clip b alone."""
 
-    def __init__(self, model, args, length: int, interp=None, spl_thresh=None, optimizer=None):
+    def __init__(self, model, args, length: int, interp=None, spl_thresh=None, optimizer=None, device_wer=False, canon=None,
+                 r_cap=None, log_cap=4096):
+        """``device_wer`` / ``canon`` / ``r_cap`` / ``log_cap`` as PgdStepper's; ``wer_rows[:B]`` keeps the per-clip (errors,
+        reference words, hypothesis words) of the last step."""
         self.model, self.args, self.L = model, args, int(length)
         self.dev = model.device
         self.norms = str(args.norm_type).split("+")
@@ -65,6 +68,7 @@ class ClipStepper(PgdStepper):
         self._ring_i = 0
         self.mask_rows = torch.zeros(self.max_batch, dtype=torch.float32, device=self.dev)      # l_b of the last step
         self._init_masking_loss()
+        self._init_device_wer(device_wer, canon, r_cap, log_cap)
 
     def _checked(self, delta, clean):
         delta = runtime.as_f32_cuda(delta, "delta")
@@ -88,6 +92,8 @@ class ClipStepper(PgdStepper):
         if self.mask_alpha > 0:
             self._masking_loss(delta, clean, grad, self.mask_rows[:B])
             r["masking_loss"] = self.mask_rows[:B]
+        if self.device_wer:
+            self._wer(r["logits"], B)
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr()
             if self.optimizer is None:
@@ -100,19 +106,25 @@ class ClipStepper(PgdStepper):
                                              _lib.ptr(self.adam_grad), B * L, st))
             for prm in self._prm:
                 _lib.check(lib.paa_project_rows(self.proj.h, prm, _lib.ptr(delta), _lib.ptr(delta), B, _lib.ptr(clean), L, st))
+        if self.device_wer:
+            self.stats_log.push(self.stats)
         r["loss"] = self.stats[ST_LOSS]
         r["grad"] = grad
         return r
 
-    def step(self, delta: torch.Tensor, clean: torch.Tensor, labels: torch.Tensor, want_logits=True, logits_out=None):
-        """In place on ``delta`` (B, L).  Returns dict(loss: 0-d device tensor, the sum over the clips, logits, grad (B, L))."""
+    def step(self, delta: torch.Tensor, clean: torch.Tensor, labels: torch.Tensor, want_logits=True, logits_out=None,
+             refs=None):
+        """In place on ``delta`` (B, L).  Returns dict(loss: 0-d device tensor, the sum over the clips, logits, grad (B, L)).
+        ``refs`` as PgdStepper.step."""
+        if refs is not None:
+            self.set_refs(refs)
         delta, clean = self._checked(delta, clean)
         self._check_p(delta)
         self._pre_step()
         return self._body(delta, clean, labels, want_logits, logits_out)
 
-    def capture(self, delta, clean, labels, logits_out=None):
-        """One step on fixed buffers as ONE hipGraph.  Returns (graph, result dict); ``graph.replay()`` re-runs the step in
+    def capture(self, delta, clean, labels, logits_out=None, refs=None):
+        """One step on fixed buffers as ONE hipGraph (``refs`` as PgdStepper.capture).  Returns (graph, result dict); ``graph.replay()`` re-runs the step in
         place on ``delta`` with whatever ``clean`` / ``labels`` hold.  With Adam the graph is wrapped so that every replay
         first pushes the step's scalars, and the warm-up step is undone (delta, moments and step count as before the call)."""
         delta, clean = self._checked(delta, clean)
@@ -125,11 +137,19 @@ class ClipStepper(PgdStepper):
             saved = (delta.detach().clone(), ast["exp_avg"].clone(), ast["exp_avg_sq"].clone(), ast["step"].clone())
         if logits_out is None:
             logits_out = torch.empty(clean.shape[0], self.model.frames, self.model.arch.vocab_size, device=self.dev)
+        self._captured_buffers = (lab, logits_out)        # the graphs hold raw pointers: keep what capture() itself created alive
+        cur0 = None
+        if self.device_wer:
+            if refs is not None:
+                self.set_refs(refs)
+            cur0 = self.stats_log.cursor.clone()
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(s):                       # warm-up on the side stream, as torch's capture rules require
             self.step(delta, clean, lab, logits_out=logits_out)
         torch.cuda.current_stream(self.dev).wait_stream(s)
+        if cur0 is not None:
+            self.stats_log.cursor.copy_(cur0)
         if saved is not None:
             torch.cuda.synchronize(self.dev)
             delta.detach().copy_(saved[0])

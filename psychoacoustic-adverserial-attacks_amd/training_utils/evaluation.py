@@ -8,11 +8,61 @@ from ..core import loss_helpers
 from .scoring_helpers import Scores
 
 
+def _evaluate_device(args, eval_data_loader, pp, model, processor, canon) -> Scores:
+    """evaluate with the WER counted on the device (--device_wer): forward -> paa_argmax_ids + paa_wer_counts -> one row of
+    [CTC loss, ..., word errors, reference words] appended to a device log; no .item() and no host decode in the loop, ONE
+    readback at the end (and, sharded over ranks, one all-reduce of the rows instead of two).  A batch whose references do not fit
+    the device rows takes the host route for its counters."""
+    from .pgd import N_STATS, ST_LOSS, ST_WER_ERR, ST_WER_REF, StatsLog
+    from .train import log_host_route, wer_of_rows
+    dev = model.device
+    log = StatsLog(dev, 1024, N_STATS)
+    st = torch.zeros(N_STATS, dtype=torch.float32, device=dev)
+    canon = canon.to(dev)
+    chunks, host, n = [], {}, 0
+    for data, target_texts in eval_data_loader:
+        if len(target_texts) == 0:           # an empty shard of a short global batch: a row of zeros for the all-reduce
+            st.zero_()
+        else:
+            data = data.to(args.device, torch.float32).contiguous()
+            labels = loss_helpers.make_labels(target_texts, processor, args, len(data))
+            r = model.forward(data, pp, labels, clamp=False)
+            st[ST_LOSS].copy_(r["loss"])
+            refs = loss_helpers.encode_refs(target_texts)
+            if refs is None:
+                log_host_route("evaluate", f"a reference needs more than {loss_helpers.R_CAP} entries")
+                host[n] = loss_helpers.wer_counts(*loss_helpers.wer_texts(r["logits"], target_texts, processor))
+                st[ST_WER_ERR:ST_WER_REF + 1].zero_()
+            else:
+                loss_helpers.wer_counts_device(r["logits"], refs, canon, sums=st[ST_WER_ERR:ST_WER_REF + 1])
+        log.push(st)
+        n += 1
+        if n % log.cap == 0:
+            chunks.append(log.read())
+    chunks.append(log.read())
+    rows = torch.cat(chunks, dim=0)
+    for i, (e, w) in host.items():
+        rows[i, ST_WER_ERR], rows[i, ST_WER_REF] = float(e), float(w)
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        rows = rows.to(dev, torch.float64)
+        torch.distributed.all_reduce(rows)
+        rows = rows.cpu()
+    ctc_scores, wer_scores = rows[:, ST_LOSS].tolist(), wer_of_rows(rows)
+    avg_ctc = sum(ctc_scores) / len(ctc_scores) if ctc_scores else float("inf")
+    avg_wer = sum(wer_scores) / len(wer_scores) if wer_scores else float("inf")
+    return Scores(ctc=avg_ctc, wer=avg_wer)
+
+
 def evaluate(args, eval_data_loader, p, model, processor, wer_metric, perturbed=False, epoch_number=-1) -> Scores:
     ctc_scores, wer_scores, counts = [], [], []
     pp = None
     if perturbed and isinstance(p, torch.Tensor):
         pp = p.detach().to(model.device, torch.float32).reshape(1, -1).contiguous()
+    if getattr(args, "device_wer", False):
+        from .train import device_wer_canon
+        canon = device_wer_canon(args, processor, wer_metric, "evaluate")
+        if canon is not None:
+            return _evaluate_device(args, eval_data_loader, pp, model, processor, canon)
     for data, target_texts in eval_data_loader:
         if len(target_texts) == 0:           # an empty shard of a short global batch (build.shard_batches): zeros for the all-reduce
             ctc_scores.append(0.0); wer_scores.append(0.0); counts.append((0, 0))

@@ -69,4 +69,7 @@ def create_arg_parser():
     parser.add_argument('--data_dir', type=str, default=None, help='local directory of wav files + transcripts (no download)')
     parser.add_argument('--logs_dir', type=str, default=None, help='root of the run directories (default ./logs)')
     parser.add_argument('--silent', action='store_true')
+    parser.add_argument('--device_wer', action='store_true',
+                        help='count word errors on the device (greedy CTC decode + edit distance) and read the per-step scores back '
+                             'once per epoch; single-character vocabularies without a wer_metric object, else the host path')
     return parser

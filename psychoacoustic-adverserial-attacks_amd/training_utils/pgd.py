@@ -30,6 +30,12 @@ alpha * grad(sum_b l_b) from the gradient BEFORE the all-reduce (the term is add
 writes sum_b l_b of this rank's clips into slot 6 (ST_MASK_LOSS), which the all-reduce sums like the CTC loss.  alpha lives in a
 one-float device tensor (``set_masking_alpha``), so captured graphs follow it.  alpha = 0 launches nothing: the step is the plain
 one, bit for bit, and slot 6 stays 0.
+
+On-device WER (``device_wer=True``): ``paa_argmax_ids`` + ``paa_wer_counts`` run right after the forward pass on a
+fixed ``refs`` buffer (handled like ``labels``) and write THIS step's word errors / reference words into slots 3 and 4, so the
+step's own all-reduce sums them over the ranks and the host ring carries no WER counters; after the update ``paa_stats_push``
+appends the (global) stats to a device log whose cursor advances on the device, so captured graphs append a row per replay and
+an epoch needs ONE readback (``read_log``).  Off by default: the launch sequence is then unchanged.
 """
 from __future__ import annotations
 
@@ -74,6 +80,31 @@ def masking_route(norm_type, world: int) -> None:
                                   "per-clip perturbations (paa_amd.attack_clips)")
 
 
+class StatsLog:
+    """Device log of per-step stats rows: ``push`` is one launch (``paa_stats_push``: row ``cursor % cap`` <- stats, cursor += 1
+    on the device; allocation-free, capturable), ``read`` the one synchronising readback — the rows since the last read, oldest
+    first, as a CPU float32 (n, N_STATS) tensor."""
+
+    def __init__(self, dev, cap: int = 4096, n: int = 8):
+        self.dev, self.cap, self.n = dev, int(cap), int(n)
+        self.log = torch.zeros(self.cap, self.n, dtype=torch.float32, device=dev)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def push(self, stats):
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().paa_stats_push(_lib.ptr(stats), self.n, _lib.ptr(self.log), _lib.ptr(self.cursor), self.cap,
+                                                 _lib.stream_ptr()))
+
+    def read(self, reset: bool = True):
+        n = int(self.cursor.item())
+        if n > self.cap:
+            raise RuntimeError(f"stats log overflow: {n} rows pushed into {self.cap} since the last read")
+        rows = self.log[:n].cpu()
+        if reset:
+            self.cursor.zero_()
+        return rows
+
+
 def adam_scalars(lr, beta1, beta2, step):
     """[-lr / (1 - beta1^t), sqrt(1 - beta2^t)] in double, as torch/optim/adam.py _multi_tensor_adam (capturable=False)
     computes step_size and bias_correction2_sqrt; the foreach kernels round them to f32."""
@@ -84,8 +115,10 @@ def adam_scalars(lr, beta1, beta2, step):
 
 class PgdStepper:
     def __init__(self, model, args, length: int, interp=None, spl_thresh=None, group=None, force_collective=False,
-                 optimizer=None):
-        """``force_collective``: run the packed all-reduce (and the global-statistics projection) even with a single rank —
+                 optimizer=None, device_wer=False, canon=None, r_cap=None, log_cap=4096):
+        """``device_wer``: count this step's word errors on the device and log every step's stats (module docstring); ``canon``
+        is ``loss_helpers.canon_table(processor)`` (default: the built-in vocabulary), ``r_cap`` the width of the ``refs`` rows.
+        ``force_collective``: run the packed all-reduce (and the global-statistics projection) even with a single rank —
         the way the one-GPU test box executes the RCCL branch (tests/test_gpu_rccl.py).  ``optimizer``: a torch.optim.Adam
         over the perturbation (``adam_unsupported`` is None); the step then applies its update instead of the sign step."""
         self.model, self.args, self.L = model, args, int(length)
@@ -134,6 +167,46 @@ class PgdStepper:
         self._ring_ev = [None] * RING
         self._ring_i = 0
         self._init_masking_loss()
+        self._init_device_wer(device_wer, canon, r_cap, log_cap)
+
+    # ---- on-device WER counters and the stats log ----------------------------------------------------------------
+    def _init_device_wer(self, device_wer, canon=None, r_cap=None, log_cap=4096):
+        self.device_wer = bool(device_wer)
+        if not self.device_wer:
+            return
+        from ..core import loss_helpers
+        canon = loss_helpers.canon_table(None) if canon is None else canon
+        self.canon = canon.to(self.dev, torch.int32).contiguous()
+        self.r_cap = int(loss_helpers.R_CAP if r_cap is None else r_cap)
+        nb = int(self.model.max_batch)
+        self.refs = torch.full((nb, self.r_cap), -1, dtype=torch.int32, device=self.dev)
+        self.ids = torch.zeros(nb * int(self.model.frames), dtype=torch.int16, device=self.dev)
+        self.wer_rows = torch.zeros(nb, 3, dtype=torch.int32, device=self.dev)     # (errors, ref words, hyp words) per clip
+        self.wer_batch = 0                                                         # clips of the last step
+        self.stats_log = StatsLog(self.dev, log_cap, N_STATS)
+
+    def set_refs(self, refs):
+        """Stream-ordered copy of the batch's reference rows (``loss_helpers.encode_refs``: (B, r_cap) int32, pinned or on the
+        device) into the fixed buffer the step — eager or captured — reads; call it before ``step`` / ``replay``."""
+        if not self.device_wer:
+            raise RuntimeError("set_refs needs a stepper built with device_wer=True")
+        if refs.dtype != torch.int32 or refs.dim() != 2 or refs.shape[1] != self.r_cap or refs.shape[0] > self.refs.shape[0]:
+            raise ValueError(f"refs must be int32 (B <= {self.refs.shape[0]}, {self.r_cap}), got {refs.dtype} {tuple(refs.shape)}")
+        self.refs[: refs.shape[0]].copy_(refs, non_blocking=True)
+
+    def _wer(self, logits, B):
+        """paa_argmax_ids + paa_wer_counts on the step's logits: per-clip counters -> wer_rows[:B], their sums -> slots 3, 4."""
+        if logits is None:
+            raise ValueError("device_wer needs the step's logits (want_logits=True)")
+        from ..core import loss_helpers
+        self.wer_batch = B
+        loss_helpers.wer_counts_device(logits, self.refs[:B], self.canon, out=self.wer_rows[:B],
+                                       sums=self.stats[ST_WER_ERR:ST_WER_REF + 1], ids_out=self.ids[: B * logits.shape[1]])
+
+    def read_log(self):
+        """The stats rows of the steps since the last call, oldest first: CPU float32 (n, N_STATS), global sums after the
+        collective (slot 0 CTC loss, 3 / 4 word errors / reference words, 6 masking loss).  The one host sync of an epoch."""
+        return self.stats_log.read()
 
     # ---- masking-threshold loss term ---------------------------------------------------------------------------
     def _init_masking_loss(self):
@@ -221,7 +294,7 @@ class PgdStepper:
         if self._ring_ev[k] is not None:
             self._ring_ev[k].synchronize()
         h = self._ring[k]
-        if self.collective:
+        if self.collective and not self.device_wer:
             h[0], h[1] = self._wer_next
             self._wer_next = (0.0, 0.0)
             self.stats[ST_WER_ERR:ST_WER_REF + 1].copy_(h[0:2], non_blocking=True)
@@ -250,6 +323,8 @@ class PgdStepper:
         if self.mask_alpha > 0:
             self._masking_loss(p, clean, self.grad)
             r["masking_loss"] = self.stats[ST_MASK_LOSS]
+        if self.device_wer:
+            self._wer(r["logits"], B)
         if self.need_clean_stats:
             with torch.cuda.device(self.dev):
                 _lib.check(_lib.lib().paa_batch_stats(self.proj.h, _lib.ptr(clean), B, self.L, _lib.ptr(self.stats[ST_SQ:ST_TV + 1]),
@@ -274,9 +349,15 @@ class PgdStepper:
                                                    _lib.ptr(self.stats[ST_CLIPS:ST_CLIPS + 1]), 0.0, L, st))
                 else:
                     _lib.check(lib.paa_project(self.proj.h, prm, _lib.ptr(p), 1, _lib.ptr(clean), B, L, st))
+        if self.device_wer:
+            self.stats_log.push(self.stats)
 
-    def step(self, p: torch.Tensor, clean: torch.Tensor, labels: torch.Tensor, want_logits=True, logits_out=None):
-        """In place on ``p`` (1, L).  Returns dict(loss: 0-d device tensor, summed over ALL ranks, logits)."""
+    def step(self, p: torch.Tensor, clean: torch.Tensor, labels: torch.Tensor, want_logits=True, logits_out=None, refs=None):
+        """In place on ``p`` (1, L).  Returns dict(loss: 0-d device tensor, summed over ALL ranks, logits).  ``refs``
+        (device_wer only): this batch's reference rows, copied to the fixed buffer first (``set_refs``); None keeps what the
+        buffer holds."""
+        if refs is not None:
+            self.set_refs(refs)
         p = runtime.as_f32_cuda(p, "p")
         clean = runtime.as_f32_cuda(clean, "clean_audio")
         if p.numel() != self.L or clean.shape[-1] != self.L:
@@ -304,9 +385,10 @@ class PgdStepper:
         r["loss"] = self.stats[ST_LOSS]
         return r
 
-    def capture(self, p, clean, labels, logits_out=None):
+    def capture(self, p, clean, labels, logits_out=None, refs=None):
         """Capture one step on fixed buffers into hipGraphs (the launch sequence allocates nothing and never
-        synchronises, so it is capturable as is).  Returns (graph, result dict); ``graph.replay()`` re-runs the step
+        synchronises, so it is capturable as is).  With device_wer, ``refs`` fills the fixed reference buffer (refresh it with
+        ``set_refs`` before a replay) and the warm-up step's log row is taken back: the log holds replayed steps only.  Returns (graph, result dict); ``graph.replay()`` re-runs the step
         in place on ``p`` with whatever ``clean`` / ``labels`` currently hold.  With several ranks the halves before
         and after the collective are two graphs and the all-reduce runs between their replays.
 
@@ -322,11 +404,19 @@ class PgdStepper:
             saved = (p.detach().clone(), ast["exp_avg"].clone(), ast["exp_avg_sq"].clone(), ast["step"].clone())
         if logits_out is None:
             logits_out = torch.empty(clean.shape[0], self.model.frames, self.model.arch.vocab_size, device=self.dev)
+        self._captured_buffers = (lab, logits_out)        # the graphs hold raw pointers: keep what capture() itself created alive
+        cur0 = None
+        if self.device_wer:
+            if refs is not None:
+                self.set_refs(refs)
+            cur0 = self.stats_log.cursor.clone()
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(s):                       # warm-up on the side stream, as torch's capture rules require
             self.step(p, clean, lab, logits_out=logits_out)
         torch.cuda.current_stream(self.dev).wait_stream(s)
+        if cur0 is not None:
+            self.stats_log.cursor.copy_(cur0)
         if saved is not None:
             torch.cuda.synchronize(self.dev)
             p.detach().copy_(saved[0])

@@ -44,6 +44,38 @@ def global_wer_per_step(counts, device, group=None):
     return [float(e) / max(float(w), 1.0) for e, w in t.tolist()]
 
 
+_host_route_logged = set()
+
+
+def device_wer_canon(args, processor, wer_metric, where: str):
+    """The canon table when ``where`` (train_epoch / evaluate / attack_clips) may count word errors on the device, else None —
+    the host route, with its reason logged once: the flag is off (silently), a ``wer_metric`` object is given (jiwer applies
+    its own transforms), or the vocabulary is not one character per token (``loss_helpers.canon_table``)."""
+    if not getattr(args, "device_wer", False):
+        return None
+    why, canon = None, None
+    if wer_metric is not None:
+        why = "a wer_metric object is given"
+    else:
+        canon = loss_helpers.canon_table(processor)
+        if canon is None:
+            why = "the vocabulary is not one character per token"
+    if why is not None:
+        log_host_route(where, why)
+    return canon
+
+
+def log_host_route(where: str, why: str):
+    if (where, why) not in _host_route_logged:
+        _host_route_logged.add((where, why))
+        logger.warning("%s: --device_wer falls back to the host WER path: %s", where, why)
+
+
+def wer_of_rows(rows):
+    """Per-step WER of stats-log rows: errors / max(reference words, 1), both small integers held exactly in float32."""
+    return [float(e) / max(float(w), 1.0) for e, w in rows[:, [3, 4]].tolist()]
+
+
 def perturbation_constraint(p: torch.Tensor, clean_audio, args, interp, spl_thresh) -> torch.Tensor:
     """train.py:69-99.  Returns a new tensor; ``p`` is left untouched.  ``args.norm_type`` may be a
     '+'-joined list (extension, applied in the written order)."""
@@ -120,10 +152,16 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
         raise NotImplementedError("masking_loss_alpha > 0 needs the device step: use the defaults of torch.optim.Adam(lr=...) "
                                   "or --optimizer_type pgd")
     mask_scores = []
+    canon = None if eager_adam else device_wer_canon(args, processor, wer_metric, "train_epoch")
+    if eager_adam and getattr(args, "device_wer", False):
+        log_host_route("train_epoch", "the optimizer runs torch's own step")
     stepper = getattr(model, "_stepper", None)
-    if stepper is None or stepper.args is not args or stepper.L != L or stepper.optimizer is not step_opt:
-        stepper = PgdStepper(model, args, L, interp, spl_thresh, optimizer=step_opt)
+    if stepper is None or stepper.args is not args or stepper.L != L or stepper.optimizer is not step_opt \
+            or stepper.device_wer != (canon is not None):
+        stepper = PgdStepper(model, args, L, interp, spl_thresh, optimizer=step_opt, device_wer=canon is not None, canon=canon)
         model._stepper = stepper
+    if canon is not None:
+        return _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alpha)
     for clean_audio, target_texts in train_data_loader:
         t0 = time.perf_counter()
         clean_audio = clean_audio.to(args.device, torch.float32, non_blocking=True).contiguous()   # train.py:129
@@ -157,3 +195,44 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
         wer_scores = global_wer_per_step(wer_counts, stepper.dev, stepper.group)
     return TrainEpochResult(p=p, avg_ctc=_avg(ctc_scores), avg_wer=_avg(wer_scores),
                             avg_masking_loss=_avg(mask_scores) if mask_alpha > 0 else None)
+
+
+def _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alpha) -> TrainEpochResult:
+    """train_epoch with the WER counted on the device (--device_wer): the loop body launches the step and nothing else — no
+    .item(), no id download, no host decode — and the per-step CTC loss, masking loss and word counters come back in ONE
+    readback of the stepper's stats log at the end of the epoch (already global sums with several ranks: they rode the step's
+    all-reduce).  A batch whose references do not fit the device rows (``encode_refs`` is None) takes the host route for its
+    WER, one rank only."""
+    rows, host_wer, n = [], {}, 0
+    stepper.stats_log.cursor.zero_()          # stream-ordered: rows a caller left unread do not count as this epoch's
+    for clean_audio, target_texts in train_data_loader:
+        clean_audio = clean_audio.to(args.device, torch.float32, non_blocking=True).contiguous()   # train.py:129
+        labels = loss_helpers.make_labels(target_texts, processor, args, len(clean_audio))
+        refs = loss_helpers.encode_refs(target_texts, stepper.r_cap)
+        fits = refs is not None
+        if not fits:
+            if stepper.world > 1:
+                raise NotImplementedError(f"--device_wer with several ranks: a reference needs more than {stepper.r_cap} "
+                                          "entries; run without the flag")
+            log_host_route("train_epoch", f"a reference needs more than {stepper.r_cap} entries")
+            refs = loss_helpers.encode_refs([""] * len(target_texts), stepper.r_cap)
+        if args.optimizer_type == "pgd":
+            if isinstance(p, torch.nn.Parameter) or p.requires_grad:
+                p = p.detach()
+            r = stepper.step(p, clean_audio, labels, refs=refs)
+        else:
+            r = stepper.step(p.data, clean_audio, labels, refs=refs)          # p.grad = -grad, as train.py:170 leaves it
+        if not fits:
+            host_wer[n] = loss_helpers.wer_counts(*loss_helpers.wer_texts(r["logits"], target_texts, processor))
+        n += 1
+        if n % stepper.stats_log.cap == 0:
+            rows.append(stepper.read_log())
+    rows.append(stepper.read_log())
+    rows = torch.cat(rows, dim=0)
+    if rows.shape[0] != n:
+        raise RuntimeError(f"the stats log holds {rows.shape[0]} rows after {n} steps")
+    wer_scores = wer_of_rows(rows)
+    for i, (e, w) in host_wer.items():
+        wer_scores[i] = e / max(w, 1)
+    return TrainEpochResult(p=p, avg_ctc=_avg(rows[:, 0].tolist()), avg_wer=_avg(wer_scores),
+                            avg_masking_loss=_avg(rows[:, 6].tolist()) if mask_alpha > 0 else None)
