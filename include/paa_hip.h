@@ -46,7 +46,8 @@ typedef struct {
 } paa_params;
 
 const char* paa_last_error(void);
-/* 330 = this header (320 + paa_wer_counts and paa_stats_push); 331 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
+/* 340 = this header (330 + the row-kernel test entries paa_layernorm_*_planes, paa_softmax_*_mats, paa_ctc_padded and
+ * paa_mul_gelu_grad_planes); 341 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
  * tools/ only).  Bindings refuse other values. */
 int paa_version(void);
 /* sizeof(paa_params), sizeof(paa_arch), sizeof(paa_tensor), sizeof(paa_gemm_desc): layout check for bindings */
@@ -329,6 +330,33 @@ paa_status paa_softmax_bwd(float* dp, const float* p, int rows, int cols, int ld
 paa_status paa_ctc(const float* logits, const int32_t* labels, int B, int T, int V, int S_max, int blank,
                    float grad_scale, float* nll /* B */, float* dlogits /* may be NULL */, float* work, void* stream);
 int64_t paa_ctc_work_floats(int B, int T, int V, int S_max);
+/* The row kernels above with every option the model passes them.  A set of bf16 planes of an f32 result v is given as
+ * (hi, lo, il): hi = bf16(v) round-to-nearest-even, lo = bf16(v - hi) (nullable: hi plane only), both uint16 arrays of the
+ * result's shape; il != 0: ONE array of twice the elements at hi holds both planes interleaved per 32-element group,
+ * [32 hi | 32 lo | 32 hi | ...] (element i at (i / 32) * 64 + i % 32, its lo part 32 further), lo is ignored; rows must then be
+ * multiples of 32 elements (cols % 32 != 0, for paa_mul_gelu_grad_planes n % 32 != 0: PAA_ERR_ARG).  hi null = no planes.
+ * paa_layernorm_fwd_planes: y nullable; yb planes of y; actb planes of gelu(y) and yact its f32 form (nullable each).
+ * paa_layernorm_bwd_planes: dx = LN'(dy) + add (add nullable); dx nullable, and it may alias dy; dxb planes of dx.
+ * cols % 4 != 0: PAA_ERR_ARG (as the entries above). */
+paa_status paa_layernorm_fwd_planes(const float* x, const float* g, const float* b, float* y, float* stats,
+                                    void* yb_hi, void* yb_lo, int yb_il, void* actb_hi, void* actb_lo, int actb_il,
+                                    float* yact, int rows, int cols, float eps, void* stream);
+paa_status paa_layernorm_bwd_planes(const float* dy, const float* x, const float* g, const float* stats, const float* add,
+                                    float* dx, void* dxb_hi, void* dxb_lo, int dxb_il, int rows, int cols, void* stream);
+/* n_mat matrices of rows_per_mat valid rows each, matrix i starting at row i * mat_rows_ld (mat_rows_ld >= rows_per_mat), row
+ * stride ld >= cols.  Columns [cols, ld) of the valid rows are zeroed; the rows between two matrices are not touched. */
+paa_status paa_softmax_fwd_mats(float* s, int n_mat, int rows_per_mat, int mat_rows_ld, int cols, int ld, float scale,
+                                void* stream);
+paa_status paa_softmax_bwd_mats(float* dp, const float* p, int n_mat, int rows_per_mat, int mat_rows_ld, int cols, int ld,
+                                float scale, void* stream);
+/* paa_ctc on logits / dlogits of (B, Tpad, V), Tpad >= T: frames [T, Tpad) of the logits are not read, those of dlogits and of
+ * its planes dlb_hi / dlb_lo (planar, nullable; they need dlogits) are zeroed.  Two calls give the same bits. */
+paa_status paa_ctc_padded(const float* logits, const int32_t* labels, int B, int T, int Tpad, int V, int S_max, int blank,
+                          float grad_scale, float* nll /* B */, float* dlogits, void* dlb_hi, void* dlb_lo, float* work,
+                          void* stream);
+/* out = dy * gelu'(pre) over n elements, gelu'(x) = Phi(x) + x phi(x): f32 out (nullable) and / or planes of it. */
+paa_status paa_mul_gelu_grad_planes(const float* dy, const float* pre, float* out, void* out_hi, void* out_lo, int out_il,
+                                    int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

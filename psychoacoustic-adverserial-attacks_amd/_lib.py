@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PAA_EXTRA_HIPCC_FLAGS (tools/ only: diagnostic builds, see build_ext.py) selects the diagnostic library built next to the shipped one
 LIB_PATH = os.path.join(HERE, "libpaa_hip_exp.so" if os.environ.get("PAA_EXTRA_HIPCC_FLAGS", "").strip() else "libpaa_hip.so")
 
-ABI_VERSIONS = (330, 331)      # include/paa_hip.h paa_version: 331 = the same ABI built with -DPAA_EXPERIMENTS
+ABI_VERSIONS = (340, 341)      # include/paa_hip.h paa_version: 341 = the same ABI built with -DPAA_EXPERIMENTS
 
 PAA_OK, PAA_ERR_BAD_NORM, PAA_ERR_NEED_CLEAN, PAA_ERR_SIZE, PAA_ERR_HIP, PAA_ERR_ARG, PAA_ERR_MISSING = range(7)
 
@@ -122,6 +122,13 @@ _SIGS = {
     "paa_ctc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "paa_ctc_work_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "paa_layernorm_fwd_planes": (C.c_int, [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                                                          C.c_float, C.c_void_p]),
+    "paa_layernorm_bwd_planes": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3 + [C.c_void_p]),
+    "paa_softmax_fwd_mats": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "paa_softmax_bwd_mats": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "paa_ctc_padded": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 6),
+    "paa_mul_gelu_grad_planes": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

@@ -103,6 +103,13 @@ __global__ void k_mul_gelu_grad(const float* __restrict__ dy, const float* __res
     }
 }
 
+// the launch geometry every caller shares: one thread per element up to 4096 workgroups, grid-stride above
+paa_status mul_gelu_grad(const float* dy, const float* pre, float* out, Bf outb, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(k_mul_gelu_grad, dim3(std::min(cdiv(n, 256), 4096)), dim3(256), 0, st, dy, pre, out, outb, n);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
 }  // namespace
 
 struct paa_model {
@@ -529,18 +536,18 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
     float* dx2 = m->dxb;  Bf dx2H = m->dxbH;
     PAA_TRY(linear(m, ro(m->dlogitsH), m->lm_wt, nullptr, dx, NOBF, M, H, V, st));
     if (a.stable_ln)
-        PAA_TRY(layernorm_bwd(dx, m->final_in, m->enc_ln_g, m->enc_stats, nullptr, nullptr, dx, dxH, M, H, st));
+        PAA_TRY(layernorm_bwd(dx, m->final_in, m->enc_ln_g, m->enc_stats, nullptr, dx, dxH, M, H, st));
     for (int l = a.layers - 1; l >= 0; --l) {
         EncL& e = m->enc[l];
         if (!a.stable_ln) {
-            PAA_TRY(layernorm_bwd(dx, e.ln2_in, e.ln2_g, e.st2, nullptr, nullptr, dx, dxH, M, H, st));                  // dr2
+            PAA_TRY(layernorm_bwd(dx, e.ln2_in, e.ln2_g, e.st2, nullptr, dx, dxH, M, H, st));                  // dr2
             PAA_TRY(linear(m, ro(dxH), e.w2_t, nullptr, nullptr, m->dfpreH, M, F, H, st, nullptr, PAA_ACT_GELU_GRAD, nullptr, e.fpre, m->pre16));
             PAA_TRY(linear(m, ro(m->dfpreH), e.w1_t, nullptr, dx2, NOBF, M, H, F, st, dx));                               // dy1 = dr2 + ...
-            PAA_TRY(layernorm_bwd(dx2, e.ln1_in, e.ln1_g, e.st1, nullptr, nullptr, dx2, dx2H, M, H, st));               // dr1
+            PAA_TRY(layernorm_bwd(dx2, e.ln1_in, e.ln1_g, e.st1, nullptr, dx2, dx2H, M, H, st));               // dr1
         } else {   // dx = dr2 with its planes in dxH
             PAA_TRY(linear(m, ro(dxH), e.w2_t, nullptr, nullptr, m->dfpreH, M, F, H, st, nullptr, PAA_ACT_GELU_GRAD, nullptr, e.fpre, m->pre16));
             PAA_TRY(linear(m, ro(m->dfpreH), e.w1_t, nullptr, dx2, NOBF, M, H, F, st));                                   // dn2
-            PAA_TRY(layernorm_bwd(dx2, e.ln2_in, e.ln2_g, e.st2, dx, nullptr, dx2, dx2H, M, H, st));                     // dr1 = dr2 + LN2'
+            PAA_TRY(layernorm_bwd(dx2, e.ln2_in, e.ln2_g, e.st2, dx, dx2, dx2H, M, H, st));                     // dr1 = dr2 + LN2'
         }
         if (m->fused) {
             PAA_TRY(linear(m, ro(dx2H), e.wo_t, nullptr, nullptr, m->dctxH, M, H, H, st));
@@ -587,15 +594,13 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
             PAA_TRY(linear(m, ro(m->dqkvH), e.wqkv_t, nullptr, dx, NOBF, M, H, 3 * H, st, dx2));          // dx = dr1 + dqkv Wqkv
         } else {
             PAA_TRY(linear(m, ro(m->dqkvH), e.wqkv_t, nullptr, dx, NOBF, M, H, 3 * H, st));               // dn1
-            PAA_TRY(layernorm_bwd(dx, e.ln1_in, e.ln1_g, e.st1, dx2, nullptr, dx, dxH, M, H, st));        // dx = dr1 + LN1'
+            PAA_TRY(layernorm_bwd(dx, e.ln1_in, e.ln1_g, e.st1, dx2, dx, dxH, M, H, st));        // dx = dr1 + LN1'
         }
     }
     if (!a.stable_ln)
-        PAA_TRY(layernorm_bwd(dx, m->hsum, m->enc_ln_g, m->enc_stats, nullptr, nullptr, dx, NOBF, M, H, st));   // d hsum
+        PAA_TRY(layernorm_bwd(dx, m->hsum, m->enc_ln_g, m->enc_stats, nullptr, dx, NOBF, M, H, st));   // d hsum
     // ---- positional conv backward: dh0 = dhsum + convT(dhsum * gelu'(pos_pre)) ----
-    hipLaunchKernelGGL(k_mul_gelu_grad, dim3(std::min(cdiv((int64_t)M * H, 256), 4096)), dim3(256), 0, st, (const float*)dx,
-                       (const float*)m->pos_pre, (float*)nullptr, m->dposH, (int64_t)M * H);
-    PAA_LAUNCH_CHECK();
+    PAA_TRY(mul_gelu_grad(dx, m->pos_pre, nullptr, m->dposH, (int64_t)M * H, st));
     {
         const int K = a.pos_k * Hg;
         paa_gemm_desc d = gdb(m, ro(m->dposH), m->pc_wd, m->dh0, m->dh0H, T, Hg, K, H, K, H);
@@ -609,13 +614,11 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
     const ConvL& cl = m->conv[nc - 1];
     PAA_TRY(linear(m, ro(m->dh0H), m->fp_wt, nullptr, m->dfn, NOBF, M, cl.cout, H, st));
     // gradient wrt conv_{last}'s GELU output, then through the GELU -> gradient wrt its norm output
-    PAA_TRY(layernorm_bwd(m->dfn, cl.act_f, m->fp_ln_g, m->fp_stats, nullptr, nullptr, m->gz, NOBF, M, cl.cout, st));
+    PAA_TRY(layernorm_bwd(m->dfn, cl.act_f, m->fp_ln_g, m->fp_stats, nullptr, m->gz, NOBF, M, cl.cout, st));
     {
         const int j = (nc - 1) & 1;
-        hipLaunchKernelGGL(k_mul_gelu_grad, dim3(std::min(cdiv((int64_t)M * cl.cout, 256), 4096)), dim3(256), 0, st,
-                           (const float*)m->gz, (const float*)cl.pre, a.feat_norm_layer ? m->gF[j] : (float*)nullptr,
-                           a.feat_norm_layer ? NOBF : m->gH[j], (int64_t)M * cl.cout);
-        PAA_LAUNCH_CHECK();
+        PAA_TRY(mul_gelu_grad(m->gz, cl.pre, a.feat_norm_layer ? m->gF[j] : nullptr, a.feat_norm_layer ? NOBF : m->gH[j],
+                              (int64_t)M * cl.cout, st));
     }
     // ---- feature encoder backward ----
     for (int i = nc - 1; i >= 1; --i) {
@@ -623,7 +626,7 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
         const ConvL& pr = m->conv[i - 1];
         const int ji = i & 1, jo = (i - 1) & 1;
         if (a.feat_norm_layer)                 // through LayerNorm_i to the raw conv output (f32 in, bf16 planes out)
-            PAA_TRY(layernorm_bwd(m->gF[ji], c.cv, c.g, c.row_stats, nullptr, nullptr, nullptr, m->gH[ji], B * c.P, c.cout, st));
+            PAA_TRY(layernorm_bwd(m->gF[ji], c.cv, c.g, c.row_stats, nullptr, nullptr, m->gH[ji], B * c.P, c.cout, st));
         const bool out_f32 = a.feat_norm_layer != 0;          // next consumer is an element-wise (LayerNorm backward) kernel
         const Bf& gout = i == 1 ? m->g0H : m->gH[jo];         // conv0's kernels read planar planes; the dgrad GEMMs further up interleaved ones
         for (int rho = 0; rho < c.s; ++rho) {
@@ -742,6 +745,16 @@ extern "C" paa_status paa_argmax_ids(const float* d_logits, int64_t rows, int V,
     hipLaunchKernelGGL(k_argmax_ids, dim3(cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, d_logits, rows, V, d_ids);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
+}
+
+// Test entry: out = dy * gelu'(pre) as the backward pass launches it (f32 and / or bf16 planes; il = the planes interleaved
+// per 32-element group in ONE array of 2 n elements at out_hi)
+extern "C" paa_status paa_mul_gelu_grad_planes(const float* dy, const float* pre, float* out, void* out_hi, void* out_lo, int out_il,
+                                               int64_t n, void* stream) {
+    if (!dy || !pre || n < 1) PAA_FAIL(PAA_ERR_ARG, "paa_mul_gelu_grad_planes: null argument or n=%lld", (long long)n);
+    if (out_il && (!out_hi || (n & 31))) PAA_FAIL(PAA_ERR_ARG, "paa_mul_gelu_grad_planes: interleaved planes need n=%lld to be a multiple of 32", (long long)n);
+    return mul_gelu_grad(dy, pre, out, Bf{(unsigned short*)out_hi, out_il ? nullptr : (unsigned short*)out_lo, out_il != 0}, n,
+                         (hipStream_t)stream);
 }
 
 // sizeof of every struct that crosses the ABI, so the host binding can verify its layout.

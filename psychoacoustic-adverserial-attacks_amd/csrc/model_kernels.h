@@ -14,7 +14,7 @@ paa_status layernorm_fwd(const float* x, const float* g, const float* b, float* 
                          float eps, Bf yb, Bf actb, float* yact, hipStream_t st);
 // dx (f32, optional; may alias dy), dxb = bf16 planes of dx (optional)
 paa_status layernorm_bwd(const float* dy, const float* x, const float* g, const float* stats, const float* add,
-                         const float* gelu_pre, float* dx, Bf dxb, int rows, int cols, hipStream_t st);
+                         float* dx, Bf dxb, int rows, int cols, hipStream_t st);
 // n_mat matrices of rows_per_mat valid rows (mat_rows_ld allocated rows each), `cols` valid columns, row stride ld
 paa_status softmax_fwd(float* s, int n_mat, int rows_per_mat, int mat_rows_ld, int cols, int ld, float scale,
                        hipStream_t st);

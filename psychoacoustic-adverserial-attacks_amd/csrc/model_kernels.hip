@@ -73,27 +73,23 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const float* __restrict__ x, con
     for (int c = 1024 + lane * 4; c < cols; c += 256) emit(c, *reinterpret_cast<const float4*>(xr + c));
 }
 
-// dx = rstd * (g*dy - mean(g*dy) - xhat * mean(g*dy*xhat)) [+ add];  if gelu_pre: dy *= gelu'(gelu_pre) first
+// dx = rstd * (g*dy - mean(g*dy) - xhat * mean(g*dy*xhat)) [+ add]
 __global__ __launch_bounds__(256) void k_ln_bwd(const float* __restrict__ dy, const float* __restrict__ x,
                                               const float* __restrict__ g, const float* __restrict__ stats,
-                                              const float* __restrict__ add, const float* __restrict__ gelu_pre,
-                                              float* __restrict__ dx, int rows, int cols, Bf dxb) {
+                                              const float* __restrict__ add, float* __restrict__ dx, int rows, int cols,
+                                              Bf dxb) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
     const size_t o = (size_t)row * cols;
     const float mean = stats[2 * (size_t)row], rstd = stats[2 * (size_t)row + 1];
-    // dy (with the optional gelu' factor applied) and x of the first 1024 columns stay in registers between the two passes
+    // dy and x of the first 1024 columns stay in registers between the two passes
     float dr[4][4], xh[4][4];
     float s1 = 0.f, s2 = 0.f;
-    auto chunk = [&](int c, float (&d)[4], float (&xv)[4]) {          // loads one chunk: d = dy [* gelu'], xv = xhat
+    auto chunk = [&](int c, float (&d)[4], float (&xv)[4]) {          // loads one chunk: d = dy, xv = xhat
         const float4 d4 = *reinterpret_cast<const float4*>(dy + o + c);
         const float4 x4 = *reinterpret_cast<const float4*>(x + o + c);
         d[0] = d4.x; d[1] = d4.y; d[2] = d4.z; d[3] = d4.w;
-        if (gelu_pre) {
-            const float4 p4 = *reinterpret_cast<const float4*>(gelu_pre + o + c);
-            d[0] *= gelu_grad_f(p4.x); d[1] *= gelu_grad_f(p4.y); d[2] *= gelu_grad_f(p4.z); d[3] *= gelu_grad_f(p4.w);
-        }
         xv[0] = (x4.x - mean) * rstd; xv[1] = (x4.y - mean) * rstd; xv[2] = (x4.z - mean) * rstd; xv[3] = (x4.w - mean) * rstd;
     };
     auto sums = [&](int c, const float (&d)[4], const float (&xv)[4]) {
@@ -152,9 +148,9 @@ paa_status layernorm_fwd(const float* x, const float* g, const float* b, float* 
 }
 
 paa_status layernorm_bwd(const float* dy, const float* x, const float* g, const float* stats, const float* add,
-                         const float* gelu_pre, float* dx, Bf dxb, int rows, int cols, hipStream_t st) {
+                         float* dx, Bf dxb, int rows, int cols, hipStream_t st) {
     if (cols & 3) PAA_FAIL(PAA_ERR_ARG, "layernorm backward: cols=%d must be a multiple of 4", cols);
-    hipLaunchKernelGGL(k_ln_bwd, dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, x, g, stats, add, gelu_pre, dx, rows, cols, dxb);
+    hipLaunchKernelGGL(k_ln_bwd, dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, x, g, stats, add, dx, rows, cols, dxb);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }
@@ -1589,13 +1585,60 @@ extern "C" paa_status paa_layernorm_fwd(const float* x, const float* g, const fl
 }
 extern "C" paa_status paa_layernorm_bwd(const float* dy, const float* x, const float* g, const float* stats, float* dx,
                                         int rows, int cols, void* stream) {
-    return layernorm_bwd(dy, x, g, stats, nullptr, nullptr, dx, Bf{nullptr, nullptr}, rows, cols, (hipStream_t)stream);
+    return layernorm_bwd(dy, x, g, stats, nullptr, dx, Bf{nullptr, nullptr}, rows, cols, (hipStream_t)stream);
 }
 extern "C" paa_status paa_softmax_fwd(float* s, int rows, int cols, int ld, float scale, void* stream) {
     return softmax_fwd(s, 1, rows, rows, cols, ld, scale, (hipStream_t)stream);
 }
 extern "C" paa_status paa_softmax_bwd(float* dp, const float* p, int rows, int cols, int ld, float scale, void* stream) {
     return softmax_bwd(dp, p, 1, rows, rows, cols, ld, scale, (hipStream_t)stream);
+}
+// ---- the same kernels with every option the model uses (bf16 planes: hi, lo, il flag; il = both planes interleaved per
+// 32-element group in ONE array of twice the elements at *_hi, *_lo unused) ----
+static bool planes_ok(const char* what, const void* hi, int il, int64_t cols) {
+    if (il && (!hi || (cols & 31))) {
+        char b[160];
+        snprintf(b, sizeof(b), "%s: interleaved planes need a plane pointer and a row length (%lld) that is a multiple of 32", what, (long long)cols);
+        paa::set_error(b);
+        return false;
+    }
+    return true;
+}
+static Bf planes(void* hi, void* lo, int il) { return Bf{(unsigned short*)hi, il ? nullptr : (unsigned short*)lo, il != 0}; }
+
+extern "C" paa_status paa_layernorm_fwd_planes(const float* x, const float* g, const float* b, float* y, float* stats,
+                                               void* yb_hi, void* yb_lo, int yb_il, void* actb_hi, void* actb_lo, int actb_il,
+                                               float* yact, int rows, int cols, float eps, void* stream) {
+    if (cols & 3) PAA_FAIL(PAA_ERR_ARG, "layernorm: cols=%d must be a multiple of 4", cols);
+    if (!planes_ok("paa_layernorm_fwd_planes", yb_hi, yb_il, cols) || !planes_ok("paa_layernorm_fwd_planes", actb_hi, actb_il, cols))
+        return PAA_ERR_ARG;
+    if (!x || !g || !b || rows < 1 || cols < 4) PAA_FAIL(PAA_ERR_ARG, "paa_layernorm_fwd_planes: null argument or empty shape");
+    return layernorm_fwd(x, g, b, y, stats, rows, cols, eps, planes(yb_hi, yb_lo, yb_il), planes(actb_hi, actb_lo, actb_il), yact,
+                         (hipStream_t)stream);
+}
+extern "C" paa_status paa_layernorm_bwd_planes(const float* dy, const float* x, const float* g, const float* stats, const float* add,
+                                               float* dx, void* dxb_hi, void* dxb_lo, int dxb_il, int rows, int cols, void* stream) {
+    if (cols & 3) PAA_FAIL(PAA_ERR_ARG, "layernorm backward: cols=%d must be a multiple of 4", cols);
+    if (!planes_ok("paa_layernorm_bwd_planes", dxb_hi, dxb_il, cols)) return PAA_ERR_ARG;
+    if (!dy || !x || !g || !stats || rows < 1 || cols < 4) PAA_FAIL(PAA_ERR_ARG, "paa_layernorm_bwd_planes: null argument or empty shape");
+    return layernorm_bwd(dy, x, g, stats, add, dx, planes(dxb_hi, dxb_lo, dxb_il), rows, cols, (hipStream_t)stream);
+}
+// n_mat matrices of rows_per_mat valid rows in slots of mat_rows_ld rows; the rows between two matrices are not touched
+static paa_status softmax_mats_ok(const void* p, int n_mat, int rows_per_mat, int mat_rows_ld, int cols, int ld) {
+    if (!p || n_mat < 1 || rows_per_mat < 1 || mat_rows_ld < rows_per_mat || cols < 1 || ld < cols)
+        PAA_FAIL(PAA_ERR_ARG, "softmax: n_mat=%d rows_per_mat=%d mat_rows_ld=%d cols=%d ld=%d", n_mat, rows_per_mat, mat_rows_ld, cols, ld);
+    return PAA_OK;
+}
+extern "C" paa_status paa_softmax_fwd_mats(float* s, int n_mat, int rows_per_mat, int mat_rows_ld, int cols, int ld, float scale,
+                                           void* stream) {
+    PAA_TRY(softmax_mats_ok(s, n_mat, rows_per_mat, mat_rows_ld, cols, ld));
+    return softmax_fwd(s, n_mat, rows_per_mat, mat_rows_ld, cols, ld, scale, (hipStream_t)stream);
+}
+extern "C" paa_status paa_softmax_bwd_mats(float* dp, const float* p, int n_mat, int rows_per_mat, int mat_rows_ld, int cols, int ld,
+                                           float scale, void* stream) {
+    PAA_TRY(softmax_mats_ok(dp, n_mat, rows_per_mat, mat_rows_ld, cols, ld));
+    if (!p) PAA_FAIL(PAA_ERR_ARG, "paa_softmax_bwd_mats: null argument");
+    return softmax_bwd(dp, p, n_mat, rows_per_mat, mat_rows_ld, cols, ld, scale, (hipStream_t)stream);
 }
 extern "C" paa_status paa_test_option(int option, int value) {
     if (option == 0) { paa::set_conv0_two_pass(value != 0); return PAA_OK; }
@@ -1605,4 +1648,13 @@ extern "C" int64_t paa_ctc_work_floats(int B, int T, int V, int S_max) { return 
 extern "C" paa_status paa_ctc(const float* logits, const int32_t* labels, int B, int T, int V, int S_max, int blank,
                               float grad_scale, float* nll, float* dlogits, float* work, void* stream) {
     return ctc(logits, labels, B, T, T, V, S_max, blank, grad_scale, nll, dlogits, Bf{nullptr, nullptr}, work, (hipStream_t)stream);
+}
+// logits / dlogits (B, Tpad, V) with Tpad >= T frames per clip (pad frames: not read; dlogits and planes zeroed); dlb_hi / dlb_lo
+// planar bf16 planes of dlogits (nullable; they need dlogits)
+extern "C" paa_status paa_ctc_padded(const float* logits, const int32_t* labels, int B, int T, int Tpad, int V, int S_max, int blank,
+                                     float grad_scale, float* nll, float* dlogits, void* dlb_hi, void* dlb_lo, float* work,
+                                     void* stream) {
+    if (Tpad < T) PAA_FAIL(PAA_ERR_SIZE, "paa_ctc_padded: Tpad=%d < T=%d", Tpad, T);
+    if ((dlb_hi || dlb_lo) && (!dlogits || !dlb_hi)) PAA_FAIL(PAA_ERR_ARG, "paa_ctc_padded: planes need dlogits and a hi plane");
+    return ctc(logits, labels, B, T, Tpad, V, S_max, blank, grad_scale, nll, dlogits, planes(dlb_hi, dlb_lo, 0), work, (hipStream_t)stream);
 }

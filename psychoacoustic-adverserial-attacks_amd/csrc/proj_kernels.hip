@@ -491,12 +491,12 @@ struct paa_proj {
 };
 
 extern "C" const char* paa_last_error(void) { return paa::g_err.c_str(); }
-// 330 + 1 if the library was built with -DPAA_EXPERIMENTS (diagnostic configurations and environment switches present)
+// 340 + 1 if the library was built with -DPAA_EXPERIMENTS (diagnostic configurations and environment switches present)
 extern "C" int paa_version(void) {
 #ifdef PAA_EXPERIMENTS
-    return 331;
+    return 341;
 #else
-    return 330;
+    return 340;
 #endif
 }
 
