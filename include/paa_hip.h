@@ -46,8 +46,8 @@ typedef struct {
 } paa_params;
 
 const char* paa_last_error(void);
-/* 340 = this header (330 + the row-kernel test entries paa_layernorm_*_planes, paa_softmax_*_mats, paa_ctc_padded and
- * paa_mul_gelu_grad_planes); 341 = the same ABI built with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
+/* 350 = this header (340 + the placement entries paa_place_draw, paa_place_rows and paa_place_reduce); 351 = the same ABI built
+ * with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
  * tools/ only).  Bindings refuse other values. */
 int paa_version(void);
 /* sizeof(paa_params), sizeof(paa_arch), sizeof(paa_tensor), sizeof(paa_gemm_desc): layout check for bindings */
@@ -184,6 +184,32 @@ paa_status paa_project_rows(paa_proj* h, const paa_params* prm, const float* d_s
  * {1, B}; p_rows = 1 is paa_compose_clamp. */
 paa_status paa_compose_clamp_rows(const float* d_clean, const float* d_p, int p_rows, float* d_out, int B, int L,
                                   void* stream);
+
+/* ---- random placement of the universal perturbation (extension) ----------------------------------------------
+ * The perturbation delta has Lp >= 1 samples, the clips L; clip b gets a shift s_b in [0, Lp) and a gain a_b > 0:
+ *   rows[b][i] = a_b * delta[(i + s_b) mod Lp]                          i = 0 .. L-1          (paa_place_rows)
+ *   grad[j]    = sum_b a_b * sum_{i < L, (i + s_b) mod Lp = j} G[b][i]                         (paa_place_reduce, the adjoint)
+ * Lp = L, s = 0, a = 1 is the plain universal step; Lp < L tiles delta (the seam is not smoothed); Lp > L uses a window of it.
+ * G (B, L) is what paa_model_fwd_bwd_rows writes for d_p = rows.  No entry uses atomics: two calls give the same bits.  Null
+ * pointers (except where stated), B < 1, L < 1 or Lp < 1: PAA_ERR_ARG, before any launch.
+ *
+ * paa_place_draw: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) with key
+ * (seed & 0xffffffff, seed >> 32) and counter (step, clip_base + b, stream_id, 0), step = *d_counter read on the device.  With
+ * outputs r0..r3: d_shift[b] = (r0 * Lp) >> 32 (64-bit product; 0 when shift_on = 0); u = (r1 >> 8) * 2^-24,
+ * d_gain[b] = exp2f(fmaf(u, 2 gain_db, -gain_db) * (log2(10) / 20)), exactly 1.0f for gain_db = 0.  Then *d_counter = step + 1 ON
+ * THE DEVICE (one thread, after every draw has read step), so a captured graph draws anew on every replay.  One launch.
+ * gain_db outside [0, 20]: PAA_ERR_ARG.  stream_id: 0 = training, 1 = evaluation (by convention of the callers). */
+paa_status paa_place_draw(uint64_t seed, int32_t* d_counter, int stream_id, int clip_base, int B, int Lp, int shift_on,
+                          float gain_db, int32_t* d_shift, float* d_gain, void* stream);
+/* d_p (Lp) -> d_rows (B, L); the product is one f32 multiply; d_gain NULL = 1.  A shift outside [0, Lp) is reduced modulo Lp on
+ * the device (never an out-of-bounds index).  64-bit element offsets; rows need no alignment. */
+paa_status paa_place_rows(const float* d_p, int Lp, const int32_t* d_shift, const float* d_gain /* nullable */, float* d_rows,
+                          int B, int L, void* stream);
+/* d_grad_rows (B, L) -> d_grad (Lp), WRITTEN, not accumulated.  Every output is owned by one thread; the terms
+ * (double) a_b * (double) G[b][i] (exact in f64) are added in f64, clips ascending and then i ascending, and rounded once to
+ * f32.  An output with no term (Lp > L) is +0.0f. */
+paa_status paa_place_reduce(const float* d_grad_rows, const int32_t* d_shift, const float* d_gain, float* d_grad, int B, int L,
+                            int Lp, void* stream);
 
 /* ------------------------------------------------------------------ model context ---------- */
 /* Wav2Vec2ForCTC forward + CTC loss + backward to the waveform (core/loss_helpers.py:12-23 ->

@@ -491,12 +491,12 @@ struct paa_proj {
 };
 
 extern "C" const char* paa_last_error(void) { return paa::g_err.c_str(); }
-// 340 + 1 if the library was built with -DPAA_EXPERIMENTS (diagnostic configurations and environment switches present)
+// 350 + 1 if the library was built with -DPAA_EXPERIMENTS (diagnostic configurations and environment switches present)
 extern "C" int paa_version(void) {
 #ifdef PAA_EXPERIMENTS
-    return 341;
+    return 351;
 #else
-    return 340;
+    return 350;
 #endif
 }
 

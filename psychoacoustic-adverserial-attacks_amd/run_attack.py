@@ -12,7 +12,7 @@ import sys
 import torch
 
 from .core import iso
-from .training_utils import build, evaluation, parser, pgd, save, scoring_helpers, train
+from .training_utils import build, evaluation, parser, pgd, place, save, scoring_helpers, train
 
 
 def main(args) -> int:
@@ -24,6 +24,7 @@ def main(args) -> int:
     # sharded over ranks; every rank keeps the same p, rank 0 writes the files
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     pgd.masking_route(args.norm_type, world)          # before any collective: every rank raises
+    place.check_flags(args)                           # the same for what placement does not combine with at any length
     if world > 1:
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
         torch.cuda.set_device(local)
@@ -57,6 +58,8 @@ def main(args) -> int:
     hist = {k: [] for k in ("train_ctc", "train_wer", "clean_ctc", "clean_wer", "pert_ctc", "pert_wer")}
     mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
     extra = {}          # results.json keys of the masking-threshold loss term: present only when masking_loss_alpha > 0
+    place_extra = place.results_extra(args, p.shape[-1])          # and those of placement, present only when it is on
+    extra.update(place_extra)
     goal = scoring_helpers.Objective(args.attack_mode)      # targeted: perturbed WER down; untargeted: perturbed CTC up
     best_epoch, no_improve, best_eval = -1, 0, goal.worst
     pert_path = os.path.join(args.save_dir, "perturbation.pt")
@@ -74,7 +77,7 @@ def main(args) -> int:
             logger.info("[%d/%d] train ctc %.4f wer %.4f | eval clean ctc %.4f wer %.4f | eval perturbed ctc %.4f wer %.4f",
                         epoch + 1, args.num_epochs, res.avg_ctc, res.avg_wer, clean.ctc, clean.wer, pert.ctc, pert.wer)
             if mask_alpha > 0:
-                extra = {"masking_loss_alpha": mask_alpha, "train_masking_loss": res.avg_masking_loss}
+                extra = {"masking_loss_alpha": mask_alpha, "train_masking_loss": res.avg_masking_loss, **place_extra}
                 logger.info("[%d/%d] train masking loss %.6g (alpha %g)", epoch + 1, args.num_epochs, res.avg_masking_loss,
                             mask_alpha)
             if writer:

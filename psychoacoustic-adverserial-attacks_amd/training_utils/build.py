@@ -12,6 +12,7 @@ from .. import arch as A
 from .. import synth
 from ..core import iso
 from ..model import PaaModel
+from . import place
 from .train import perturbation_constraint
 
 
@@ -23,7 +24,13 @@ def init_phon_threshold_tensor(args):
 
 def init_perturbation(args, length, spl_thresh, interp, first_batch_data):
     """build.py:288-321.  Fresh init: N(0,1) from the counter-based generator (seed args.seed), then one
-    projection.  Resume: a (1, L) float32 tensor saved with torch.save (loaded with weights_only=True)."""
+    projection.  Resume: a (1, L) float32 tensor saved with torch.save (loaded with weights_only=True).  With placement on
+    (training_utils/place.py) the perturbation has Lp = place.perturbation_length(args, length) samples; the initial
+    projection then sees the first batch only when Lp equals the clip length."""
+    clip_length, length = length, (place.perturbation_length(args, length) if place.placement_on(args) else length)
+    place.check(args, clip_length, length)
+    if length != clip_length:
+        first_batch_data = None
     ckpt = getattr(args, "resume_from", None)
     if ckpt and os.path.isfile(ckpt):
         p = torch.load(ckpt, map_location="cpu", weights_only=True).detach().to(args.device, torch.float32)
@@ -31,6 +38,8 @@ def init_perturbation(args, length, spl_thresh, interp, first_batch_data):
         p = torch.from_numpy(synth.perturbation(length, seed=int(getattr(args, "seed", 5)))).to(args.device)
         p = perturbation_constraint(p=p, clean_audio=first_batch_data, args=args, interp=interp,
                                     spl_thresh=spl_thresh).detach()
+        if length != clip_length and p.shape[-1] != length:           # no clean batch to align to: the iSTFT length hop * (T - 1), zero-padded (_align_to)
+            p = torch.nn.functional.pad(p, (0, length - p.shape[-1]))
     if p.shape[-1] != length:
         raise ValueError(f"Loaded perturbation length {p.shape[-1]} != expected {length}")     # build.py:315
     if args.optimizer_type == "adam":
@@ -111,8 +120,8 @@ def create_logger(args, logs_root=None):
     args.attack_size_string = attack_size_string(args)
     root = logs_root or getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}_{args.attack_mode}_"
-                                 f"{args.optimizer_type}")
+                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}{place.suffix(args)}_"
+                                 f"{args.attack_mode}_{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)
     logger = logging.getLogger("asr_attack")
     logger.setLevel(logging.INFO)

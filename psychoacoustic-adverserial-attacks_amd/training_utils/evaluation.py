@@ -5,7 +5,34 @@ from __future__ import annotations
 import torch
 
 from ..core import loss_helpers
+from . import place
 from .scoring_helpers import Scores
+
+
+class _PlacedEval:
+    """evaluate(perturbed=True) with placement on: every batch sees the perturbation at a drawn placement (Philox stream 1, the
+    step counter restarting at 0 in every evaluate call, so every evaluation sees the same placements and epochs compare)."""
+
+    def __init__(self, args, model, pp):
+        rank = 0
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank = torch.distributed.get_rank()
+        nb, L = int(model.max_batch), int(model.length)
+        seed = getattr(args, "place_seed", None)
+        seed = int(getattr(args, "seed", 5) if seed is None else seed)
+        place.check(args, L, pp.numel())
+        self.pp = pp
+        self.placer = place.Placer(model.device, nb, L, pp.numel(), seed, place.STREAM_EVAL, place.shift_on(args),
+                                   place.gain_db(args), clip_base=rank * nb, with_grad=False)
+
+    def rows(self, B):
+        self.placer.draw(B)
+        return self.placer.place(self.pp, B)
+
+
+def _pert(pp, B):
+    """The perturbation operand of model.forward for a batch of B clips: the (1, L) row, placed rows, or None."""
+    return pp.rows(B) if isinstance(pp, _PlacedEval) else pp
 
 
 def _evaluate_device(args, eval_data_loader, pp, model, processor, canon) -> Scores:
@@ -26,7 +53,7 @@ def _evaluate_device(args, eval_data_loader, pp, model, processor, canon) -> Sco
         else:
             data = data.to(args.device, torch.float32).contiguous()
             labels = loss_helpers.make_labels(target_texts, processor, args, len(data))
-            r = model.forward(data, pp, labels, clamp=False)
+            r = model.forward(data, _pert(pp, len(data)), labels, clamp=False)
             st[ST_LOSS].copy_(r["loss"])
             refs = loss_helpers.encode_refs(target_texts)
             if refs is None:
@@ -58,6 +85,8 @@ def evaluate(args, eval_data_loader, p, model, processor, wer_metric, perturbed=
     pp = None
     if perturbed and isinstance(p, torch.Tensor):
         pp = p.detach().to(model.device, torch.float32).reshape(1, -1).contiguous()
+        if place.placement_on(args):
+            pp = _PlacedEval(args, model, pp)
     if getattr(args, "device_wer", False):
         from .train import device_wer_canon
         canon = device_wer_canon(args, processor, wer_metric, "evaluate")
@@ -69,7 +98,7 @@ def evaluate(args, eval_data_loader, p, model, processor, wer_metric, perturbed=
             continue
         data = data.to(args.device, torch.float32).contiguous()
         labels = loss_helpers.make_labels(target_texts, processor, args, len(data))
-        r = model.forward(data, pp, labels, clamp=False)
+        r = model.forward(data, _pert(pp, len(data)), labels, clamp=False)
         ctc_scores.append(float(r["loss"].item()))
         pred_texts, ref_texts = loss_helpers.wer_texts(r["logits"], target_texts, processor)
         e, w = loss_helpers.wer_counts(pred_texts, ref_texts)

@@ -13,6 +13,13 @@ def _norm_type(v: str) -> str:
     return v
 
 
+def _place_gain_db(v: str) -> float:
+    g = float(v)
+    if not 0.0 <= g <= 20.0:
+        raise argparse.ArgumentTypeError(f"place_gain_db must be in [0, 20], got {v}")
+    return g
+
+
 def create_arg_parser():
     parser = argparse.ArgumentParser()
     # standard training params (parser.py:10-20)
@@ -72,4 +79,12 @@ def create_arg_parser():
     parser.add_argument('--device_wer', action='store_true',
                         help='count word errors on the device (greedy CTC decode + edit distance) and read the per-step scores back '
                              'once per epoch; single-character vocabularies without a wer_metric object, else the host path')
+    # random placement of the universal perturbation (extension); the defaults leave the step as it is
+    parser.add_argument('--perturbation_seconds', type=float, default=None,
+                        help='length of the universal perturbation in seconds (default: the clip length); a shorter one is '
+                             'tiled over the clip, a longer one windowed')
+    parser.add_argument('--place_shift', type=str, choices=["none", "random"], default="none",
+                        help='random: every clip of every step sees the perturbation at a circular shift of its own')
+    parser.add_argument('--place_gain_db', type=_place_gain_db, default=0.0,
+                        help='G in [0, 20]: every clip of every step sees the perturbation at a gain uniform in [-G, +G] dB')
     return parser

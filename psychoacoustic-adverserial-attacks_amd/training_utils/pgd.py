@@ -36,12 +36,20 @@ fixed ``refs`` buffer (handled like ``labels``) and write THIS step's word error
 step's own all-reduce sums them over the ranks and the host ring carries no WER counters; after the update ``paa_stats_push``
 appends the (global) stats to a device log whose cursor advances on the device, so captured graphs append a row per replay and
 an epoch needs ONE readback (``read_log``).  Off by default: the launch sequence is then unchanged.
+
+Random placement (``args.perturbation_seconds`` / ``place_shift`` / ``place_gain_db``, DESIGN.md §6f, training_utils/place.py): the
+perturbation has ``Lp`` samples, the clips ``L``; clip b is composed with a_b * delta[(i + s_b) mod Lp].  The step then runs
+``paa_place_draw`` (skipped after ``set_placement``) -> ``paa_place_rows`` -> the per-clip-row forward / backward on the placed rows
+-> ``paa_place_reduce`` (the adjoint gather-sum) into the packed gradient, which holds Lp + 8 floats; the sign / Adam step and the
+projections run on (1, Lp).  Loss, logits, WER counters and the collective are untouched.  The draw's step counter lives on the
+device, so a captured graph draws anew on every replay.  Placement off: no new launch, buffer or attribute use — the parent's step.
 """
 from __future__ import annotations
 
 import torch
 
 from .. import _lib, runtime
+from . import place
 
 FREQ_NORMS = ("fletcher_munson", "min_max_freqs", "max_phon")
 N_STATS = 8
@@ -115,23 +123,32 @@ def adam_scalars(lr, beta1, beta2, step):
 
 class PgdStepper:
     def __init__(self, model, args, length: int, interp=None, spl_thresh=None, group=None, force_collective=False,
-                 optimizer=None, device_wer=False, canon=None, r_cap=None, log_cap=4096):
+                 optimizer=None, device_wer=False, canon=None, r_cap=None, log_cap=4096, p_length=None):
         """``device_wer``: count this step's word errors on the device and log every step's stats (module docstring); ``canon``
         is ``loss_helpers.canon_table(processor)`` (default: the built-in vocabulary), ``r_cap`` the width of the ``refs`` rows.
         ``force_collective``: run the packed all-reduce (and the global-statistics projection) even with a single rank —
         the way the one-GPU test box executes the RCCL branch (tests/test_gpu_rccl.py).  ``optimizer``: a torch.optim.Adam
-        over the perturbation (``adam_unsupported`` is None); the step then applies its update instead of the sign step."""
+        over the perturbation (``adam_unsupported`` is None); the step then applies its update instead of the sign step.
+        ``length`` is the clip length L.  With placement on (module docstring) the perturbation has ``p_length`` samples (default:
+        ``place.perturbation_length(args, L)``); with placement off it has L."""
         self.model, self.args, self.L = model, args, int(length)
+        self.place_on = place.placement_on(args)
+        self.Lp = self.L
+        if self.place_on:
+            self.Lp = int(p_length) if p_length is not None else place.perturbation_length(args, self.L)
+            place.check(args, self.L, self.Lp)                                   # refusals: before any launch or collective
+        elif p_length is not None and int(p_length) != self.L:
+            raise ValueError(f"p_length {p_length} != clip length {self.L} needs placement on (perturbation_seconds)")
         self.dev = model.device
         self.norms = str(args.norm_type).split("+")
         for n in self.norms:
             if n not in _lib.NORM_IDS:
                 raise ValueError(f"Unknown norm_type: {n!r}")                  # train.py:98
         self.direction = +1 if args.attack_mode == "untargeted" else -1          # train.py:124
-        self.packed = torch.zeros(self.L + N_STATS, dtype=torch.float32, device=self.dev)
-        self.grad = self.packed[: self.L].view(1, self.L)
-        self.stats = self.packed[self.L:]
-        self.proj = runtime.get_proj(args, self.dev, 1, self.L, interp)
+        self.packed = torch.zeros(self.Lp + N_STATS, dtype=torch.float32, device=self.dev)
+        self.grad = self.packed[: self.Lp].view(1, self.Lp)
+        self.stats = self.packed[self.Lp:]
+        self.proj = runtime.get_proj(args, self.dev, 1, self.Lp, interp)
         if spl_thresh is not None:
             self.proj.set_spl_thresh(spl_thresh)
         self.group = group
@@ -156,8 +173,8 @@ class PgdStepper:
             if why is not None:
                 raise NotImplementedError(f"the device Adam step does not implement {why}")
             self.adam_p = optimizer.param_groups[0]["params"][0]
-            if self.adam_p.numel() != self.L:
-                raise ValueError(f"optimizer parameter has {self.adam_p.numel()} elements, expected {self.L}")
+            if self.adam_p.numel() != self.Lp:
+                raise ValueError(f"optimizer parameter has {self.adam_p.numel()} elements, expected {self.Lp}")
             self.adam_scal = torch.zeros(2, dtype=torch.float32, device=self.dev)
             self.adam_grad = torch.zeros_like(self.adam_p, dtype=torch.float32, device=self.dev)
         # host -> device scalars of each step: [wer errors, wer reference words, adam step_size, adam bias_correction2_sqrt].
@@ -168,6 +185,57 @@ class PgdStepper:
         self._ring_i = 0
         self._init_masking_loss()
         self._init_device_wer(device_wer, canon, r_cap, log_cap)
+        if self.place_on:
+            self._init_placement()
+
+    # ---- random placement of the perturbation ----------------------------------------------------------------------
+    def _init_placement(self):
+        rank = 0
+        if self.world > 1:
+            rank = torch.distributed.get_rank(self.group)
+        nb = int(self.model.max_batch)
+        seed = getattr(self.args, "place_seed", None)
+        seed = int(getattr(self.args, "seed", 5) if seed is None else seed)
+        self.placer = place.Placer(self.dev, nb, self.L, self.Lp, seed, place.STREAM_TRAIN, place.shift_on(self.args),
+                                   place.gain_db(self.args), clip_base=rank * nb)
+        self.shift, self.gain, self.counter = self.placer.shift, self.placer.gain, self.placer.counter
+        self.rows, self.grad_rows = self.placer.rows, self.placer.grad_rows
+
+    def _placer(self):
+        if not self.place_on:
+            raise RuntimeError("the stepper was built with placement off (perturbation_seconds / place_shift / place_gain_db)")
+        return self.placer
+
+    def set_placement(self, shift, gain=None):
+        """Explicit per-clip shifts (and gains, default 1) instead of the draw, from the next step on (stream-ordered copy into the
+        fixed buffers); ``set_placement(None)`` returns to drawing.  A captured graph keeps the form it was captured with."""
+        self._placer().set_placement(shift, gain)
+
+    def set_place_step(self, n: int):
+        """Device step counter of the next draw (resume, tests)."""
+        self._placer().set_step(n)
+
+    @property
+    def clip_base(self):
+        """Global id of this rank's first clip in the draw's counter (default rank * model.max_batch); assignable per step.  A
+        captured graph holds the value it was captured with."""
+        return self._placer().clip_base
+
+    @clip_base.setter
+    def clip_base(self, v):
+        self._placer().clip_base = int(v)
+
+    def _placed_fwd_bwd(self, p, clean, labels, want_logits, out):
+        """draw -> rows -> forward / backward with one gradient row per clip -> adjoint gather-sum into self.grad."""
+        B, pl = clean.shape[0], self.placer
+        if not pl.explicit:
+            pl.draw(B)
+        rows = pl.place(p, B)
+        out["grad"] = pl.grad_rows[:B]
+        r = self.model.fwd_bwd(clean, rows, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
+        pl.reduce(B, self.grad)
+        r["grad_rows"], r["grad"] = r["grad"], self.grad
+        return r
 
     # ---- on-device WER counters and the stats log ----------------------------------------------------------------
     def _init_device_wer(self, device_wer, canon=None, r_cap=None, log_cap=4096):
@@ -319,7 +387,10 @@ class PgdStepper:
         out = {"grad": self.grad, "stats": self.stats}
         if logits_out is not None:
             out["logits"] = logits_out
-        r = self.model.fwd_bwd(clean, p, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
+        if self.place_on:
+            r = self._placed_fwd_bwd(p, clean, labels, want_logits, out)
+        else:
+            r = self.model.fwd_bwd(clean, p, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
         if self.mask_alpha > 0:
             self._masking_loss(p, clean, self.grad)
             r["masking_loss"] = self.stats[ST_MASK_LOSS]
@@ -332,7 +403,9 @@ class PgdStepper:
         return r
 
     def _post(self, p, clean):
-        lib, L, B = _lib.lib(), self.L, clean.shape[0]
+        lib, L, B = _lib.lib(), self.Lp, clean.shape[0]
+        if L != self.L:                     # a perturbation of its own length: nothing pairs it with the clean samples
+            clean, B = None, 0
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr()
             if self.optimizer is None:
@@ -360,8 +433,9 @@ class PgdStepper:
             self.set_refs(refs)
         p = runtime.as_f32_cuda(p, "p")
         clean = runtime.as_f32_cuda(clean, "clean_audio")
-        if p.numel() != self.L or clean.shape[-1] != self.L:
-            raise ValueError(f"Loaded perturbation length {p.numel()} / clip length {clean.shape[-1]} != expected {self.L}")
+        if p.numel() != self.Lp or clean.shape[-1] != self.L:
+            raise ValueError(f"Loaded perturbation length {p.numel()} / clip length {clean.shape[-1]} != expected "
+                             f"{self.Lp if self.place_on else self.L}" + (f" / {self.L}" if self.place_on else ""))
         self._check_p(p)
         self._fit_proj(clean.shape[0])
         self._pre_step()
@@ -394,7 +468,15 @@ class PgdStepper:
 
         With Adam the result is always an object with ``replay()`` (the step's scalars are pushed before each replay), betas
         and eps are captured by value (``replay()`` raises ValueError once they change), and the warm-up step is undone:
-        ``p``, the optimizer state and the step count are as before the call."""
+        ``p``, the optimizer state and the step count are as before the call.
+
+        The graphs hold raw pointers into this stepper's buffers (and into ``p``, ``clean`` and the labels): a plain
+        ``torch.cuda.CUDAGraph`` does not keep them alive, so the caller keeps the stepper and those tensors for as long as it
+        replays the graph.  A freed block is handed to later allocations, and labels read as another tensor's bits index the
+        logits out of bounds.
+
+        With placement the draw is inside the graph (the first one of the split form) and the warm-up step's draw is taken back:
+        the device step counter is as before the call, so the first replay draws what the first eager step would have."""
         lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
         self._alpha_captured = self.mask_alpha > 0
         saved = None
@@ -410,6 +492,7 @@ class PgdStepper:
             if refs is not None:
                 self.set_refs(refs)
             cur0 = self.stats_log.cursor.clone()
+        cnt0 = self.counter.clone() if self.place_on else None
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(s):                       # warm-up on the side stream, as torch's capture rules require
@@ -417,6 +500,8 @@ class PgdStepper:
         torch.cuda.current_stream(self.dev).wait_stream(s)
         if cur0 is not None:
             self.stats_log.cursor.copy_(cur0)
+        if cnt0 is not None:
+            self.counter.copy_(cnt0)
         if saved is not None:
             torch.cuda.synchronize(self.dev)
             p.detach().copy_(saved[0])

@@ -1,0 +1,195 @@
+"""Random placement of the universal perturbation: delta has Lp samples, the clips L, and clip b sees
+
+    rows[b][i] = a_b * delta[(i + s_b) mod Lp]            shift s_b in [0, Lp), gain a_b > 0
+
+— a circular shift (Lp = L), a tiling (Lp < L; the seam is not smoothed) or a window (Lp > L) of delta, at a playback level of
+its own.  The gradient of delta is the adjoint, a gather-sum over the per-clip gradient rows.  The three launches
+(``paa_place_draw`` / ``paa_place_rows`` / ``paa_place_reduce``) allocate nothing and the draw's step counter lives on the device,
+so a captured step draws anew on every replay.
+
+Flags (training_utils/parser.py): ``--perturbation_seconds`` (None = the clip length), ``--place_shift {none,random}``,
+``--place_gain_db G`` (gain uniform in [-G, +G] dB).  Placement is ON iff perturbation_seconds is set, place_shift == "random" or
+place_gain_db > 0; OFF leaves every caller exactly as it was.
+"""
+from __future__ import annotations
+
+import logging
+
+import torch
+
+from .. import _lib
+
+logger = logging.getLogger(__name__)
+
+STREAM_TRAIN, STREAM_EVAL = 0, 1
+GAIN_DB_MAX = 20.0
+_FREQ_NORMS = ("fletcher_munson", "min_max_freqs", "max_phon")
+_hop_warned = set()
+
+
+def placement_on(args) -> bool:
+    return (getattr(args, "perturbation_seconds", None) is not None or getattr(args, "place_shift", "none") == "random"
+            or float(getattr(args, "place_gain_db", 0.0)) > 0)
+
+
+def shift_on(args) -> bool:
+    mode = getattr(args, "place_shift", "none")
+    if mode not in ("none", "random"):
+        raise ValueError(f"place_shift must be 'none' or 'random', got {mode!r}")
+    return mode == "random"
+
+
+def gain_db(args) -> float:
+    g = float(getattr(args, "place_gain_db", 0.0))
+    if not 0.0 <= g <= GAIN_DB_MAX:
+        raise ValueError(f"place_gain_db must be in [0, {GAIN_DB_MAX:g}], got {g}")
+    return g
+
+
+def perturbation_length(args, clip_length: int) -> int:
+    """Lp: round(perturbation_seconds * sr), or the clip length when the flag is not set."""
+    s = getattr(args, "perturbation_seconds", None)
+    if s is None:
+        return int(clip_length)
+    lp = int(round(float(s) * int(args.sr)))
+    if lp < 1:
+        raise ValueError(f"perturbation_seconds {s} gives a perturbation of {lp} samples")
+    return lp
+
+
+def check_flags(args) -> None:
+    """The refusals that need no length: flag values outside their ranges, and the masking norm / masking loss.  A no-op with
+    placement off."""
+    if not placement_on(args):
+        return
+    shift_on(args), gain_db(args)
+    norms = str(args.norm_type).split("+")
+    if "masking" in norms or float(getattr(args, "masking_loss_alpha", 0.0)) > 0:
+        raise NotImplementedError("placement (perturbation_seconds / place_shift / place_gain_db) is not implemented with the masking "
+                                  "norm or masking_loss_alpha > 0: both pair the perturbation's frames with the clean clip's frames")
+
+
+def check(args, L: int, Lp: int, eager_adam: bool = False) -> None:
+    """What placement does not combine with, for clips of L and a perturbation of Lp samples; raises before any launch or
+    collective.  A no-op with placement off."""
+    if not placement_on(args):
+        return
+    check_flags(args)
+    norms = str(args.norm_type).split("+")
+    if Lp != L and any(n in ("snr", "tv") for n in norms):
+        raise NotImplementedError(f"the snr / tv norms need a perturbation as long as the clips (Lp = {Lp}, L = {L}): their bound "
+                                  "compares the two sample for sample")
+    if eager_adam:
+        raise NotImplementedError("placement needs the device step: use the defaults of torch.optim.Adam(lr=...) or "
+                                  "--optimizer_type pgd")
+    hop = int(getattr(args, "hop_length", 256))
+    if Lp % hop and any(n in _FREQ_NORMS for n in norms) and (Lp, hop) not in _hop_warned:
+        _hop_warned.add((Lp, hop))
+        logger.warning("perturbation length %d is no multiple of hop_length %d: the frequency-domain projection zeroes its last %d "
+                       "samples every step", Lp, hop, Lp % hop)
+
+
+def refuse_for_clips(args) -> None:
+    """paa_amd.attack_clips: one perturbation row per clip has no placement."""
+    if placement_on(args):
+        raise NotImplementedError("--perturbation_seconds / --place_shift / --place_gain_db apply to the universal perturbation "
+                                  "(paa_amd.run_attack); per-clip perturbations have no placement")
+
+
+def suffix(args) -> str:
+    """Run-directory part of a run with placement: "_place<Lp samples>[s][g<G>]"; empty with placement off, so other runs keep
+    their directory (and resume from it)."""
+    if not placement_on(args):
+        return ""
+    s = getattr(args, "perturbation_seconds", None)
+    out = "_place" + (f"{perturbation_length(args, 0)}" if s is not None else "")
+    if shift_on(args):
+        out += "s"
+    if gain_db(args) > 0:
+        out += f"g{gain_db(args):g}"
+    return out
+
+
+def results_extra(args, Lp: int) -> dict:
+    """results.json keys of a run with placement (none otherwise)."""
+    if not placement_on(args):
+        return {}
+    return {"perturbation_length": int(Lp), "place_shift": str(getattr(args, "place_shift", "none")), "place_gain_db": gain_db(args)}
+
+
+class Placer:
+    """Fixed device buffers and the three launches of one placement site (the training step, or one evaluation).
+    ``draw`` -> shift / gain of the next step's clips (Philox counter (step, clip_base + b, stream_id, 0), step read from and
+    advanced in ``counter`` on the device), ``place`` -> rows[:B], ``reduce`` -> the adjoint of ``place`` on grad_rows[:B]."""
+
+    def __init__(self, dev, max_batch: int, L: int, Lp: int, seed: int, stream_id: int, shift: bool, gain_db_: float,
+                 clip_base: int = 0, with_grad: bool = True):
+        self.dev, self.max_batch, self.L, self.Lp = dev, int(max_batch), int(L), int(Lp)
+        self.seed, self.stream_id = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id)
+        self.shift_on, self.gain_db, self.clip_base = bool(shift), float(gain_db_), int(clip_base)
+        self.shift = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
+        self.gain = torch.ones(self.max_batch, dtype=torch.float32, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rows = torch.zeros(self.max_batch, self.L, dtype=torch.float32, device=dev)
+        self.grad_rows = torch.zeros(self.max_batch, self.L, dtype=torch.float32, device=dev) if with_grad else None
+        self.explicit = False
+
+    def _fits(self, B):
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"batch {B} outside [1, {self.max_batch}]")
+
+    def set_step(self, n: int):
+        """Step counter of the next draw (resume, tests); stream-ordered."""
+        self.counter.fill_(int(n))
+
+    def set_placement(self, shift, gain=None):
+        """Pin explicit shifts (and gains, default 1) for the clips of the following steps by a stream-ordered copy: the draw is
+        skipped until ``set_placement(None)``.  Which of the two a captured graph holds is fixed by ``capture()``."""
+        if shift is None:
+            self.explicit = False
+            return
+        s = torch.as_tensor(shift, dtype=torch.int32).reshape(-1)
+        g = torch.ones(s.numel(), dtype=torch.float32) if gain is None else torch.as_tensor(gain, dtype=torch.float32).reshape(-1)
+        self._fits(s.numel())
+        if g.numel() != s.numel():
+            raise ValueError(f"{s.numel()} shifts but {g.numel()} gains")
+        if not bool((g > 0).all()):
+            raise ValueError("gains must be > 0")
+        self.shift[: s.numel()].copy_(s, non_blocking=True)
+        self.gain[: g.numel()].copy_(g, non_blocking=True)
+        self.explicit = True
+
+    def draw(self, B: int, clip_base=None):
+        self._fits(B)
+        base = self.clip_base if clip_base is None else int(clip_base)
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().paa_place_draw(self.seed, _lib.ptr(self.counter), self.stream_id, base, B, self.Lp,
+                                                 int(self.shift_on), self.gain_db, _lib.ptr(self.shift), _lib.ptr(self.gain),
+                                                 _lib.stream_ptr()))
+
+    def place(self, p, B: int):
+        self._fits(B)
+        if p.numel() != self.Lp:
+            raise ValueError(f"Loaded perturbation length {p.numel()} != expected {self.Lp}")
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().paa_place_rows(_lib.ptr(p), self.Lp, _lib.ptr(self.shift), _lib.ptr(self.gain),
+                                                 _lib.ptr(self.rows), B, self.L, _lib.stream_ptr()))
+        return self.rows[:B]
+
+    def reduce(self, B: int, grad):
+        self._fits(B)
+        if grad.numel() != self.Lp:
+            raise ValueError(f"gradient buffer holds {grad.numel()} floats, expected {self.Lp}")
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().paa_place_reduce(_lib.ptr(self.grad_rows), _lib.ptr(self.shift), _lib.ptr(self.gain),
+                                                   _lib.ptr(grad), B, self.L, self.Lp, _lib.stream_ptr()))
+
+
+def place_rows(p, L: int, shift=None, gain=None, B: int = 1):
+    """rows (B, L) of the perturbation ``p`` (Lp samples, on the GPU) at explicit shifts / gains (default: shift 0, gain 1 — how a
+    saved perturbation is laid over an example clip).  Allocates; for files and tests, not for the step."""
+    p = p.detach().reshape(-1)
+    s = torch.zeros(B, dtype=torch.int32) if shift is None else torch.as_tensor(shift, dtype=torch.int32).reshape(-1)
+    pl = Placer(p.device, s.numel(), L, p.numel(), 0, STREAM_EVAL, False, 0.0, with_grad=False)
+    pl.set_placement(s, gain)
+    return pl.place(p.to(torch.float32).contiguous(), s.numel())

@@ -13,6 +13,7 @@ import torch
 
 from .. import _lib, runtime
 from ..core import loss_helpers
+from . import place
 from .pgd import FREQ_NORMS, PgdStepper, adam_unsupported
 
 logger = logging.getLogger(__name__)
@@ -139,7 +140,8 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
         raise NotImplementedError(f"Optimization type not implemented: {args.optimizer_type!r}")   # train.py:177
     if args.optimizer_type == "adam" and optimizer is None:
         raise ValueError("Adam optimizer selected but optimizer is None")                          # train.py:167
-    L = p.shape[-1]
+    Lp = p.shape[-1]
+    L = int(model.length) if place.placement_on(args) else Lp          # placement: p has a length of its own (place.py)
     world = 1
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         world = torch.distributed.get_world_size()
@@ -151,15 +153,19 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
     if eager_adam and mask_alpha > 0:
         raise NotImplementedError("masking_loss_alpha > 0 needs the device step: use the defaults of torch.optim.Adam(lr=...) "
                                   "or --optimizer_type pgd")
+    place.check(args, L, Lp, eager_adam)
     mask_scores = []
     canon = None if eager_adam else device_wer_canon(args, processor, wer_metric, "train_epoch")
     if eager_adam and getattr(args, "device_wer", False):
         log_host_route("train_epoch", "the optimizer runs torch's own step")
     stepper = getattr(model, "_stepper", None)
-    if stepper is None or stepper.args is not args or stepper.L != L or stepper.optimizer is not step_opt \
+    if stepper is None or stepper.args is not args or stepper.L != L or stepper.Lp != Lp or stepper.optimizer is not step_opt \
             or stepper.device_wer != (canon is not None):
-        stepper = PgdStepper(model, args, L, interp, spl_thresh, optimizer=step_opt, device_wer=canon is not None, canon=canon)
+        stepper = PgdStepper(model, args, L, interp, spl_thresh, optimizer=step_opt, device_wer=canon is not None, canon=canon,
+                             p_length=Lp)
         model._stepper = stepper
+        if stepper.place_on:          # a resumed run goes on drawing where the epochs before it stopped, not from step 0 again
+            stepper.set_place_step(int(epoch) * len(train_data_loader))
     if canon is not None:
         return _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alpha)
     for clean_audio, target_texts in train_data_loader:
