@@ -46,11 +46,9 @@ def masking_loss(delta: torch.Tensor, clean: torch.Tensor, args, grad: bool = Fa
     pr = runtime.get_proj(args, x.device, B, L)
     rows = torch.empty(B, dtype=torch.float32, device=x.device)
     g = torch.zeros_like(d2) if grad else None
-    a = type("A", (), dict(vars(args)))()
-    a.norm_type = "masking"
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().paa_masking_loss(pr.h, runtime.params_of(a), _lib.ptr(d2), d2.shape[0], _lib.ptr(x), B, L, None,
-                                               _lib.ptr(g), _lib.ptr(rows), None, None, _lib.stream_ptr()))
+        _lib.check(_lib.lib().paa_masking_loss(pr.h, runtime.params_of(args, "masking"), _lib.ptr(d2), d2.shape[0], _lib.ptr(x), B, L,
+                                               None, _lib.ptr(g), _lib.ptr(rows), None, None, _lib.stream_ptr()))
     if g is not None:
         g = g.neg_().view_as(d)
     return rows, g

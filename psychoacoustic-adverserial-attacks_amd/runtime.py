@@ -85,9 +85,10 @@ def get_proj(args, device, rows: int, length: int, interp=None) -> Proj:
     return pr
 
 
-def params_of(args) -> _lib.PaaParams:
-    """argparse namespace (training_utils/parser.py) -> paa_params."""
-    nt = getattr(args, "norm_type", None)
+def params_of(args, norm_type=None) -> _lib.PaaParams:
+    """argparse namespace (training_utils/parser.py) -> paa_params.  ``norm_type``: this one norm instead of ``args.norm_type``
+    (one of the norms of a '+'-joined list, or the masking norm for the masking loss)."""
+    nt = getattr(args, "norm_type", None) if norm_type is None else norm_type
     if nt not in _lib.NORM_IDS:
         raise ValueError(f"Unknown norm_type: {nt!r}")          # train.py:98
     g = lambda k, d: float(getattr(args, k, d))

@@ -1,50 +1,53 @@
-"""The PGD inner step as one launch sequence on the device (SURVEY §8a S1-S6 + P0):
+"""The PGD inner step as one launch sequence on the device (SURVEY §8a S1-S6 + P0).  ``_StepperCore`` holds what the universal step
+(``PgdStepper``, here) and the per-clip step (``clip_attack.ClipStepper``) share; a mode adds launches to the plain sequence:
 
-    forward + CTC + backward-to-waveform  ->  [all-reduce SUM over ranks]  ->  p += lr*sign(grad)  ->  projection
+    mode (switched on by)                      launches                                                  where
+    -----------------------------------------  --------------------------------------------------------  --------------------------------
+    plain universal step                       paa_model_fwd_bwd, paa_sign_step, paa_project per norm     (forward + CTC + backward to the
+                                                                                                          waveform, update, projections)
+    per-clip step (ClipStepper)                paa_model_fwd_bwd_rows, paa_sign_step over B*L,            the whole sequence; no collective
+                                               paa_project_rows per norm
+    Adam (``optimizer=``)                      paa_adam_step                                              in place of paa_sign_step
+    masking loss (``masking_loss_alpha`` > 0)  paa_masking_loss                                           right after the backward pass
+    device WER (``device_wer=True``)           paa_argmax_ids, paa_wer_counts                             after the masking loss
+                                               paa_stats_push                                             after the last projection
+    collective (several ranks, or              paa_batch_stats (snr / tv only)                            last before the all-reduce
+    ``force_collective``; universal only)      all_reduce(packed, SUM)                                    between backward and update
+                                               paa_project_ext                                            in place of paa_project (snr / tv)
+    placement (``perturbation_seconds`` /      paa_place_draw (not after ``set_placement``),              before the forward pass
+    ``place_shift`` / ``place_gain_db``;       paa_place_rows
+    universal only)                            paa_model_fwd_bwd_rows                                     in place of paa_model_fwd_bwd
+                                               paa_place_reduce                                           right after the backward pass
 
-Data-parallel form: every rank holds the full universal perturbation and a shard of the
-utterances; because HF's CTC reduction is 'sum', the global gradient is the sum of the shard
-gradients, so ONE all-reduce (RCCL over xGMI via torch.distributed's "nccl" backend) per step of the packed
-f32 vector
+A mode that is off adds no launch: alpha = 0, ``device_wer=False`` and placement off are the plain step, bit for bit.
 
-    [ grad (L) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, masking loss, 0 ]
+The packed vector is ``[ grad (Lp) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, masking loss, 0 ]`` in
+float32; the 8 stat slots are defined HERE (ST_*) and documented in include/paa_hip.h (paa_model_fwd_bwd, d_stats).  Every rank
+holds the full universal perturbation and a shard of the utterances; HF's CTC reduction is 'sum', so the global gradient is the sum
+of the shard gradients and ONE all-reduce of the packed vector per step (RCCL over xGMI via torch.distributed's "nccl" backend)
+suffices: every rank then applies the identical update and projection, and the replicas stay bit-identical without a broadcast.
+Slots 1, 2 and 5 are there because project_snr / project_tv use whole-GLOBAL-batch statistics (projections.py:11-35, 56-66) and
+the SNR target norm the global ``clean.numel()``: ``paa_batch_stats`` writes this rank's sums and clip count, the all-reduce adds
+them (the count is a small integer, exact in f32) and ``paa_project_ext`` reads the sums on the device, so ranks may hold different
+numbers of clips, in any step.  Slots 3 and 4 carry the word errors / reference words: of the PREVIOUS step, counted on the host
+(train.py:149-153 runs one step behind the GPU; ``set_wer_counts``), or of THIS step with ``device_wer``, counted on a
+fixed ``refs`` buffer that is handled like ``labels``; ``paa_stats_push`` then appends the global stats to a device log whose cursor
+advances on the device, so a captured graph appends a row per replay and an epoch needs ONE readback (``read_log``).  Slot 6 is
+sum_b l_b of the masking loss: the step optimises direction * CTC(x + delta) - alpha * sum_b l_b(delta), and
+``paa_masking_loss`` subtracts alpha * grad(sum_b l_b) from the gradient BEFORE the all-reduce (the term is additive over clips).
 
-suffices; every rank then applies the identical sign step and projection, so replicas stay bit-identical
-without a broadcast.  ``sum clean^2`` / ``TV(clean)`` are there because project_snr / project_tv use
-whole-GLOBAL-batch statistics (projections.py:11-35, 56-66); the SNR target norm also uses the global
-``clean.numel()`` = ``L * sum of the ranks' batch sizes``: every rank writes its own clip count into slot 5 each step
-(``paa_batch_stats``), the all-reduce sums it (a small integer, exact in f32) and ``paa_project_ext`` reads the sum on the
-device — so ranks may hold different numbers of clips, in any step, without a collective of their own.  The WER counters
-are the host-side bookkeeping of the PREVIOUS step (train.py:149-153 runs one step behind the GPU), reduced with the same
-buffer.  The layout of the 8 slots is defined HERE (ST_*) and documented in include/paa_hip.h (paa_model_fwd_bwd, d_stats).
+Host -> device scalars of a step travel through a ring of pinned slots (``_HostRing``) by asynchronous copies, so captured graphs
+follow them on replay: the host's WER counters, Adam's (-lr / (1 - beta1^t), sqrt(1 - beta2^t)) — computed as torch does, with the
+moments and the step count kept in ``optimizer.state[p]`` (build.py:352-359, train.py:165-175), so ``optimizer.state_dict()`` and a
+later plain ``optimizer.step()`` see the steps taken here, and a StepLR lr is picked up — and alpha (``set_masking_alpha``).
 
-Second update rule (``optimizer=``): torch.optim.Adam as build.py:352-359 creates it (train.py:165-175).  Only the first launch
-after the collective changes (``paa_adam_step`` instead of ``paa_sign_step``); the moments and the step count stay in
-``optimizer.state[p]``, so ``optimizer.state_dict()`` and a later plain ``optimizer.step()`` see the steps taken here.  The
-per-step scalars (-lr / (1 - beta1^t), sqrt(1 - beta2^t)) are computed on the host as torch does and reach the device
-through the same pinned ring as the WER counters, so a captured graph picks up the step count and a StepLR lr on replay.
-
-Masking-threshold loss term (``args.masking_loss_alpha`` = alpha > 0): the step optimises
-direction * CTC(x + delta) - alpha * sum_b l_b(delta).  ``paa_masking_loss`` runs right after the backward pass and subtracts
-alpha * grad(sum_b l_b) from the gradient BEFORE the all-reduce (the term is additive over clips, so the SUM carries it), and
-writes sum_b l_b of this rank's clips into slot 6 (ST_MASK_LOSS), which the all-reduce sums like the CTC loss.  alpha lives in a
-one-float device tensor (``set_masking_alpha``), so captured graphs follow it.  alpha = 0 launches nothing: the step is the plain
-one, bit for bit, and slot 6 stays 0.
-
-On-device WER (``device_wer=True``): ``paa_argmax_ids`` + ``paa_wer_counts`` run right after the forward pass on a
-fixed ``refs`` buffer (handled like ``labels``) and write THIS step's word errors / reference words into slots 3 and 4, so the
-step's own all-reduce sums them over the ranks and the host ring carries no WER counters; after the update ``paa_stats_push``
-appends the (global) stats to a device log whose cursor advances on the device, so captured graphs append a row per replay and
-an epoch needs ONE readback (``read_log``).  Off by default: the launch sequence is then unchanged.
-
-Random placement (``args.perturbation_seconds`` / ``place_shift`` / ``place_gain_db``, DESIGN.md §6f, training_utils/place.py): the
-perturbation has ``Lp`` samples, the clips ``L``; clip b is composed with a_b * delta[(i + s_b) mod Lp].  The step then runs
-``paa_place_draw`` (skipped after ``set_placement``) -> ``paa_place_rows`` -> the per-clip-row forward / backward on the placed rows
--> ``paa_place_reduce`` (the adjoint gather-sum) into the packed gradient, which holds Lp + 8 floats; the sign / Adam step and the
-projections run on (1, Lp).  Loss, logits, WER counters and the collective are untouched.  The draw's step counter lives on the
-device, so a captured graph draws anew on every replay.  Placement off: no new launch, buffer or attribute use — the parent's step.
+Placement (training_utils/place.py): the perturbation has ``Lp`` samples, the clips ``L``; clip b is composed with
+a_b * delta[(i + s_b) mod Lp] and ``paa_place_reduce`` is the adjoint gather-sum into the packed gradient; the update and the
+projections run on (1, Lp).  The draw's step counter lives on the device, so a captured graph draws anew on every replay.
 """
 from __future__ import annotations
+
+import contextlib
 
 import torch
 
@@ -93,7 +96,7 @@ class StatsLog:
     on the device; allocation-free, capturable), ``read`` the one synchronising readback — the rows since the last read, oldest
     first, as a CPU float32 (n, N_STATS) tensor."""
 
-    def __init__(self, dev, cap: int = 4096, n: int = 8):
+    def __init__(self, dev, cap: int = 4096, n: int = N_STATS):
         self.dev, self.cap, self.n = dev, int(cap), int(n)
         self.log = torch.zeros(self.cap, self.n, dtype=torch.float32, device=dev)
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -121,7 +124,246 @@ def adam_scalars(lr, beta1, beta2, step):
     return (lr / bc1) * -1, bc2 ** 0.5
 
 
-class PgdStepper:
+class _HostRing:
+    """RING pinned slots of ``n`` floats for the host -> device scalars of a step.  The copies out of a slot are asynchronous, so
+    the slot is rewritten only after the event behind its copies has completed."""
+
+    def __init__(self, n: int, dev):
+        self.dev = dev
+        self.slots = [torch.zeros(n, dtype=torch.float32).pin_memory() for _ in range(RING)]
+        self.events = [None] * RING
+        self.i = 0
+
+    @contextlib.contextmanager
+    def slot(self):
+        """``with ring.slot() as h``: the next slot, free to write; the block fills it and issues its ``copy_(h[...],
+        non_blocking=True)`` on the current stream, whose position is recorded behind them."""
+        k = self.i % RING
+        self.i += 1
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        yield self.slots[k]
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        self.events[k] = ev
+
+
+class _StepperCore:
+    """What the universal and the per-clip step share: the norms and their params, the projection context, the adopted Adam, the
+    host scalars of a step, the masking-loss term, the device WER counters with the stats log, the update launch and the
+    warm-up of ``capture()``.  A leaf allocates ``grad`` / ``stats``, checks its shapes, and orders the launches in ``_body``."""
+    collective = False                  # PgdStepper alone runs the packed all-reduce ...
+    _wer_next = (0.0, 0.0)              # ... and carries the host's WER counters behind its gradient
+
+    def __init__(self, model, args, length, interp, spl_thresh, optimizer, device_wer, canon, r_cap, log_cap, proj_rows, proj_len):
+        self.model, self.args, self.L = model, args, int(length)
+        self.dev = model.device
+        self.norms = str(args.norm_type).split("+")
+        for n in self.norms:
+            if n not in _lib.NORM_IDS:
+                raise ValueError(f"Unknown norm_type: {n!r}")                  # train.py:98
+        self.direction = +1 if args.attack_mode == "untargeted" else -1          # train.py:124
+        self._prm = [runtime.params_of(args, n) for n in self.norms]
+        self.proj = runtime.get_proj(args, self.dev, proj_rows, proj_len, interp)
+        if spl_thresh is not None:
+            self.proj.set_spl_thresh(spl_thresh)
+        self.optimizer = optimizer
+        if optimizer is not None:
+            why = adam_unsupported(optimizer)
+            if why is not None:
+                raise NotImplementedError(f"the device Adam step does not implement {why}")
+            self.adam_p = optimizer.param_groups[0]["params"][0]
+            self._check_adam_shape()
+            self.adam_scal = torch.zeros(2, dtype=torch.float32, device=self.dev)
+            self.adam_grad = torch.zeros_like(self.adam_p, dtype=torch.float32, device=self.dev)
+        # one slot per step: [wer errors, wer reference words, adam step_size, adam bias_correction2_sqrt]
+        self._ring = _HostRing(4, self.dev) if (self.collective or optimizer is not None) else None
+        self._init_masking_loss()
+        self._init_device_wer(device_wer, canon, r_cap, log_cap)
+
+    # ---- on-device WER counters and the stats log ----------------------------------------------------------------
+    def _init_device_wer(self, device_wer, canon=None, r_cap=None, log_cap=4096):
+        self.device_wer = bool(device_wer)
+        if not self.device_wer:
+            return
+        from ..core import loss_helpers
+        canon = loss_helpers.canon_table(None) if canon is None else canon
+        self.canon = canon.to(self.dev, torch.int32).contiguous()
+        self.r_cap = int(loss_helpers.R_CAP if r_cap is None else r_cap)
+        nb = int(self.model.max_batch)
+        self.refs = torch.full((nb, self.r_cap), -1, dtype=torch.int32, device=self.dev)
+        self.ids = torch.zeros(nb * int(self.model.frames), dtype=torch.int16, device=self.dev)
+        self.wer_rows = torch.zeros(nb, 3, dtype=torch.int32, device=self.dev)     # (errors, ref words, hyp words) per clip
+        self.wer_batch = 0                                                         # clips of the last step
+        self.stats_log = StatsLog(self.dev, log_cap, N_STATS)
+
+    def set_refs(self, refs):
+        """Stream-ordered copy of the batch's reference rows (``loss_helpers.encode_refs``: (B, r_cap) int32, pinned or on the
+        device) into the fixed buffer the step — eager or captured — reads; call it before ``step`` / ``replay``."""
+        if not self.device_wer:
+            raise RuntimeError("set_refs needs a stepper built with device_wer=True")
+        if refs.dtype != torch.int32 or refs.dim() != 2 or refs.shape[1] != self.r_cap or refs.shape[0] > self.refs.shape[0]:
+            raise ValueError(f"refs must be int32 (B <= {self.refs.shape[0]}, {self.r_cap}), got {refs.dtype} {tuple(refs.shape)}")
+        self.refs[: refs.shape[0]].copy_(refs, non_blocking=True)
+
+    def _wer(self, logits, B):
+        """paa_argmax_ids + paa_wer_counts on the step's logits: per-clip counters -> wer_rows[:B], their sums -> slots 3, 4."""
+        if logits is None:
+            raise ValueError("device_wer needs the step's logits (want_logits=True)")
+        from ..core import loss_helpers
+        self.wer_batch = B
+        loss_helpers.wer_counts_device(logits, self.refs[:B], self.canon, out=self.wer_rows[:B],
+                                       sums=self.stats[ST_WER_ERR:ST_WER_REF + 1], ids_out=self.ids[: B * logits.shape[1]])
+
+    def read_log(self):
+        """The stats rows of the steps since the last call, oldest first: CPU float32 (n, N_STATS), global sums after the
+        collective (slot 0 CTC loss, 3 / 4 word errors / reference words, 6 masking loss).  The one host sync of an epoch."""
+        return self.stats_log.read()
+
+    # ---- masking-threshold loss term ---------------------------------------------------------------------------
+    def _init_masking_loss(self):
+        self.mask_alpha = 0.0
+        self.alpha_dev = None
+        self._alpha_captured = None          # capture() records whether the captured launch sequence holds the term
+        self._mask_prm = runtime.params_of(self.args, "masking")          # paa_masking_loss reads masking_margin_db only
+        alpha = float(getattr(self.args, "masking_loss_alpha", 0.0))
+        if alpha < 0:
+            raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
+        if alpha > 0:
+            self.set_masking_alpha(alpha)
+
+    def set_masking_alpha(self, alpha: float):
+        """Weight of the masking-threshold loss term from the next step on.  The value goes to a one-float device tensor by a
+        stream-ordered copy from pinned memory, so eager steps and captured graphs alike follow it without recapture.  Whether
+        the term is in the launch sequence at all (alpha > 0) is fixed by ``capture()``: switching it on or off afterwards
+        raises."""
+        alpha = float(alpha)
+        if alpha < 0:
+            raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
+        if self._alpha_captured is not None and (alpha > 0) != self._alpha_captured:
+            raise ValueError("masking_loss_alpha cannot switch between 0 and > 0 after capture(): the captured launch sequence "
+                             f"{'holds' if self._alpha_captured else 'does not hold'} the loss term; capture the step again")
+        if alpha > 0:
+            if self.alpha_dev is None:
+                self.alpha_dev = torch.zeros(1, dtype=torch.float32, device=self.dev)
+                self._alpha_ring = _HostRing(1, self.dev)
+            with torch.cuda.device(self.dev), self._alpha_ring.slot() as h:
+                h[0] = alpha
+                self.alpha_dev.copy_(h, non_blocking=True)
+        elif self.mask_alpha > 0:
+            self.stats[ST_MASK_LOSS] = 0.0
+        self.mask_alpha = alpha
+
+    def _masking_loss(self, p, clean, grad, loss_rows=None):
+        """grad -= alpha * grad(sum_b l_b); sum_b l_b -> slot 6.  p (rows, L), rows in {1, B}."""
+        B = clean.shape[0]
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().paa_masking_loss(self.proj.h, self._mask_prm, _lib.ptr(p), p.shape[0] if p.dim() == 2 else 1,
+                                                   _lib.ptr(clean), B, self.L, _lib.ptr(self.alpha_dev), _lib.ptr(grad),
+                                                   _lib.ptr(loss_rows), _lib.ptr(self.stats[ST_MASK_LOSS:ST_MASK_LOSS + 1]), None,
+                                                   _lib.stream_ptr()))
+
+    # ---- the update -------------------------------------------------------------------------------------------------
+    def adam_consts(self):
+        """(w1, beta2, omb2, eps) of the optimizer's param group as the foreach kernels see them (f32 by value)."""
+        g = self.optimizer.param_groups[0]
+        b1, b2 = g["betas"]
+        return float(1 - b1), float(b2), float(1 - b2), float(g["eps"])
+
+    def _adam_state(self):
+        """optimizer.state[p], created as torch's Adam._init_group does on its first step (non-capturable, non-fused)."""
+        st = self.optimizer.state[self.adam_p]
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0, dtype=torch.float32)
+            st["exp_avg"] = torch.zeros_like(self.adam_p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(self.adam_p, memory_format=torch.preserve_format)
+        return st
+
+    def _check_p(self, p):
+        if self.optimizer is not None and p.data_ptr() != self.adam_p.data_ptr():
+            raise ValueError("the Adam step updates the optimizer's own parameter; pass that tensor as p")
+
+    def _pre_step(self, consts=None):
+        """Host side of one step, before its launches (eager step, single-graph replay and _SplitGraph.replay alike): this
+        rank's WER counters of the previous step go behind the gradient, and for Adam the step count is advanced and the
+        step's scalars go to ``adam_scal``.  ``consts``: the (w1, beta2, omb2, eps) a graph captured by value."""
+        if self._ring is None:
+            return
+        with self._ring.slot() as h:
+            if self.collective and not self.device_wer:
+                h[0], h[1] = self._wer_next
+                self._wer_next = (0.0, 0.0)
+                self.stats[ST_WER_ERR:ST_WER_REF + 1].copy_(h[0:2], non_blocking=True)
+            if self.optimizer is not None:
+                if consts is not None and self.adam_consts() != consts:
+                    raise ValueError("Adam betas / eps changed after capture(); capture the step again")
+                g = self.optimizer.param_groups[0]
+                st = self._adam_state()
+                if self.adam_p.grad is not self.adam_grad:
+                    self.adam_p.grad = self.adam_grad
+                st["step"] += 1                                                  # _multi_tensor_adam: steps on the CPU
+                self.optimizer._opt_called = True   # what torch's wrapped optimizer.step() sets for the LR schedulers' order check
+                h[2], h[3] = adam_scalars(g["lr"], g["betas"][0], g["betas"][1], st["step"].item())
+                self.adam_scal.copy_(h[2:4], non_blocking=True)
+
+    def _update(self, p, grad, n):
+        """The update over ``n`` elements, on the current device: p += lr * sign(grad) (train.py:160-161), or the optimizer's
+        Adam step (train.py:168-171: Adam minimises -direction * loss, grad = d(direction * loss))."""
+        lib, st = _lib.lib(), _lib.stream_ptr()
+        if self.optimizer is None:
+            _lib.check(lib.paa_sign_step(_lib.ptr(p), _lib.ptr(grad), float(self.args.lr), n, st))
+        else:
+            w1, b2, omb2, eps = self.adam_consts()
+            ast = self._adam_state()
+            _lib.check(lib.paa_adam_step(_lib.ptr(p), _lib.ptr(grad), -1.0, _lib.ptr(ast["exp_avg"]), _lib.ptr(ast["exp_avg_sq"]),
+                                         _lib.ptr(self.adam_scal), w1, b2, omb2, eps, _lib.ptr(self.adam_grad), n, st))
+
+    # ---- capture ----------------------------------------------------------------------------------------------------
+    def _replay_state(self):
+        """The device tensors a step advances and the warm-up step of capture() hands back."""
+        return [self.stats_log.cursor] if self.device_wer else []
+
+    def _warm_up(self, p, clean, labels, logits_out, refs):
+        """What capture() does before it opens a graph: fixes the buffers the graph will point into (-> labels, logits_out), runs
+        one eager step on a side stream, as torch's capture rules require, and undoes it — ``p``, the optimizer state and its
+        step count, the log cursor (the log holds replayed steps only) and the leaf's ``_replay_state`` are as before."""
+        lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
+        self._alpha_captured = self.mask_alpha > 0
+        saved = None
+        if self.optimizer is not None:
+            self._check_p(p)
+            ast = self._adam_state()
+            saved = (p.detach().clone(), ast["exp_avg"].clone(), ast["exp_avg_sq"].clone(), ast["step"].clone())
+        if logits_out is None:
+            logits_out = torch.empty(clean.shape[0], self.model.frames, self.model.arch.vocab_size, device=self.dev)
+        self._captured_buffers = (lab, logits_out)        # the graphs hold raw pointers: keep what capture() itself created alive
+        if self.device_wer and refs is not None:
+            self.set_refs(refs)
+        state = [(t, t.clone()) for t in self._replay_state()]
+        s = torch.cuda.Stream(device=self.dev)
+        s.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(s):
+            self.step(p, clean, lab, logits_out=logits_out)
+        torch.cuda.current_stream(self.dev).wait_stream(s)
+        for t, t0 in state:
+            t.copy_(t0)
+        if saved is not None:
+            torch.cuda.synchronize(self.dev)
+            p.detach().copy_(saved[0])
+            ast["exp_avg"].copy_(saved[1])
+            ast["exp_avg_sq"].copy_(saved[2])
+            ast["step"].copy_(saved[3])
+        return lab, logits_out
+
+    def _capture_body(self, p, clean, lab, logits_out):
+        """``_body`` as ONE hipGraph -> (graph, result dict); with Adam the graph is wrapped (``_AdamGraph``)."""
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            r = self._body(p, clean, lab, logits_out=logits_out)
+        return (g if self.optimizer is None else _AdamGraph(self, g)), r
+
+
+class PgdStepper(_StepperCore):
     def __init__(self, model, args, length: int, interp=None, spl_thresh=None, group=None, force_collective=False,
                  optimizer=None, device_wer=False, canon=None, r_cap=None, log_cap=4096, p_length=None):
         """``device_wer``: count this step's word errors on the device and log every step's stats (module docstring); ``canon``
@@ -131,62 +373,33 @@ class PgdStepper:
         over the perturbation (``adam_unsupported`` is None); the step then applies its update instead of the sign step.
         ``length`` is the clip length L.  With placement on (module docstring) the perturbation has ``p_length`` samples (default:
         ``place.perturbation_length(args, L)``); with placement off it has L."""
-        self.model, self.args, self.L = model, args, int(length)
+        L = int(length)
         self.place_on = place.placement_on(args)
-        self.Lp = self.L
+        self.Lp = L
         if self.place_on:
-            self.Lp = int(p_length) if p_length is not None else place.perturbation_length(args, self.L)
-            place.check(args, self.L, self.Lp)                                   # refusals: before any launch or collective
-        elif p_length is not None and int(p_length) != self.L:
-            raise ValueError(f"p_length {p_length} != clip length {self.L} needs placement on (perturbation_seconds)")
-        self.dev = model.device
-        self.norms = str(args.norm_type).split("+")
-        for n in self.norms:
-            if n not in _lib.NORM_IDS:
-                raise ValueError(f"Unknown norm_type: {n!r}")                  # train.py:98
-        self.direction = +1 if args.attack_mode == "untargeted" else -1          # train.py:124
-        self.packed = torch.zeros(self.Lp + N_STATS, dtype=torch.float32, device=self.dev)
-        self.grad = self.packed[: self.Lp].view(1, self.Lp)
-        self.stats = self.packed[self.Lp:]
-        self.proj = runtime.get_proj(args, self.dev, 1, self.Lp, interp)
-        if spl_thresh is not None:
-            self.proj.set_spl_thresh(spl_thresh)
-        self.group = group
+            self.Lp = int(p_length) if p_length is not None else place.perturbation_length(args, L)
+            place.check(args, L, self.Lp)                                        # refusals: before any launch or collective
+        elif p_length is not None and int(p_length) != L:
+            raise ValueError(f"p_length {p_length} != clip length {L} needs placement on (perturbation_seconds)")
+        self.group, self.interp = group, interp
         self.world = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.world = torch.distributed.get_world_size(group)
         masking_route(args.norm_type, self.world)
-        self.interp = interp
         self.collective = self.world > 1 or bool(force_collective)
         if self.collective and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
             raise RuntimeError("force_collective needs an initialised torch.distributed process group")
+        super().__init__(model, args, L, interp, spl_thresh, optimizer, device_wer, canon, r_cap, log_cap, 1, self.Lp)
         self.need_clean_stats = self.collective and any(n in ("snr", "tv") for n in self.norms)
-        self._prm = []
-        for n in self.norms:
-            a = type("A", (), dict(vars(args)))()
-            a.norm_type = n
-            self._prm.append(runtime.params_of(a))
-        self._wer_next = (0.0, 0.0)
-        self.optimizer = optimizer
-        if optimizer is not None:
-            why = adam_unsupported(optimizer)
-            if why is not None:
-                raise NotImplementedError(f"the device Adam step does not implement {why}")
-            self.adam_p = optimizer.param_groups[0]["params"][0]
-            if self.adam_p.numel() != self.Lp:
-                raise ValueError(f"optimizer parameter has {self.adam_p.numel()} elements, expected {self.Lp}")
-            self.adam_scal = torch.zeros(2, dtype=torch.float32, device=self.dev)
-            self.adam_grad = torch.zeros_like(self.adam_p, dtype=torch.float32, device=self.dev)
-        # host -> device scalars of each step: [wer errors, wer reference words, adam step_size, adam bias_correction2_sqrt].
-        # The copies are asynchronous, so a slot is rewritten only after the event behind its copies has completed.
-        self._ring = [torch.zeros(4, dtype=torch.float32).pin_memory() for _ in range(RING)] \
-            if (self.collective or optimizer is not None) else None
-        self._ring_ev = [None] * RING
-        self._ring_i = 0
-        self._init_masking_loss()
-        self._init_device_wer(device_wer, canon, r_cap, log_cap)
+        self.packed = torch.zeros(self.Lp + N_STATS, dtype=torch.float32, device=self.dev)
+        self.grad = self.packed[: self.Lp].view(1, self.Lp)
+        self.stats = self.packed[self.Lp:]
         if self.place_on:
             self._init_placement()
+
+    def _check_adam_shape(self):
+        if self.adam_p.numel() != self.Lp:
+            raise ValueError(f"optimizer parameter has {self.adam_p.numel()} elements, expected {self.Lp}")
 
     # ---- random placement of the perturbation ----------------------------------------------------------------------
     def _init_placement(self):
@@ -237,149 +450,14 @@ class PgdStepper:
         r["grad_rows"], r["grad"] = r["grad"], self.grad
         return r
 
-    # ---- on-device WER counters and the stats log ----------------------------------------------------------------
-    def _init_device_wer(self, device_wer, canon=None, r_cap=None, log_cap=4096):
-        self.device_wer = bool(device_wer)
-        if not self.device_wer:
-            return
-        from ..core import loss_helpers
-        canon = loss_helpers.canon_table(None) if canon is None else canon
-        self.canon = canon.to(self.dev, torch.int32).contiguous()
-        self.r_cap = int(loss_helpers.R_CAP if r_cap is None else r_cap)
-        nb = int(self.model.max_batch)
-        self.refs = torch.full((nb, self.r_cap), -1, dtype=torch.int32, device=self.dev)
-        self.ids = torch.zeros(nb * int(self.model.frames), dtype=torch.int16, device=self.dev)
-        self.wer_rows = torch.zeros(nb, 3, dtype=torch.int32, device=self.dev)     # (errors, ref words, hyp words) per clip
-        self.wer_batch = 0                                                         # clips of the last step
-        self.stats_log = StatsLog(self.dev, log_cap, N_STATS)
-
-    def set_refs(self, refs):
-        """Stream-ordered copy of the batch's reference rows (``loss_helpers.encode_refs``: (B, r_cap) int32, pinned or on the
-        device) into the fixed buffer the step — eager or captured — reads; call it before ``step`` / ``replay``."""
-        if not self.device_wer:
-            raise RuntimeError("set_refs needs a stepper built with device_wer=True")
-        if refs.dtype != torch.int32 or refs.dim() != 2 or refs.shape[1] != self.r_cap or refs.shape[0] > self.refs.shape[0]:
-            raise ValueError(f"refs must be int32 (B <= {self.refs.shape[0]}, {self.r_cap}), got {refs.dtype} {tuple(refs.shape)}")
-        self.refs[: refs.shape[0]].copy_(refs, non_blocking=True)
-
-    def _wer(self, logits, B):
-        """paa_argmax_ids + paa_wer_counts on the step's logits: per-clip counters -> wer_rows[:B], their sums -> slots 3, 4."""
-        if logits is None:
-            raise ValueError("device_wer needs the step's logits (want_logits=True)")
-        from ..core import loss_helpers
-        self.wer_batch = B
-        loss_helpers.wer_counts_device(logits, self.refs[:B], self.canon, out=self.wer_rows[:B],
-                                       sums=self.stats[ST_WER_ERR:ST_WER_REF + 1], ids_out=self.ids[: B * logits.shape[1]])
-
-    def read_log(self):
-        """The stats rows of the steps since the last call, oldest first: CPU float32 (n, N_STATS), global sums after the
-        collective (slot 0 CTC loss, 3 / 4 word errors / reference words, 6 masking loss).  The one host sync of an epoch."""
-        return self.stats_log.read()
-
-    # ---- masking-threshold loss term ---------------------------------------------------------------------------
-    def _init_masking_loss(self):
-        self.mask_alpha = 0.0
-        self.alpha_dev = None
-        self._alpha_captured = None          # capture() records whether the captured launch sequence holds the term
-        a = type("A", (), dict(vars(self.args)))()
-        a.norm_type = "masking"
-        self._mask_prm = runtime.params_of(a)                 # paa_masking_loss reads masking_margin_db only
-        alpha = float(getattr(self.args, "masking_loss_alpha", 0.0))
-        if alpha < 0:
-            raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
-        if alpha > 0:
-            self.set_masking_alpha(alpha)
-
-    def set_masking_alpha(self, alpha: float):
-        """Weight of the masking-threshold loss term from the next step on.  The value goes to a one-float device tensor by a
-        stream-ordered copy from pinned memory, so eager steps and captured graphs alike follow it without recapture.  Whether
-        the term is in the launch sequence at all (alpha > 0) is fixed by ``capture()``: switching it on or off afterwards
-        raises."""
-        alpha = float(alpha)
-        if alpha < 0:
-            raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
-        if self._alpha_captured is not None and (alpha > 0) != self._alpha_captured:
-            raise ValueError("masking_loss_alpha cannot switch between 0 and > 0 after capture(): the captured launch sequence "
-                             f"{'holds' if self._alpha_captured else 'does not hold'} the loss term; capture the step again")
-        if alpha > 0:
-            if self.alpha_dev is None:
-                self.alpha_dev = torch.zeros(1, dtype=torch.float32, device=self.dev)
-                self._aring = [torch.zeros(1, dtype=torch.float32).pin_memory() for _ in range(RING)]
-                self._aring_ev = [None] * RING
-                self._aring_i = 0
-            k = self._aring_i % RING
-            self._aring_i += 1
-            if self._aring_ev[k] is not None:
-                self._aring_ev[k].synchronize()
-            self._aring[k][0] = alpha
-            with torch.cuda.device(self.dev):
-                self.alpha_dev.copy_(self._aring[k], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(self.dev))
-            self._aring_ev[k] = ev
-        elif self.mask_alpha > 0:
-            self.stats[ST_MASK_LOSS] = 0.0
-        self.mask_alpha = alpha
-
-    def _masking_loss(self, p, clean, grad, loss_rows=None):
-        """grad -= alpha * grad(sum_b l_b); sum_b l_b -> slot 6.  p (rows, L), rows in {1, B}."""
-        B = clean.shape[0]
-        with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().paa_masking_loss(self.proj.h, self._mask_prm, _lib.ptr(p), p.shape[0] if p.dim() == 2 else 1,
-                                                   _lib.ptr(clean), B, self.L, _lib.ptr(self.alpha_dev), _lib.ptr(grad),
-                                                   _lib.ptr(loss_rows), _lib.ptr(self.stats[ST_MASK_LOSS:ST_MASK_LOSS + 1]), None,
-                                                   _lib.stream_ptr()))
+    def _replay_state(self):
+        return super()._replay_state() + ([self.counter] if self.place_on else [])
 
     # ---- bookkeeping carried by the packed vector -------------------------------------------------------------
     def set_wer_counts(self, errors: float, ref_words: float):
         """Host-side WER counters of the PREVIOUS step (train.py:149-153): the next ``step`` writes them behind the
         gradient, so its all-reduce sums them over ranks; read the global sums from ``stats[3:5]`` afterwards."""
         self._wer_next = (float(errors), float(ref_words))
-
-    def adam_consts(self):
-        """(w1, beta2, omb2, eps) of the optimizer's param group as the foreach kernels see them (f32 by value)."""
-        g = self.optimizer.param_groups[0]
-        b1, b2 = g["betas"]
-        return float(1 - b1), float(b2), float(1 - b2), float(g["eps"])
-
-    def _adam_state(self):
-        """optimizer.state[p], created as torch's Adam._init_group does on its first step (non-capturable, non-fused)."""
-        st = self.optimizer.state[self.adam_p]
-        if len(st) == 0:
-            st["step"] = torch.tensor(0.0, dtype=torch.float32)
-            st["exp_avg"] = torch.zeros_like(self.adam_p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(self.adam_p, memory_format=torch.preserve_format)
-        return st
-
-    def _pre_step(self, consts=None):
-        """Host side of one step, before its launches (eager step, single-graph replay and _SplitGraph.replay alike): this
-        rank's WER counters of the previous step go behind the gradient, and for Adam the step count is advanced and the
-        step's scalars go to ``adam_scal``.  ``consts``: the (w1, beta2, omb2, eps) a graph captured by value."""
-        if self._ring is None:
-            return
-        k = self._ring_i % RING
-        self._ring_i += 1
-        if self._ring_ev[k] is not None:
-            self._ring_ev[k].synchronize()
-        h = self._ring[k]
-        if self.collective and not self.device_wer:
-            h[0], h[1] = self._wer_next
-            self._wer_next = (0.0, 0.0)
-            self.stats[ST_WER_ERR:ST_WER_REF + 1].copy_(h[0:2], non_blocking=True)
-        if self.optimizer is not None:
-            if consts is not None and self.adam_consts() != consts:
-                raise ValueError("Adam betas / eps changed after capture(); capture the step again")
-            g = self.optimizer.param_groups[0]
-            st = self._adam_state()
-            if self.adam_p.grad is not self.adam_grad:
-                self.adam_p.grad = self.adam_grad
-            st["step"] += 1                                                  # _multi_tensor_adam: steps on the CPU
-            self.optimizer._opt_called = True       # what torch's wrapped optimizer.step() sets for the LR schedulers' order check
-            h[2], h[3] = adam_scalars(g["lr"], g["betas"][0], g["betas"][1], st["step"].item())
-            self.adam_scal.copy_(h[2:4], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))
-        self._ring_ev[k] = ev
 
     # ---- the two halves of a step (everything before / after the collective) ----------------------------------
     def _pre(self, p, clean, labels, want_logits=True, logits_out=None):
@@ -403,25 +481,18 @@ class PgdStepper:
         return r
 
     def _post(self, p, clean):
-        lib, L, B = _lib.lib(), self.Lp, clean.shape[0]
-        if L != self.L:                     # a perturbation of its own length: nothing pairs it with the clean samples
+        lib, Lp, B = _lib.lib(), self.Lp, clean.shape[0]
+        if Lp != self.L:                    # a perturbation of its own length: nothing pairs it with the clean samples
             clean, B = None, 0
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr()
-            if self.optimizer is None:
-                _lib.check(lib.paa_sign_step(_lib.ptr(p), _lib.ptr(self.grad), float(self.args.lr), L, st))   # train.py:160-161
-            else:                       # train.py:168-171: Adam minimises -direction * loss, self.grad = d(direction * loss)
-                w1, b2, omb2, eps = self.adam_consts()
-                ast = self._adam_state()
-                _lib.check(lib.paa_adam_step(_lib.ptr(p), _lib.ptr(self.grad), -1.0, _lib.ptr(ast["exp_avg"]),
-                                             _lib.ptr(ast["exp_avg_sq"]), _lib.ptr(self.adam_scal), w1, b2, omb2, eps,
-                                             _lib.ptr(self.adam_grad), L, st))
+            self._update(p, self.grad, Lp)
             for n, prm in zip(self.norms, self._prm):                                                   # train.py:162
                 if self.need_clean_stats and n in ("snr", "tv"):
                     _lib.check(lib.paa_project_ext(self.proj.h, prm, _lib.ptr(p), 1, _lib.ptr(self.stats[ST_SQ:ST_TV + 1]),
-                                                   _lib.ptr(self.stats[ST_CLIPS:ST_CLIPS + 1]), 0.0, L, st))
+                                                   _lib.ptr(self.stats[ST_CLIPS:ST_CLIPS + 1]), 0.0, Lp, st))
                 else:
-                    _lib.check(lib.paa_project(self.proj.h, prm, _lib.ptr(p), 1, _lib.ptr(clean), B, L, st))
+                    _lib.check(lib.paa_project(self.proj.h, prm, _lib.ptr(p), 1, _lib.ptr(clean), B, Lp, st))
         if self.device_wer:
             self.stats_log.push(self.stats)
 
@@ -447,10 +518,6 @@ class PgdStepper:
         if ("masking" in self.norms or self.mask_alpha > 0) and self.proj.max_batch < B:
             self.proj = runtime.get_proj(self.args, self.dev, B, self.L, self.interp)
 
-    def _check_p(self, p):
-        if self.optimizer is not None and p.data_ptr() != self.adam_p.data_ptr():
-            raise ValueError("the Adam step updates the optimizer's own parameter; pass that tensor as p")
-
     def _body(self, p, clean, labels, want_logits=True, logits_out=None):
         r = self._pre(p, clean, labels, want_logits, logits_out)
         if self.collective:
@@ -462,9 +529,10 @@ class PgdStepper:
     def capture(self, p, clean, labels, logits_out=None, refs=None):
         """Capture one step on fixed buffers into hipGraphs (the launch sequence allocates nothing and never
         synchronises, so it is capturable as is).  With device_wer, ``refs`` fills the fixed reference buffer (refresh it with
-        ``set_refs`` before a replay) and the warm-up step's log row is taken back: the log holds replayed steps only.  Returns (graph, result dict); ``graph.replay()`` re-runs the step
-        in place on ``p`` with whatever ``clean`` / ``labels`` currently hold.  With several ranks the halves before
-        and after the collective are two graphs and the all-reduce runs between their replays.
+        ``set_refs`` before a replay) and the warm-up step's log row is taken back: the log holds replayed steps only.  Returns
+        (graph, result dict); ``graph.replay()`` re-runs the step in place on ``p`` with whatever ``clean`` / ``labels`` currently
+        hold.  With several ranks the halves before and after the collective are two graphs and the all-reduce runs between
+        their replays.
 
         With Adam the result is always an object with ``replay()`` (the step's scalars are pushed before each replay), betas
         and eps are captured by value (``replay()`` raises ValueError once they change), and the warm-up step is undone:
@@ -477,44 +545,9 @@ class PgdStepper:
 
         With placement the draw is inside the graph (the first one of the split form) and the warm-up step's draw is taken back:
         the device step counter is as before the call, so the first replay draws what the first eager step would have."""
-        lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
-        self._alpha_captured = self.mask_alpha > 0
-        saved = None
-        if self.optimizer is not None:
-            self._check_p(p)
-            ast = self._adam_state()
-            saved = (p.detach().clone(), ast["exp_avg"].clone(), ast["exp_avg_sq"].clone(), ast["step"].clone())
-        if logits_out is None:
-            logits_out = torch.empty(clean.shape[0], self.model.frames, self.model.arch.vocab_size, device=self.dev)
-        self._captured_buffers = (lab, logits_out)        # the graphs hold raw pointers: keep what capture() itself created alive
-        cur0 = None
-        if self.device_wer:
-            if refs is not None:
-                self.set_refs(refs)
-            cur0 = self.stats_log.cursor.clone()
-        cnt0 = self.counter.clone() if self.place_on else None
-        s = torch.cuda.Stream(device=self.dev)
-        s.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(s):                       # warm-up on the side stream, as torch's capture rules require
-            self.step(p, clean, lab, logits_out=logits_out)
-        torch.cuda.current_stream(self.dev).wait_stream(s)
-        if cur0 is not None:
-            self.stats_log.cursor.copy_(cur0)
-        if cnt0 is not None:
-            self.counter.copy_(cnt0)
-        if saved is not None:
-            torch.cuda.synchronize(self.dev)
-            p.detach().copy_(saved[0])
-            ast["exp_avg"].copy_(saved[1])
-            ast["exp_avg_sq"].copy_(saved[2])
-            ast["step"].copy_(saved[3])
+        lab, logits_out = self._warm_up(p, clean, labels, logits_out, refs)
         if not self.collective:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                r = self._body(p, clean, lab, logits_out=logits_out)
-            if self.optimizer is None:
-                return g, r
-            return _AdamGraph(self, g), r
+            return self._capture_body(p, clean, lab, logits_out)
         # No collective may be in flight while a capture is open (the process group's watchdog thread polls its events), and the
         # captures only guard THIS thread's launches: the RCCL call between them runs eagerly.
         torch.cuda.synchronize(self.dev)

@@ -102,17 +102,15 @@ def perturbation_constraint(p: torch.Tensor, clean_audio, args, interp, spl_thre
     out_len = L
     with torch.cuda.device(q.device):
         for i, n in enumerate(norms):
-            a = type("A", (), dict(vars(args)))()
-            a.norm_type = n
+            prm = runtime.params_of(args, n)
             if n == "max_phon":
                 pr.set_spl_thresh(spl_thresh)
             nb = 0 if clean is None else clean.shape[0]
             if i == 0:       # the reference's functions return a new tensor: out of place from p (one fused launch for the FFT norms)
-                _lib.check(_lib.lib().paa_project_to(pr.h, runtime.params_of(a), _lib.ptr(src), _lib.ptr(q), rows, _lib.ptr(clean),
+                _lib.check(_lib.lib().paa_project_to(pr.h, prm, _lib.ptr(src), _lib.ptr(q), rows, _lib.ptr(clean),
                                                      nb, L, _lib.stream_ptr()))
             else:
-                _lib.check(_lib.lib().paa_project(pr.h, runtime.params_of(a), _lib.ptr(q), rows, _lib.ptr(clean), nb, L,
-                                                  _lib.stream_ptr()))
+                _lib.check(_lib.lib().paa_project(pr.h, prm, _lib.ptr(q), rows, _lib.ptr(clean), nb, L, _lib.stream_ptr()))
             if n in FREQ_NORMS and clean is None:
                 out_len = pr.hop * (L // pr.hop)        # iSTFT length hop*(T-1); no _align_to without clean audio
     return q if out_len == L else q[..., :out_len]

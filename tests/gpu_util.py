@@ -1,4 +1,5 @@
-"""Helpers for the -m gpu tests: run a paa_gemm descriptor on device buffers, report errors."""
+"""Helpers for the -m gpu tests: run a paa_gemm descriptor on device buffers, report errors, record the library calls of a step."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -36,3 +37,34 @@ def rel_err(got, ref):
     got = np.asarray(got, dtype=np.float64)
     ref = np.asarray(ref, dtype=np.float64)
     return float(np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-30))
+
+
+class _LibProxy:
+    """Forwards every attribute to the loaded library; a called ``paa_*`` entry appends its name to ``names`` first.  The
+    ``paa_*_destroy`` entries are left out: finalizers call them, whenever an object of an earlier test happens to be freed."""
+
+    def __init__(self, lib, names):
+        self._lib, self._names = lib, names
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("paa_") or name.endswith("_destroy"):
+            return fn
+
+        def call(*a):
+            self._names.append(name)
+            return fn(*a)
+        return call
+
+
+@contextlib.contextmanager
+def record_launches():
+    """``with record_launches() as names``: every ``paa_*`` entry called through ``paa_amd._lib.lib()`` inside the block, in call
+    order.  The calls themselves go through unchanged."""
+    real, names = _lib.lib, []
+    proxy = _LibProxy(real(), names)
+    _lib.lib = lambda: proxy
+    try:
+        yield names
+    finally:
+        _lib.lib = real

@@ -1,6 +1,7 @@
 """Child process of tests/test_gpu_rccl.py (started fresh, before any GPU call of its own): ONE rank on cuda:0 with the "nccl"
 (= RCCL) backend.  Runs the PGD step with the packed all-reduce really executing (PgdStepper(force_collective=True)) — eagerly and
-through capture()'s two-graph form — next to the collective-free stepper from the same starting point, and prints one JSON line."""
+through capture()'s two-graph form — next to the collective-free stepper from the same starting point, and prints one JSON line
+(with the library calls of the collective stepper's first eager step, in order)."""
 import json
 import os
 import sys
@@ -17,6 +18,7 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    from gpu_util import record_launches
     from oracle import pgd as opgd
     from oracle.gen_cases import cli_to_args
     from paa_amd import arch as A, synth
@@ -42,8 +44,10 @@ def main():
         coll = PgdStepper(m, args, L, force_collective=True)
         assert coll.collective and coll.world == 1
         p_e = p0.clone()
-        for _ in range(steps):
+        with record_launches() as launches:
             r = coll.step(p_e, clean, labels)                     # fwd/bwd -> all_reduce(packed) over RCCL -> sign step + projection
+        for _ in range(steps - 1):
+            r = coll.step(p_e, clean, labels)
         torch.cuda.synchronize()
         loss_e, clips = float(coll.stats[ST_LOSS]), float(coll.stats[ST_CLIPS])
         p_g = p0.clone()
@@ -56,7 +60,8 @@ def main():
         out[norm] = {"eager_equal": bool(torch.equal(p_e, p_ref)), "graph_equal": bool(torch.equal(p_g, p_ref)),
                      "graph_equals_eager_collective": bool(torch.equal(p_g, p_e)),
                      "eager_maxdiff": float((p_e - p_ref).abs().max()) / scale, "graph_maxdiff": float((p_g - p_ref).abs().max()) / scale,
-                     "loss_ref": loss_ref, "loss_collective": loss_e, "clips_slot": clips, "split_graph": type(graph).__name__}
+                     "loss_ref": loss_ref, "loss_collective": loss_e, "clips_slot": clips, "split_graph": type(graph).__name__,
+                     "launches": launches}
         del graph, coll, plain, m
     dist.destroy_process_group()
     print("RCCL_CHILD " + json.dumps(out), flush=True)

@@ -159,3 +159,32 @@ def test_per_clip_init_independent_of_split_and_ranks():
             for _, _, idx in clip_batches(_batches(7, bs * world), r, world):
                 assert np.array_equal(init_rows(L, idx, seed=5), whole[idx])
     assert not np.array_equal(init_rows(L, [0], seed=6)[0], whole[0])
+
+
+def test_params_of_norm_override_equals_a_cloned_namespace():
+    """``params_of(args, n)`` is, field for field, what ``params_of`` gives for a copy of ``args`` whose norm_type is ``n``."""
+    import copy
+    from paa_amd import _lib, runtime
+    from paa_amd.training_utils import parser
+    args = parser.create_arg_parser().parse_args(["--norm_type", "linf+tv+masking", "--linf_size", "0.02", "--tv_epsilon", "0.5",
+                                                  "--masking_margin_db", "-3", "--attack_mode", "targeted", "--lr", "3e-4"])
+    for a in (args, types.SimpleNamespace(norm_type="snr+l2")):                   # the second: every field from its default
+        for n in (*str(a.norm_type).split("+"), "masking"):
+            clone = copy.copy(a)
+            clone.norm_type = n
+            want, got = runtime.params_of(clone), runtime.params_of(a, n)
+            for field, _ in _lib.PaaParams._fields_:
+                assert getattr(got, field) == getattr(want, field), (n, field)
+        with pytest.raises(ValueError, match="Unknown norm_type"):
+            runtime.params_of(a)                                                  # a '+'-joined list is no norm
+        with pytest.raises(ValueError, match="Unknown norm_type"):
+            runtime.params_of(a, "l3")
+
+
+def test_clip_stepper_has_no_universal_surface():
+    """Placement, the clip base of the draw and the host WER counters of the collective belong to the universal step alone."""
+    from paa_amd.training_utils.clip_attack import ClipStepper
+    from paa_amd.training_utils.pgd import PgdStepper
+    for name in ("set_placement", "set_place_step", "clip_base", "set_wer_counts"):
+        assert hasattr(PgdStepper, name), name
+        assert not hasattr(ClipStepper, name), name

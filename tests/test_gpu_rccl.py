@@ -36,5 +36,8 @@ def test_one_rank_rccl_all_reduce_eager_and_captured():
     assert snr["graph_equals_eager_collective"], snr
     assert snr["eager_maxdiff"] < 1e-6 and snr["graph_maxdiff"] < 1e-6, snr
     assert snr["clips_slot"] == 3.0                               # the clip count survived the all-reduce in slot 5
+    # the library calls of the collective stepper's eager step: snr takes the clean statistics from the all-reduced vector
+    assert snr["launches"] == ["paa_model_fwd_bwd", "paa_batch_stats", "paa_sign_step", "paa_project_ext"]
+    assert mp_["launches"] == ["paa_model_fwd_bwd", "paa_sign_step", "paa_project"]
     for c in (mp_, snr):
         assert c["loss_collective"] == pytest.approx(c["loss_ref"], rel=1e-6)
