@@ -46,7 +46,8 @@ typedef struct {
 } paa_params;
 
 const char* paa_last_error(void);
-/* 350 = this header (340 + the placement entries paa_place_draw, paa_place_rows and paa_place_reduce); 351 = the same ABI built
+/* 350 = this header (340 + the placement entries paa_place_draw, paa_place_rows and paa_place_reduce; the room-response entries
+ * paa_rir_draw and paa_rir_apply are later additions that changed nothing else and took no new number); 351 = the same ABI built
  * with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
  * tools/ only).  Bindings refuse other values. */
 int paa_version(void);
@@ -210,6 +211,29 @@ paa_status paa_place_rows(const float* d_p, int Lp, const int32_t* d_shift, cons
  * f32.  An output with no term (Lp > L) is +0.0f. */
 paa_status paa_place_reduce(const float* d_grad_rows, const int32_t* d_shift, const float* d_gain, float* d_grad, int B, int L,
                             int Lp, void* stream);
+
+/* ---- room responses on the placement layer (extension) ---------------------------------------------------------
+ * A bank d_bank (N, K) of float32 room responses; clip b hears its row through response c_b = d_index[b]:
+ *   out[b][i] = sum_{k=0}^{min(K-1, i)}     h_c[k] * in[b][i - k]      i = 0 .. L-1   (adjoint = 0: causal FIR, zero history, the
+ *                                                                                      tail beyond L dropped; linear, not circular)
+ *   out[b][j] = sum_{k=0}^{min(K-1, L-1-j)} h_c[k] * in[b][j + k]      j = 0 .. L-1   (adjoint = 1: the exact adjoint)
+ * Both entries are asynchronous on the stream, allocate nothing, are capturable and use no atomics: two calls give the same bits.
+ * They are additions to ABI 350: a binding that does not know them loses nothing.
+ *
+ * paa_rir_draw: Philox4x32-10 as paa_place_draw, the same key, counter (step, clip_base + b, stream_id, 1) — word 3 = 1 keeps the
+ * draw disjoint from placement's, which uses 0.  d_index[b] = (r0 * N) >> 32.  step = *d_counter, a counter of the room draw's
+ * own (placement's is not advanced under explicit placements); *d_counter = step + 1 on the device, by one thread, after every
+ * clip has read it.  One block.  Null pointers, B < 1 or N < 1: PAA_ERR_ARG. */
+#define PAA_RIR_MAX_TAPS 16384
+paa_status paa_rir_draw(uint64_t seed, int32_t* d_counter, int stream_id, int clip_base, int B, int N, int32_t* d_index,
+                        void* stream);
+/* d_in (B, L) -> d_out (B, L), WRITTEN; they must not overlap (PAA_ERR_ARG).  An index outside [0, N) is reduced modulo N on the
+ * device (never an out-of-bounds row).  1 <= K <= PAA_RIR_MAX_TAPS, N >= 1, B >= 1, L >= 1, else PAA_ERR_ARG before any launch.
+ * 64-bit element offsets; rows need no alignment.  Every output is one f32 fmaf chain over j = 0 .. K + 30 in ascending order
+ * (v_mfma_f32_32x32x2_f32; terms outside the response or the row are exact zeros), independent of the grid:
+ * |out - exact| <= (K + 64) 2^-24 sum_k |h_k in| + 2^-149. */
+paa_status paa_rir_apply(const float* d_bank, int N, int K, const int32_t* d_index, const float* d_in, float* d_out, int B, int L,
+                         int adjoint, void* stream);
 
 /* ------------------------------------------------------------------ model context ---------- */
 /* Wav2Vec2ForCTC forward + CTC loss + backward to the waveform (core/loss_helpers.py:12-23 ->

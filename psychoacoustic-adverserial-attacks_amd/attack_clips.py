@@ -21,7 +21,7 @@ import torch
 
 from .core import iso, loss_helpers
 from .core.masking import masking_loss
-from .training_utils import build, parser, place, save
+from .training_utils import build, parser, place, rir, save
 from .training_utils.clip_attack import ClipStepper, clip_nll, compose_rows, init_rows, project_rows
 
 SPLITS = ("test", "val", "train")
@@ -158,6 +158,7 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
 
 def main(args) -> int:
     place.refuse_for_clips(args)
+    rir.refuse_for_clips(args)
     if not torch.cuda.is_available():
         raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")
     if not str(args.device).startswith("cuda"):

@@ -12,7 +12,7 @@ import sys
 import torch
 
 from .core import iso
-from .training_utils import build, evaluation, parser, pgd, place, save, scoring_helpers, train
+from .training_utils import build, evaluation, parser, pgd, place, rir, save, scoring_helpers, train
 
 
 def main(args) -> int:
@@ -25,6 +25,7 @@ def main(args) -> int:
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     pgd.masking_route(args.norm_type, world)          # before any collective: every rank raises
     place.check_flags(args)                           # the same for what placement does not combine with at any length
+    rir.check_flags(args)                             # and for room responses
     if world > 1:
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
         torch.cuda.set_device(local)
@@ -59,6 +60,7 @@ def main(args) -> int:
     mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
     extra = {}          # results.json keys of the masking-threshold loss term: present only when masking_loss_alpha > 0
     place_extra = place.results_extra(args, p.shape[-1])          # and those of placement, present only when it is on
+    place_extra.update(rir.results_extra(args))                   # and those of room responses, likewise
     extra.update(place_extra)
     goal = scoring_helpers.Objective(args.attack_mode)      # targeted: perturbed WER down; untargeted: perturbed CTC up
     best_epoch, no_improve, best_eval = -1, 0, goal.worst

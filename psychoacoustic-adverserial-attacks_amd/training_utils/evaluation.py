@@ -5,13 +5,15 @@ from __future__ import annotations
 import torch
 
 from ..core import loss_helpers
-from . import place
+from . import place, rir
 from .scoring_helpers import Scores
 
 
 class _PlacedEval:
     """evaluate(perturbed=True) with placement on: every batch sees the perturbation at a drawn placement (Philox stream 1, the
-    step counter restarting at 0 in every evaluate call, so every evaluation sees the same placements and epochs compare)."""
+    step counter restarting at 0 in every evaluate call, so every evaluation sees the same placements and epochs compare).  With
+    room responses on (training_utils/rir.py) the rows then pass through rooms drawn the same way: every evaluation hears the same
+    rooms; with placement itself off the rows are the perturbation at shift 0 and gain 1."""
 
     def __init__(self, args, model, pp):
         rank = 0
@@ -24,10 +26,22 @@ class _PlacedEval:
         self.pp = pp
         self.placer = place.Placer(model.device, nb, L, pp.numel(), seed, place.STREAM_EVAL, place.shift_on(args),
                                    place.gain_db(args), clip_base=rank * nb, with_grad=False)
+        self.reverb = None
+        if not place.placement_on(args):
+            self.placer.set_placement([0] * nb)
+        if rir.rir_on(args):
+            rir.check(args)
+            self.reverb = rir.Reverb(model.device, rir.bank_of(args), nb, L, rir.draw_seed(args), place.STREAM_EVAL,
+                                     clip_base=rank * nb, with_grad=False)
 
     def rows(self, B):
-        self.placer.draw(B)
-        return self.placer.place(self.pp, B)
+        if not self.placer.explicit:
+            self.placer.draw(B)
+        rows = self.placer.place(self.pp, B)
+        if self.reverb is not None:
+            self.reverb.draw(B)
+            rows = self.reverb.apply(self.placer.rows, B)
+        return rows
 
 
 def _pert(pp, B):
@@ -85,7 +99,7 @@ def evaluate(args, eval_data_loader, p, model, processor, wer_metric, perturbed=
     pp = None
     if perturbed and isinstance(p, torch.Tensor):
         pp = p.detach().to(model.device, torch.float32).reshape(1, -1).contiguous()
-        if place.placement_on(args):
+        if place.placement_on(args) or rir.rir_on(args):
             pp = _PlacedEval(args, model, pp)
     if getattr(args, "device_wer", False):
         from .train import device_wer_canon

@@ -20,6 +20,16 @@ def _place_gain_db(v: str) -> float:
     return g
 
 
+def _ranged(name, lo, hi, typ):
+    def conv(v: str):
+        x = typ(v)
+        if not lo <= x <= hi:
+            raise argparse.ArgumentTypeError(f"{name} must be in [{lo:g}, {hi:g}], got {v}")
+        return x
+    conv.__name__ = name
+    return conv
+
+
 def create_arg_parser():
     parser = argparse.ArgumentParser()
     # standard training params (parser.py:10-20)
@@ -87,4 +97,15 @@ def create_arg_parser():
                         help='random: every clip of every step sees the perturbation at a circular shift of its own')
     parser.add_argument('--place_gain_db', type=_place_gain_db, default=0.0,
                         help='G in [0, 20]: every clip of every step sees the perturbation at a gain uniform in [-G, +G] dB')
+    # room responses on the placement layer (extension); the default leaves the step as it is
+    parser.add_argument('--rir_bank', type=str, default="none",
+                        help='none | synthetic | PATH (.npy or weights-only .pt holding a float (N, K) array): every clip of every '
+                             'step hears the perturbation through a room response drawn from the bank')
+    parser.add_argument('--rir_count', type=_ranged("rir_count", 1, 65536, int), default=64, help='responses in a synthetic bank')
+    parser.add_argument('--rir_taps', type=_ranged("rir_taps", 1, 16384, int), default=4096, help='taps per response in a synthetic bank')
+    parser.add_argument('--rir_rt60', type=_ranged("rir_rt60", 0.01, 10.0, float), nargs=2, default=[0.2, 0.6], metavar=("LO", "HI"),
+                        help='RT60 range of a synthetic bank in seconds')
+    parser.add_argument('--rir_drr_db', type=_ranged("rir_drr_db", -40.0, 60.0, float), default=6.0,
+                        help='direct-to-reverberant energy ratio of a synthetic bank in dB')
+    parser.add_argument('--rir_seed', type=int, default=None, help='seed of the synthetic bank (default: --seed)')
     return parser

@@ -18,8 +18,12 @@
     ``place_shift`` / ``place_gain_db``;       paa_place_rows
     universal only)                            paa_model_fwd_bwd_rows                                     in place of paa_model_fwd_bwd
                                                paa_place_reduce                                           right after the backward pass
+    room responses (``rir_bank``; universal    paa_rir_draw (not after ``set_rooms``), paa_rir_apply      between paa_place_rows and the forward
+    only; runs the placement launches too,     paa_rir_apply (adjoint)                                    between the backward pass and
+    at shift 0 / gain 1 when placement is off)                                                            paa_place_reduce
 
-A mode that is off adds no launch: alpha = 0, ``device_wer=False`` and placement off are the plain step, bit for bit.
+A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off and room responses off are the plain step, bit
+for bit.
 
 The packed vector is ``[ grad (Lp) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, masking loss, 0 ]`` in
 float32; the 8 stat slots are defined HERE (ST_*) and documented in include/paa_hip.h (paa_model_fwd_bwd, d_stats).  Every rank
@@ -44,6 +48,10 @@ later plain ``optimizer.step()`` see the steps taken here, and a StepLR lr is pi
 Placement (training_utils/place.py): the perturbation has ``Lp`` samples, the clips ``L``; clip b is composed with
 a_b * delta[(i + s_b) mod Lp] and ``paa_place_reduce`` is the adjoint gather-sum into the packed gradient; the update and the
 projections run on (1, Lp).  The draw's step counter lives on the device, so a captured graph draws anew on every replay.
+
+Room responses (training_utils/rir.py): the placed rows pass through a causal FIR h_{c_b} per clip before the model
+and the gradient rows through its adjoint before ``paa_place_reduce``; the room draw has a device counter of its own.  With
+placement off the rows are placed at Lp = L with explicit zero shifts and unit gains, and ``place_on`` stays False.
 """
 from __future__ import annotations
 
@@ -52,7 +60,7 @@ import contextlib
 import torch
 
 from .. import _lib, runtime
-from . import place
+from . import place, rir
 
 FREQ_NORMS = ("fletcher_munson", "min_max_freqs", "max_phon")
 N_STATS = 8
@@ -375,6 +383,8 @@ class PgdStepper(_StepperCore):
         ``place.perturbation_length(args, L)``); with placement off it has L."""
         L = int(length)
         self.place_on = place.placement_on(args)
+        self.rir_on = rir.rir_on(args)
+        rir.check(args)                                                          # refusals: before any launch or collective
         self.Lp = L
         if self.place_on:
             self.Lp = int(p_length) if p_length is not None else place.perturbation_length(args, L)
@@ -394,8 +404,10 @@ class PgdStepper(_StepperCore):
         self.packed = torch.zeros(self.Lp + N_STATS, dtype=torch.float32, device=self.dev)
         self.grad = self.packed[: self.Lp].view(1, self.Lp)
         self.stats = self.packed[self.Lp:]
-        if self.place_on:
+        if self.place_on or self.rir_on:
             self._init_placement()
+        if self.rir_on:
+            self._init_rir()
 
     def _check_adam_shape(self):
         if self.adam_p.numel() != self.Lp:
@@ -411,8 +423,30 @@ class PgdStepper(_StepperCore):
         seed = int(getattr(self.args, "seed", 5) if seed is None else seed)
         self.placer = place.Placer(self.dev, nb, self.L, self.Lp, seed, place.STREAM_TRAIN, place.shift_on(self.args),
                                    place.gain_db(self.args), clip_base=rank * nb)
+        if not self.place_on:               # room responses alone: the rows are delta itself, and nothing is drawn
+            self.placer.set_placement([0] * nb)
         self.shift, self.gain, self.counter = self.placer.shift, self.placer.gain, self.placer.counter
         self.rows, self.grad_rows = self.placer.rows, self.placer.grad_rows
+
+    def _init_rir(self):
+        pl = self.placer
+        self.reverb = rir.Reverb(self.dev, rir.bank_of(self.args), pl.max_batch, self.L, rir.draw_seed(self.args), place.STREAM_TRAIN,
+                                 clip_base=pl.clip_base)
+        self.room, self.rir_counter, self.wet_rows = self.reverb.index, self.reverb.counter, self.reverb.rows
+
+    def _reverb(self):
+        if not self.rir_on:
+            raise RuntimeError("the stepper was built with room responses off (rir_bank)")
+        return self.reverb
+
+    def set_rooms(self, index):
+        """Explicit per-clip room indices instead of the draw, from the next step on (stream-ordered copy into the fixed buffer);
+        ``set_rooms(None)`` returns to drawing.  A captured graph keeps the form it was captured with."""
+        self._reverb().set_rooms(index)
+
+    def set_rir_step(self, n: int):
+        """Device step counter of the next room draw (resume, tests)."""
+        self._reverb().set_step(n)
 
     def _placer(self):
         if not self.place_on:
@@ -430,28 +464,35 @@ class PgdStepper(_StepperCore):
 
     @property
     def clip_base(self):
-        """Global id of this rank's first clip in the draw's counter (default rank * model.max_batch); assignable per step.  A
+        """Global id of this rank's first clip in the draws' counters (default rank * model.max_batch); assignable per step.  A
         captured graph holds the value it was captured with."""
-        return self._placer().clip_base
+        return (self.placer if self.rir_on else self._placer()).clip_base
 
     @clip_base.setter
     def clip_base(self, v):
-        self._placer().clip_base = int(v)
+        (self.placer if self.rir_on else self._placer()).clip_base = int(v)
+        if self.rir_on:
+            self.reverb.clip_base = int(v)
 
     def _placed_fwd_bwd(self, p, clean, labels, want_logits, out):
-        """draw -> rows -> forward / backward with one gradient row per clip -> adjoint gather-sum into self.grad."""
+        """draw -> rows [-> room draw -> rows through the rooms] -> forward / backward with one gradient row per clip [-> the
+        rooms' adjoint] -> adjoint gather-sum into self.grad."""
         B, pl = clean.shape[0], self.placer
         if not pl.explicit:
             pl.draw(B)
         rows = pl.place(p, B)
+        if self.rir_on:
+            if not self.reverb.explicit:
+                self.reverb.draw(B)
+            rows = self.reverb.apply(pl.rows, B)
         out["grad"] = pl.grad_rows[:B]
         r = self.model.fwd_bwd(clean, rows, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
-        pl.reduce(B, self.grad)
+        pl.reduce(B, self.grad, self.reverb.adjoint(pl.grad_rows, B) if self.rir_on else None)
         r["grad_rows"], r["grad"] = r["grad"], self.grad
         return r
 
     def _replay_state(self):
-        return super()._replay_state() + ([self.counter] if self.place_on else [])
+        return super()._replay_state() + ([self.counter] if self.place_on else []) + ([self.rir_counter] if self.rir_on else [])
 
     # ---- bookkeeping carried by the packed vector -------------------------------------------------------------
     def set_wer_counts(self, errors: float, ref_words: float):
@@ -465,7 +506,7 @@ class PgdStepper(_StepperCore):
         out = {"grad": self.grad, "stats": self.stats}
         if logits_out is not None:
             out["logits"] = logits_out
-        if self.place_on:
+        if self.place_on or self.rir_on:
             r = self._placed_fwd_bwd(p, clean, labels, want_logits, out)
         else:
             r = self.model.fwd_bwd(clean, p, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)

@@ -2,8 +2,8 @@
 
     rows[b][i] = a_b * delta[(i + s_b) mod Lp]            shift s_b in [0, Lp), gain a_b > 0
 
-— a circular shift (Lp = L), a tiling (Lp < L; the seam is not smoothed) or a window (Lp > L) of delta, at a playback level of
-its own.  The gradient of delta is the adjoint, a gather-sum over the per-clip gradient rows.  The three launches
+— a circular shift (Lp = L), a tiling (Lp < L; the seam is not smoothed, and a room response laid over the rows
+(training_utils/rir.py) convolves linearly across it, not circularly) or a window (Lp > L) of delta, at a playback level of its own.  The gradient of delta is the adjoint, a gather-sum over the per-clip gradient rows.  The three launches
 (``paa_place_draw`` / ``paa_place_rows`` / ``paa_place_reduce``) allocate nothing and the draw's step counter lives on the device,
 so a captured step draws anew on every replay.
 
@@ -176,12 +176,14 @@ class Placer:
                                                  _lib.ptr(self.rows), B, self.L, _lib.stream_ptr()))
         return self.rows[:B]
 
-    def reduce(self, B: int, grad):
+    def reduce(self, B: int, grad, grad_rows=None):
+        """``grad_rows``: gradient rows to reduce instead of this site's own (rir.Reverb.adjoint's)."""
         self._fits(B)
         if grad.numel() != self.Lp:
             raise ValueError(f"gradient buffer holds {grad.numel()} floats, expected {self.Lp}")
+        src = self.grad_rows if grad_rows is None else grad_rows
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().paa_place_reduce(_lib.ptr(self.grad_rows), _lib.ptr(self.shift), _lib.ptr(self.gain),
+            _lib.check(_lib.lib().paa_place_reduce(_lib.ptr(src), _lib.ptr(self.shift), _lib.ptr(self.gain),
                                                    _lib.ptr(grad), B, self.L, self.Lp, _lib.stream_ptr()))
 
 

@@ -13,7 +13,7 @@ import torch
 
 from .. import _lib, runtime
 from ..core import loss_helpers
-from . import place
+from . import place, rir
 from .pgd import FREQ_NORMS, PgdStepper, adam_unsupported
 
 logger = logging.getLogger(__name__)
@@ -152,6 +152,7 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
         raise NotImplementedError("masking_loss_alpha > 0 needs the device step: use the defaults of torch.optim.Adam(lr=...) "
                                   "or --optimizer_type pgd")
     place.check(args, L, Lp, eager_adam)
+    rir.check(args, eager_adam)
     mask_scores = []
     canon = None if eager_adam else device_wer_canon(args, processor, wer_metric, "train_epoch")
     if eager_adam and getattr(args, "device_wer", False):
@@ -164,6 +165,8 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
         model._stepper = stepper
         if stepper.place_on:          # a resumed run goes on drawing where the epochs before it stopped, not from step 0 again
             stepper.set_place_step(int(epoch) * len(train_data_loader))
+        if stepper.rir_on:            # the same for the room draw's counter
+            stepper.set_rir_step(int(epoch) * len(train_data_loader))
     if canon is not None:
         return _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alpha)
     for clean_audio, target_texts in train_data_loader:
