@@ -302,6 +302,31 @@ paa_status paa_model_forward(paa_model* m, const float* d_clean, const float* d_
 paa_status paa_model_forward_rows(paa_model* m, const float* d_clean, const float* d_p, int p_rows, int clamp,
                                   const int32_t* d_labels, int B, int S_max, float* d_logits, float* d_stats, void* stream);
 
+/* ---- true clip lengths (extension) ----------------------------------------------------------------------------
+ * Every clip is cropped or right-zero-padded to the model's length L.  With lengths set, the model computes what HuggingFace's
+ * Wav2Vec2ForCTC(input_values, attention_mask, labels) computes for clips of len_b in [400, L] samples, T_b = feat_len(len_b):
+ *   compose   perturbed[b][i] = clamp(clean[b][i] + p[..][i], -1, 1) for i < len_b and exactly 0 beyond (clamp = 0: the plain sum
+ *             under the same mask); the input gradient gets no term from i >= len_b (row b, or the sum over b)
+ *   frames    rows t >= T_b of the feature projection's output are zeroed before the positional conv, and their gradient dropped
+ *   attention keys >= T_b of clip b get probability 0 in every layer; ctx and dqkv rows >= T_b are zeros
+ *   CTC       input_length = T_b; dlogits rows >= T_b are zero; an infeasible label row gives +inf as without lengths
+ *   outputs   rows >= T_b of d_logits are zeros
+ * d_lengths: device pointer to max_batch int32 entries, or NULL to switch the mode off (then every result is bit-identical to a
+ * model that never had lengths).  The pointer is KEPT; its contents are read on the stream by every later
+ * paa_model_fwd_bwd{,_rows} / paa_model_forward{,_rows} call, so a replayed graph follows the buffer.  The caller validates the
+ * values; the device additionally clamps len_b to [0, L] and T_b to [1, T_e], so no value can index out of bounds.  Only the
+ * fused attention path (head dim 64) supports lengths: PAA_ERR_ARG elsewhere.  Not itself capturable (it changes what later
+ * calls launch); an addition to ABI 350. */
+paa_status paa_model_set_lengths(paa_model* m, const int32_t* d_lengths);
+/* d_out (B) int32 = T_b of the current length buffer, on the stream; PAA_ERR_ARG when no lengths are set. */
+paa_status paa_model_frame_counts(paa_model* m, int B, int32_t* d_out, void* stream);
+/* paa_argmax_ids on (B, T, V) logits with per-clip frame counts d_frames (B, clamped to [1, T] on the device): frames
+ * t >= d_frames[b] get the id `blank`, so the greedy decode and paa_wer_counts see T_b frames of clip b. */
+paa_status paa_argmax_ids_len(const float* d_logits, int B, int T, int V, const int32_t* d_frames, int blank, int16_t* d_ids,
+                              void* stream);
+/* d_p[r][i] = 0 for i >= d_lengths[r] (clamped to [0, L]), r < rows: the tail of a per-clip perturbation row beyond its clip. */
+paa_status paa_mask_tail_rows(float* d_p, int rows, int L, const int32_t* d_lengths, void* stream);
+
 /* core/loss_helpers.py:26,61  pred_ids = torch.argmax(logits, dim=-1): d_logits (rows, V) f32 -> d_ids (rows) int16
  * (first maximum wins; a NaN counts as the maximum, as in torch).  Feeds the host-side greedy CTC decode / WER. */
 paa_status paa_argmax_ids(const float* d_logits, int64_t rows, int V, int16_t* d_ids, void* stream);
@@ -371,6 +396,18 @@ paa_status paa_attn_fwd_split(const void* qkv_hi, const void* qkv_lo, void* ctx_
 paa_status paa_attn_bwd_split(const void* qkv_hi, const void* qkv_lo, const void* ctx_hi, const void* ctx_lo, const float* lse,
                               const void* dctx_hi, const void* dctx_lo, float* delta, void* dqkv_hi, void* dqkv_lo,
                               int B, int T, int P, int Tp, int H, int nh, void* stream);
+/* The four entries above with a per-clip key count d_klen (device, B int32, clamped to [1, T] on the device; NULL = the entries
+ * above, bit for bit).  Rows < d_klen[b] of clip b's ctx / lse / delta / dqkv are what the entries above write for that clip alone
+ * at T = d_klen[b], bit for bit; rows [d_klen[b], T) of ctx and dqkv are zero bits; lse / delta there are not written. */
+paa_status paa_attn_fwd_len(const void* qkv, void* ctx, float* lse, const int32_t* d_klen, int B, int T, int P, int Tp, int H,
+                            int nh, void* stream);
+paa_status paa_attn_bwd_len(const void* qkv, const void* ctx, const float* lse, const void* dctx, float* delta, void* dqkv,
+                            const int32_t* d_klen, int B, int T, int P, int Tp, int H, int nh, void* stream);
+paa_status paa_attn_fwd_split_len(const void* qkv_hi, const void* qkv_lo, void* ctx_hi, void* ctx_lo, float* lse,
+                                  const int32_t* d_klen, int B, int T, int P, int Tp, int H, int nh, void* stream);
+paa_status paa_attn_bwd_split_len(const void* qkv_hi, const void* qkv_lo, const void* ctx_hi, const void* ctx_lo, const float* lse,
+                                  const void* dctx_hi, const void* dctx_lo, float* delta, void* dqkv_hi, void* dqkv_lo,
+                                  const int32_t* d_klen, int B, int T, int P, int Tp, int H, int nh, void* stream);
 paa_status paa_layernorm_fwd(const float* x, const float* g, const float* b, float* y, float* stats,
                              int rows, int cols, float eps, void* stream);
 paa_status paa_layernorm_bwd(const float* dy, const float* x, const float* g, const float* stats, float* dx,
@@ -380,6 +417,15 @@ paa_status paa_softmax_bwd(float* dp, const float* p, int rows, int cols, int ld
 paa_status paa_ctc(const float* logits, const int32_t* labels, int B, int T, int V, int S_max, int blank,
                    float grad_scale, float* nll /* B */, float* dlogits /* may be NULL */, float* work, void* stream);
 int64_t paa_ctc_work_floats(int B, int T, int V, int S_max);
+/* paa_ctc with a per-clip frame count d_frames (device, B int32, clamped to [1, T] on the device; NULL = paa_ctc): clip b aligns
+ * over its first d_frames[b] frames — nll[b] and dlogits rows < d_frames[b] are what paa_ctc gives for that clip alone at
+ * T = d_frames[b], bit for bit — and dlogits rows beyond are zero.  The work buffer is sized for T (paa_ctc_work_floats). */
+paa_status paa_ctc_len(const float* logits, const int32_t* labels, const int32_t* d_frames, int B, int T, int V, int S_max,
+                       int blank, float grad_scale, float* nll /* B */, float* dlogits /* may be NULL */, float* work, void* stream);
+/* rows [d_frames[b], T) of clip b of x (B, P, cols) f32 (nullable) and of its bf16 planes (hi, lo, il as below; nullable) become
+ * zero; cols % 4 == 0 (il: % 32), P >= T. */
+paa_status paa_zero_frames(float* x, void* hi, void* lo, int il, const int32_t* d_frames, int B, int T, int P, int cols,
+                           void* stream);
 /* The row kernels above with every option the model passes them.  A set of bf16 planes of an f32 result v is given as
  * (hi, lo, il): hi = bf16(v) round-to-nearest-even, lo = bf16(v - hi) (nullable: hi plane only), both uint16 arrays of the
  * result's shape; il != 0: ONE array of twice the elements at hi holds both planes interleaved per 32-element group,

@@ -136,6 +136,17 @@ _SIGS = {
     "paa_softmax_bwd_mats": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "paa_ctc_padded": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 6),
     "paa_mul_gelu_grad_planes": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_void_p]),
+    # true clip lengths
+    "paa_model_set_lengths": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "paa_model_frame_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "paa_argmax_ids_len": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "paa_mask_tail_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "paa_attn_fwd_len": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
+    "paa_attn_bwd_len": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 6 + [C.c_void_p]),
+    "paa_attn_fwd_split_len": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p]),
+    "paa_attn_bwd_split_len": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 6 + [C.c_void_p]),
+    "paa_ctc_len": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float] + [C.c_void_p] * 4),
+    "paa_zero_frames": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
 }
 
 _lib = None

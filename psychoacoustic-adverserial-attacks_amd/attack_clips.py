@@ -21,13 +21,14 @@ import torch
 
 from .core import iso, loss_helpers
 from .core.masking import masking_loss
-from .training_utils import build, parser, place, rir, save
+from .training_utils import build, parser, pgd, place, rir, save
 from .training_utils.clip_attack import ClipStepper, clip_nll, compose_rows, init_rows, project_rows
 
 SPLITS = ("test", "val", "train")
 RECORD_FIELDS = ("index", "clean_wer", "adv_wer", "clean_ctc", "final_ctc", "l2", "linf", "snr_db")
 TARGET_FIELD = "target_wer"
 MASK_FIELD = "final_masking_loss"          # l_b(delta_b) of the finished perturbation (masking_loss_alpha > 0 only)
+LENGTH_FIELD = "length"                     # the clip's true sample count (--clip_lengths true only)
 SUMMARY_FIELDS = ("clean_wer", "adv_wer", "final_ctc", "l2", "linf", "snr_db")
 
 
@@ -39,17 +40,20 @@ def create_arg_parser():
 
 
 def clip_batches(batches, rank: int = 0, world: int = 1):
-    """Global batches (x (n, L), texts) of a split -> this rank's shards as (x, texts, global clip indices).  The index of a
-    clip is its position in the split, whatever the batch size or the number of ranks."""
+    """Global batches (x (n, L), texts[, lengths]) of a split -> this rank's shards as (x, texts, global clip indices[,
+    lengths]).  The index of a clip is its position in the split, whatever the batch size or the number of ranks."""
     tagged, first = [], 0
-    for x, texts in batches:
+    for batch in batches:
+        x, texts, lengths = pgd.unpack_batch(batch)
         idx = list(range(first, first + len(texts)))
         first += len(texts)
-        tagged.append((x, list(zip(idx, texts))))
+        tagged.append((x, list(zip(idx, texts))) if lengths is None else (x, list(zip(idx, texts)), lengths))
     out = []
-    for x, pairs in build.shard_batches(tagged, rank, world, keep_empty=True):
+    for shard in build.shard_batches(tagged, rank, world, keep_empty=True):
+        x, pairs, lengths = pgd.unpack_batch(shard)
         if len(pairs):
-            out.append((x, [t for _, t in pairs], [i for i, _ in pairs]))
+            item = (x, [t for _, t in pairs], [i for i, _ in pairs])
+            out.append(item if lengths is None else item + (lengths,))
     return out
 
 
@@ -94,7 +98,7 @@ def _wer(pred, ref):
     return e / max(w, 1)
 
 
-def _device_wers(args, processor, logits, texts):
+def _device_wers(args, processor, logits, texts, frames=None, blank=0):
     """Per-clip WER of ``logits`` against ``texts`` from the on-device counters (--device_wer): one (B, 3) readback.  None when
     the device route does not apply (flag off, multi-character vocabulary, a reference over the row cap): host path."""
     from .training_utils.train import device_wer_canon, log_host_route
@@ -105,42 +109,56 @@ def _device_wers(args, processor, logits, texts):
     if refs is None:
         log_host_route("attack_clips", f"a reference needs more than {loss_helpers.R_CAP} entries")
         return None
-    return [e / max(w, 1) for e, w, _ in loss_helpers.wer_counts_device(logits, refs, canon).cpu().tolist()]
+    return [e / max(w, 1) for e, w, _ in loss_helpers.wer_counts_device(logits, refs, canon, frames=frames, blank=blank).cpu().tolist()]
 
 
-def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper=None):
-    """Attack one batch of clips (x (B, L) on the device) and return (records, delta, adversarial waveforms)."""
+def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper=None, lengths=None):
+    """Attack one batch of clips (x (B, L) on the device) and return (records, delta, adversarial waveforms).  ``lengths``
+    (--clip_lengths true): the clips' true sample counts — the model masks the padding, delta_b[len_b:] stays zero, and the
+    record's norms and SNR are those of delta_b[:len_b] against x_b[:len_b]."""
     B, L = x.shape
     labels = loss_helpers.make_labels(texts, processor, args, B)
     delta = torch.from_numpy(init_rows(L, idx, int(args.seed))).to(x.device)
-    project_rows(delta, x, args, interp, spl_thresh)                      # build.py:301-304, per clip
+    frames, blank = None, int(model.arch.pad_token_id)
+    if lengths is not None:
+        lengths = model.check_lengths(lengths, B)
+        model.set_lengths(lengths)
+        frames = model.frame_counts(B)
+    elif model.lengths_on:
+        model.set_lengths(None)
+    project_rows(delta, x, args, interp, spl_thresh, lengths)             # build.py:301-304, per clip
     if args.optimizer_type == "adam":
         optimizer = torch.optim.Adam([delta], lr=args.lr)
         stepper = ClipStepper(model, args, L, interp, spl_thresh, optimizer=optimizer)
     elif stepper is None:
         stepper = ClipStepper(model, args, L, interp, spl_thresh)
     for _ in range(int(args.pgd_steps)):
-        stepper.step(delta.data, x, labels, want_logits=False)
+        stepper.step(delta.data, x, labels, want_logits=False)          # reads the model's length buffer, set above
     delta = delta.detach()
     clean_out = model.forward(x, None, labels)
     adv_out = model.forward(x, delta, labels, clamp=True)
-    clean_nll = clip_nll(model, clean_out["logits"], labels).cpu()
-    adv_nll = clip_nll(model, adv_out["logits"], labels).cpu()
+    clean_nll = clip_nll(model, clean_out["logits"], labels, frames).cpu()
+    adv_nll = clip_nll(model, adv_out["logits"], labels, frames).cpu()
     refs = loss_helpers.clean_transcripts(texts)
     target = loss_helpers.clean_transcripts([" ".join([args.target] * args.target_reps)])[0]
     targeted = args.attack_mode == "targeted"
-    clean_w, adv_w = _device_wers(args, processor, clean_out["logits"], texts), _device_wers(args, processor, adv_out["logits"], texts)
-    target_w = _device_wers(args, processor, adv_out["logits"], [target] * B) if targeted else None
+    dw = lambda logits, refs_: _device_wers(args, processor, logits, refs_, frames, blank)
+    clean_w, adv_w = dw(clean_out["logits"], texts), dw(adv_out["logits"], texts)
+    target_w = dw(adv_out["logits"], [target] * B) if targeted else None
     if clean_w is None or adv_w is None or (targeted and target_w is None):
-        clean_pred, _ = loss_helpers.wer_texts(clean_out["logits"], texts, processor)
-        adv_pred, _ = loss_helpers.wer_texts(adv_out["logits"], texts, processor)
+        clean_pred, _ = loss_helpers.wer_texts(clean_out["logits"], texts, processor, frames, blank)
+        adv_pred, _ = loss_helpers.wer_texts(adv_out["logits"], texts, processor, frames, blank)
         clean_w = [_wer(clean_pred[b], refs[b].lower()) for b in range(B)]
         adv_w = [_wer(adv_pred[b], refs[b].lower()) for b in range(B)]
         target_w = [_wer(adv_pred[b], target.lower()) for b in range(B)] if targeted else None
-    l2 = delta.norm(dim=1).cpu()
-    linf = delta.abs().amax(dim=1).cpu()
-    sig = x.double().pow(2).sum(dim=1).cpu()
-    noise = delta.double().pow(2).sum(dim=1).cpu()
+    dm, xm = delta, x
+    if lengths is not None:          # the norms and the SNR of delta_b[:len_b] against x_b[:len_b]
+        keep = torch.arange(L, device=x.device)[None, :] < lengths.to(x.device)[:, None]
+        dm, xm = delta * keep, x * keep
+    l2 = dm.norm(dim=1).cpu()
+    linf = dm.abs().amax(dim=1).cpu()
+    sig = xm.double().pow(2).sum(dim=1).cpu()
+    noise = dm.double().pow(2).sum(dim=1).cpu()
     mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
     mloss = masking_loss(delta, x, args)[0].cpu() if mask_alpha > 0 else None
     records = []
@@ -152,13 +170,16 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
             rec[TARGET_FIELD] = target_w[b]
         if mloss is not None:
             rec[MASK_FIELD] = float(mloss[b])
+        if lengths is not None:
+            rec[LENGTH_FIELD] = int(lengths[b])
         records.append(rec)
-    return records, delta, compose_rows(x, delta), stepper
+    return records, delta, compose_rows(x, delta, lengths), stepper
 
 
 def main(args) -> int:
     place.refuse_for_clips(args)
     rir.refuse_for_clips(args)
+    lengths_mode = pgd.check_clip_lengths(args)          # refusals of --clip_lengths true: before any launch or collective
     if not torch.cuda.is_available():
         raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")
     if not str(args.device).startswith("cuda"):
@@ -184,16 +205,21 @@ def main(args) -> int:
     spl_thresh = build.init_phon_threshold_tensor(args)
     batches, length = split_batches(args, world)
     mine = clip_batches(batches, rank, world)
-    model, processor = build.load_model(args, max_batch=max([len(t) for _, t, _ in mine] or [1]), length=length)
+    model, processor = build.load_model(args, max_batch=max([len(item[1]) for item in mine] or [1]), length=length)
     records, stepper = [], None
     n_wav = int(args.num_items_to_inspect)
-    for x, texts, idx in mine:
+    for item in mine:
+        x, texts, idx = item[:3]
+        lengths = item[3] if lengths_mode else None
+        if lengths_mode and len(item) < 4:
+            raise ValueError("--clip_lengths true needs loaders that yield (x, texts, lengths)")
         x = x.to(args.device, torch.float32).contiguous()
-        recs, _, adv, stepper = attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper)
+        recs, _, adv, stepper = attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper, lengths)
         records += recs
         for b, i in enumerate(idx):
-            if i < n_wav:
-                save.save_audio(os.path.join(args.save_dir, f"adv_clip{i}.wav"), adv[b], sample_rate=args.sr)
+            if i < n_wav:          # with true lengths the wav holds the clip's own len_b samples
+                wav = adv[b] if lengths is None else adv[b, : int(lengths[b])]
+                save.save_audio(os.path.join(args.save_dir, f"adv_clip{i}.wav"), wav, sample_rate=args.sr)
         if not getattr(args, "silent", False):
             print(f"[rank {rank}] clips {idx[0]}..{idx[-1]}: mean adv WER "
                   f"{sum(r['adv_wer'] for r in recs) / len(recs):.4f}, mean final CTC {sum(r['final_ctc'] for r in recs) / len(recs):.4f}",

@@ -75,13 +75,27 @@ def get_logits(batch_waveforms, processor, args, model):
     return model.forward(x.contiguous(), None, None)["logits"]
 
 
-def argmax_ids(logits: torch.Tensor) -> torch.Tensor:
-    """``torch.argmax(logits, dim=-1)`` (loss_helpers.py:26,61) through the C ABI: (..., V) f32 cuda -> (...) int16."""
-    from .. import _lib, runtime
+def _argmax_launch(x, ids, frames=None, blank=0):
+    """paa_argmax_ids on x (..., V) -> ids, or paa_argmax_ids_len on x (B, T, V) with ``frames`` (B) int32 on the device: the
+    frames t >= frames[b] of clip b get the id ``blank`` (true clip lengths)."""
+    from .. import _lib
+    with torch.cuda.device(x.device):
+        if frames is None:
+            _lib.check(_lib.lib().paa_argmax_ids(_lib.ptr(x), ids.numel(), x.shape[-1], _lib.ptr(ids), _lib.stream_ptr()))
+            return
+        if x.dim() != 3 or frames.dtype != torch.int32 or frames.device != x.device or frames.numel() < x.shape[0]:
+            raise ValueError(f"frames must be int32 ({x.shape[0]},) on the device of (B, T, V) logits")
+        _lib.check(_lib.lib().paa_argmax_ids_len(_lib.ptr(x), x.shape[0], x.shape[1], x.shape[2], _lib.ptr(frames), int(blank),
+                                                 _lib.ptr(ids), _lib.stream_ptr()))
+
+
+def argmax_ids(logits: torch.Tensor, frames=None, blank=0) -> torch.Tensor:
+    """``torch.argmax(logits, dim=-1)`` (loss_helpers.py:26,61) through the C ABI: (..., V) f32 cuda -> (...) int16.  With
+    ``frames`` (per-clip frame counts), frames beyond a clip's end decode as ``blank``."""
+    from .. import runtime
     x = runtime.as_f32_cuda(logits, "logits")
     ids = torch.empty(x.shape[:-1], dtype=torch.int16, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().paa_argmax_ids(_lib.ptr(x), ids.numel(), x.shape[-1], _lib.ptr(ids), _lib.stream_ptr()))
+    _argmax_launch(x, ids, frames, blank)
     return ids
 
 
@@ -117,10 +131,10 @@ def wer_counts(pred_texts, ref_texts):
     return errs, sum(len(r.split()) for r in ref_texts)
 
 
-def wer_texts(logits, target_texts, processor):
+def wer_texts(logits, target_texts, processor, frames=None, blank=0):
     """The two string lists loss_helpers.py:26-30 hands to the WER metric: greedy CTC decode of ``logits`` and the cleaned
-    references, both lower-cased."""
-    pred_ids = argmax_ids(logits)
+    references, both lower-cased.  ``frames`` / ``blank`` as ``argmax_ids``."""
+    pred_ids = argmax_ids(logits, frames, blank)
     if processor is not None:
         pred_texts = processor.batch_decode(pred_ids.long().cpu(), skip_special_tokens=True)
     else:
@@ -128,9 +142,9 @@ def wer_texts(logits, target_texts, processor):
     return [p.strip().lower() for p in pred_texts], [t.lower() for t in clean_transcripts(target_texts)]
 
 
-def compute_wer(logits, target_texts, processor, wer_metric):
+def compute_wer(logits, target_texts, processor, wer_metric, frames=None, blank=0):
     """loss_helpers.py:25-32."""
-    pred_texts, ref_texts = wer_texts(logits, target_texts, processor)
+    pred_texts, ref_texts = wer_texts(logits, target_texts, processor, frames, blank)
     if wer_metric is not None:
         return wer_metric.compute(predictions=pred_texts, references=ref_texts)
     e, w = wer_counts(pred_texts, ref_texts)
@@ -205,12 +219,12 @@ def encode_refs(target_texts, r_cap: int = None):
     return out.pin_memory() if torch.cuda.is_available() else out
 
 
-def wer_counts_device(logits_or_ids, refs, canon, out=None, sums=None, ids_out=None):
+def wer_counts_device(logits_or_ids, refs, canon, out=None, sums=None, ids_out=None, frames=None, blank=0):
     """Per-clip (errors, reference words, hypothesis words) as an int32 (B, 3) device tensor, with no host round trip:
     ``paa_argmax_ids`` (when given (B, T, V) float logits; int16 (B, T) ids are used as they are) then ``paa_wer_counts``.
     ``refs`` (B, r_cap) int32 and ``canon`` (V) int32 live on the device of the logits (a CPU tensor is copied there).
     ``out`` / ``sums`` (2 floats: sum of errors, sum of reference words) / ``ids_out`` are caller-owned buffers: with all of them
-    given the call allocates nothing and is graph-capturable."""
+    given the call allocates nothing and is graph-capturable.  ``frames`` / ``blank`` (logits only) as ``argmax_ids``."""
     from .. import _lib, runtime
     x = logits_or_ids
     dev = x.device
@@ -225,8 +239,7 @@ def wer_counts_device(logits_or_ids, refs, canon, out=None, sums=None, ids_out=N
         ids = ids_out if ids_out is not None else torch.empty(x.shape[:2], dtype=torch.int16, device=dev)
         if ids.dtype != torch.int16 or ids.numel() != x.shape[0] * x.shape[1] or ids.device != dev:
             raise ValueError("ids_out must hold B x T int16 on the device of the logits")
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().paa_argmax_ids(_lib.ptr(x), ids.numel(), x.shape[-1], _lib.ptr(ids), _lib.stream_ptr()))
+        _argmax_launch(x, ids, frames, blank)
     B, T = x.shape[0], x.shape[1]
     refs = refs.to(dev, non_blocking=True)
     canon = canon.to(dev, non_blocking=True)

@@ -160,6 +160,24 @@ __device__ __forceinline__ void store_own_s(unsigned short* __restrict__ dh, uns
         }
 }
 
+// Per-clip key count (AttnArgs::klen, nullable): clip b attends over its first klen[b] positions only, clamped to [1, T] so a
+// bad entry cannot index out of bounds.  One scalar load per workgroup; null = a.T for every clip (the mask-free model).
+__device__ __forceinline__ int attn_klen(const AttnArgs& a, int b) {
+    if (!a.klen) return a.T;
+    const int v = a.klen[b];
+    return v < 1 ? 1 : (v > a.T ? a.T : v);
+}
+// zero bits for the 64 columns of own-position `row` in the hi (and lo) plane: the rows [klen, T) of a clip
+template <int PREC>
+__device__ __forceinline__ void zero_own_s(unsigned short* __restrict__ dh, unsigned short* __restrict__ dl, int64_t ld, int row, int lh) {
+#pragma unroll
+    for (int g8 = 0; g8 < 8; ++g8) {
+        const int d = 8 * g8 + 4 * lh;
+        *reinterpret_cast<uint2*>(dh + (int64_t)row * ld + d) = make_uint2(0u, 0u);
+        if constexpr (PREC) *reinterpret_cast<uint2*>(dl + (int64_t)row * ld + d) = make_uint2(0u, 0u);
+    }
+}
+
 // ------------------------------------------------------------------------------------------ forward
 // 64 keys per iteration (two 32-key score tiles), K / V tiles double-buffered in LDS and prefetched through registers:
 // one barrier per 64 keys, 16 (x3 in split mode) MFMAs per wave between barriers.
@@ -173,7 +191,13 @@ __global__ __launch_bounds__(256, 2) void k_attn_fwd(AttnArgs a) {
     const int b = bh / a.nh, h = bh - b * a.nh;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, lh = lane >> 5;
     const int q = oblk * 128 + wave * 32 + lr;
-    const int qc = q < a.T ? q : a.T - 1;
+    const int T = attn_klen(a, b);                   // keys (and live queries) of this clip
+    const int64_t co = (int64_t)b * a.P * a.H + h * AT_D;
+    if (oblk * 128 >= T) {                           // a block of queries past the clip's end: zero ctx rows, no work
+        if (q < a.T) zero_own_s<PREC>(a.ctx + co, PREC ? a.ctx_lo + co : nullptr, a.H, q, lh);
+        return;
+    }
+    const int qc = q < T ? q : T - 1;
     const int64_t ld = 3 * (int64_t)a.H;
     const int64_t hoff = (int64_t)b * a.P * ld + h * AT_D;
     const unsigned short* base[2] = {a.qkv + hoff, PREC ? a.qkv_lo + hoff : nullptr};
@@ -185,13 +209,13 @@ __global__ __launch_bounds__(256, 2) void k_attn_fwd(AttnArgs a) {
     f32x16 o[2];
 #pragma unroll
     for (int e = 0; e < 16; ++e) { o[0][e] = 0.f; o[1][e] = 0.f; }
-    const int nt = (a.T + KT - 1) / KT;
+    const int nt = (T + KT - 1) / KT;
     uint4 rk[NPL][KT / 32], rv[NPL][KT / 32];
     auto tload = [&](int kt) {
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) {
-            tile_load<KT>(base[pl] + a.H, ld, kt * KT, a.T, rk[pl]);
-            tile_load<KT>(base[pl] + 2 * a.H, ld, kt * KT, a.T, rv[pl]);
+            tile_load<KT>(base[pl] + a.H, ld, kt * KT, T, rk[pl]);
+            tile_load<KT>(base[pl] + 2 * a.H, ld, kt * KT, T, rv[pl]);
         }
     };
     auto tstore = [&](int buf) {
@@ -221,13 +245,13 @@ __global__ __launch_bounds__(256, 2) void k_attn_fwd(AttnArgs a) {
         // raised — and l, O rescaled — when some row of the wave exceeds it by more than 2^8: exp2 of a bounded
         // positive excess is harmless in f32 / bf16 and the per-tile rescale of the 32 O registers mostly disappears.
         float mx = -INFINITY;
-        if (kt + 1 == nt) {                                  // the only tile that can hold keys >= T (zero-filled rows)
+        if (kt + 1 == nt) {                                  // the tile that holds T: the only one with keys >= T (zero-filled rows)
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int key = kt * KT + u * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                    if (key >= a.T) s[u][e] = -INFINITY;
+                    if (key >= T) s[u][e] = -INFINITY;
                 }
         }
 #pragma unroll
@@ -267,10 +291,11 @@ __global__ __launch_bounds__(256, 2) void k_attn_fwd(AttnArgs a) {
         if (kt + 1 < nt) tstore((kt + 1) & 1);
         __syncthreads();
     }
-    if (q < a.T) {
-        const int64_t co = (int64_t)b * a.P * a.H + h * AT_D;
+    if (q < T) {
         store_own_s<PREC>(a.ctx + co, PREC ? a.ctx_lo + co : nullptr, a.H, q, lh, o, 1.f / l);
         if (lh == 0) a.lse[(int64_t)bh * a.Tp + q] = m + log2f(l);
+    } else if (q < a.T) {                            // queries past the clip's end inside its last block
+        zero_own_s<PREC>(a.ctx + co, PREC ? a.ctx_lo + co : nullptr, a.H, q, lh);
     }
 }
 
@@ -286,9 +311,14 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(AttnArgs a) {
     const int b = bh / a.nh, h = bh - b * a.nh;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, lh = lane >> 5;
     const int q = oblk * 128 + wave * 32 + lr;
-    const int qc = q < a.T ? q : a.T - 1;
+    const int T = attn_klen(a, b);
     const int64_t ld = 3 * (int64_t)a.H;
     const int64_t hoff = (int64_t)b * a.P * ld + h * AT_D, coff = (int64_t)b * a.P * a.H + h * AT_D;
+    if (oblk * 128 >= T) {                           // queries past the clip's end: zero dQ rows
+        if (q < a.T) zero_own_s<PREC>(a.dqkv + hoff, PREC ? a.dqkv_lo + hoff : nullptr, ld, q, lh);
+        return;
+    }
+    const int qc = q < T ? q : T - 1;
     const unsigned short* base[2] = {a.qkv + hoff, PREC ? a.qkv_lo + hoff : nullptr};
     const unsigned short* dob[2] = {a.dctx + coff, PREC ? a.dctx_lo + coff : nullptr};
     const unsigned short* ob[2] = {a.ctx + coff, PREC ? a.ctx_lo + coff : nullptr};
@@ -313,18 +343,18 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(AttnArgs a) {
     }
     delta += __shfl_xor(delta, 32, 64);
     const float lse = a.lse[(int64_t)bh * a.Tp + qc];
-    if (q < a.T && lh == 0) a.delta[(int64_t)bh * a.Tp + q] = delta;
+    if (q < T && lh == 0) a.delta[(int64_t)bh * a.Tp + q] = delta;
     const float c = a.scale * 1.44269504088896341f;
     f32x16 dq[2];
 #pragma unroll
     for (int e = 0; e < 16; ++e) { dq[0][e] = 0.f; dq[1][e] = 0.f; }
-    const int nt = (a.T + 31) / 32;
+    const int nt = (T + 31) / 32;
     uint4 rk[NPL][1], rv[NPL][1];
     auto tload = [&](int kt) {
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) {
-            tile_load<32>(base[pl] + a.H, ld, kt * 32, a.T, rk[pl]);
-            tile_load<32>(base[pl] + 2 * a.H, ld, kt * 32, a.T, rv[pl]);
+            tile_load<32>(base[pl] + a.H, ld, kt * 32, T, rk[pl]);
+            tile_load<32>(base[pl] + 2 * a.H, ld, kt * 32, T, rv[pl]);
         }
     };
     auto tstore = [&](int buf) {
@@ -354,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(AttnArgs a) {
         if (kt + 1 == nt) {                                  // keys >= T: zero-filled K rows would give p = exp2(-lse)
 #pragma unroll
             for (int e = 0; e < 16; ++e)
-                if (kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh >= a.T) ds[e] = 0.f;
+                if (kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh >= T) ds[e] = 0.f;
         }
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
@@ -371,7 +401,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(AttnArgs a) {
         if (kt + 1 < nt) tstore((kt + 1) & 1);
         __syncthreads();
     }
-    if (q < a.T) store_own_s<PREC>(a.dqkv + hoff, PREC ? a.dqkv_lo + hoff : nullptr, ld, q, lh, dq, a.scale);
+    if (q < T) store_own_s<PREC>(a.dqkv + hoff, PREC ? a.dqkv_lo + hoff : nullptr, ld, q, lh, dq, a.scale);
+    else if (q < a.T) zero_own_s<PREC>(a.dqkv + hoff, PREC ? a.dqkv_lo + hoff : nullptr, ld, q, lh);
 }
 
 // ---------------------------------------------------------------------------------- backward: dK, dV
@@ -387,9 +418,17 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv(AttnArgs a) {
     const int b = bh / a.nh, h = bh - b * a.nh;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, lh = lane >> 5;
     const int key = oblk * 128 + wave * 32 + lr;
-    const int kc = key < a.T ? key : a.T - 1;
+    const int T = attn_klen(a, b);
     const int64_t ld = 3 * (int64_t)a.H;
     const int64_t hoff = (int64_t)b * a.P * ld + h * AT_D, coff = (int64_t)b * a.P * a.H + h * AT_D;
+    if (oblk * 128 >= T) {                           // keys past the clip's end: zero dK / dV rows
+        if (key < a.T) {
+            zero_own_s<PREC>(a.dqkv + hoff + a.H, PREC ? a.dqkv_lo + hoff + a.H : nullptr, ld, key, lh);
+            zero_own_s<PREC>(a.dqkv + hoff + 2 * a.H, PREC ? a.dqkv_lo + hoff + 2 * a.H : nullptr, ld, key, lh);
+        }
+        return;
+    }
+    const int kc = key < T ? key : T - 1;
     const unsigned short* base[2] = {a.qkv + hoff, PREC ? a.qkv_lo + hoff : nullptr};
     const unsigned short* dob[2] = {a.dctx + coff, PREC ? a.dctx_lo + coff : nullptr};
     bf16x8 kf[NPL][4], vf[NPL][4];
@@ -402,19 +441,19 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv(AttnArgs a) {
     f32x16 dk[2], dv[2];
 #pragma unroll
     for (int e = 0; e < 16; ++e) { dk[0][e] = 0.f; dk[1][e] = 0.f; dv[0][e] = 0.f; dv[1][e] = 0.f; }
-    const int nt = (a.T + 31) / 32;
+    const int nt = (T + 31) / 32;
     uint4 rq[NPL][1], rdo[NPL][1];
     float rl = INFINITY, rd = 0.f;               // lse / delta of query threadIdx.x of the tile (threads 0..31)
     auto tload = [&](int qt) {
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) {
-            tile_load<32>(base[pl], ld, qt * 32, a.T, rq[pl]);
-            tile_load<32>(dob[pl], a.H, qt * 32, a.T, rdo[pl]);
+            tile_load<32>(base[pl], ld, qt * 32, T, rq[pl]);
+            tile_load<32>(dob[pl], a.H, qt * 32, T, rdo[pl]);
         }
         if (threadIdx.x < 32) {
             const int qq = qt * 32 + threadIdx.x;
-            rl = qq < a.T ? a.lse[(int64_t)bh * a.Tp + qq] : INFINITY;     // exp2(-inf) = 0 for pad queries
-            rd = qq < a.T ? a.delta[(int64_t)bh * a.Tp + qq] : 0.f;
+            rl = qq < T ? a.lse[(int64_t)bh * a.Tp + qq] : INFINITY;     // exp2(-inf) = 0 for pad queries
+            rd = qq < T ? a.delta[(int64_t)bh * a.Tp + qq] : 0.f;
         }
     };
     auto tstore = [&](int buf) {
@@ -465,9 +504,12 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv(AttnArgs a) {
         if (qt + 1 < nt) tstore((qt + 1) & 1);
         __syncthreads();
     }
-    if (key < a.T) {
+    if (key < T) {
         store_own_s<PREC>(a.dqkv + hoff + a.H, PREC ? a.dqkv_lo + hoff + a.H : nullptr, ld, key, lh, dk, a.scale);
         store_own_s<PREC>(a.dqkv + hoff + 2 * a.H, PREC ? a.dqkv_lo + hoff + 2 * a.H : nullptr, ld, key, lh, dv, 1.f);
+    } else if (key < a.T) {
+        zero_own_s<PREC>(a.dqkv + hoff + a.H, PREC ? a.dqkv_lo + hoff + a.H : nullptr, ld, key, lh);
+        zero_own_s<PREC>(a.dqkv + hoff + 2 * a.H, PREC ? a.dqkv_lo + hoff + 2 * a.H : nullptr, ld, key, lh);
     }
 }
 
@@ -536,5 +578,44 @@ extern "C" paa_status paa_attn_bwd_split(const void* qkv_hi, const void* qkv_lo,
     a.dqkv = (unsigned short*)dqkv_hi; a.dqkv_lo = (unsigned short*)dqkv_lo;
     a.T = T; a.P = P; a.Tp = Tp; a.H = H; a.nh = nh; a.scale = 1.0f / sqrtf((float)(H / nh));
     if (!qkv_lo || !ctx_lo || !dctx_lo || !dqkv_lo) { paa::set_error("paa_attn_bwd_split: lo planes required"); return PAA_ERR_ARG; }
+    return paa::attn_bwd(a, B, H / nh, (hipStream_t)stream);
+}
+
+// The same four entries with a per-clip key count d_klen (device, B entries; null = the entries above).
+extern "C" paa_status paa_attn_fwd_len(const void* qkv, void* ctx, float* lse, const int32_t* d_klen, int B, int T, int P, int Tp,
+                                       int H, int nh, void* stream) {
+    paa::AttnArgs a{};
+    a.qkv = (const unsigned short*)qkv; a.ctx = (unsigned short*)ctx; a.lse = lse; a.klen = d_klen;
+    a.T = T; a.P = P; a.Tp = Tp; a.H = H; a.nh = nh; a.scale = 1.0f / sqrtf((float)(H / nh));
+    return paa::attn_fwd(a, B, H / nh, (hipStream_t)stream);
+}
+extern "C" paa_status paa_attn_bwd_len(const void* qkv, const void* ctx, const float* lse, const void* dctx, float* delta,
+                                       void* dqkv, const int32_t* d_klen, int B, int T, int P, int Tp, int H, int nh, void* stream) {
+    paa::AttnArgs a{};
+    a.qkv = (const unsigned short*)qkv; a.ctx = (unsigned short*)ctx; a.lse = (float*)lse;
+    a.dctx = (const unsigned short*)dctx; a.delta = delta; a.dqkv = (unsigned short*)dqkv; a.klen = d_klen;
+    a.T = T; a.P = P; a.Tp = Tp; a.H = H; a.nh = nh; a.scale = 1.0f / sqrtf((float)(H / nh));
+    return paa::attn_bwd(a, B, H / nh, (hipStream_t)stream);
+}
+extern "C" paa_status paa_attn_fwd_split_len(const void* qkv_hi, const void* qkv_lo, void* ctx_hi, void* ctx_lo, float* lse,
+                                             const int32_t* d_klen, int B, int T, int P, int Tp, int H, int nh, void* stream) {
+    paa::AttnArgs a{};
+    a.qkv = (const unsigned short*)qkv_hi; a.qkv_lo = (const unsigned short*)qkv_lo;
+    a.ctx = (unsigned short*)ctx_hi; a.ctx_lo = (unsigned short*)ctx_lo; a.lse = lse; a.klen = d_klen;
+    a.T = T; a.P = P; a.Tp = Tp; a.H = H; a.nh = nh; a.scale = 1.0f / sqrtf((float)(H / nh));
+    if (!qkv_lo || !ctx_lo) { paa::set_error("paa_attn_fwd_split_len: lo planes required"); return PAA_ERR_ARG; }
+    return paa::attn_fwd(a, B, H / nh, (hipStream_t)stream);
+}
+extern "C" paa_status paa_attn_bwd_split_len(const void* qkv_hi, const void* qkv_lo, const void* ctx_hi, const void* ctx_lo,
+                                             const float* lse, const void* dctx_hi, const void* dctx_lo, float* delta,
+                                             void* dqkv_hi, void* dqkv_lo, const int32_t* d_klen, int B, int T, int P, int Tp, int H,
+                                             int nh, void* stream) {
+    paa::AttnArgs a{};
+    a.qkv = (const unsigned short*)qkv_hi; a.qkv_lo = (const unsigned short*)qkv_lo;
+    a.ctx = (unsigned short*)ctx_hi; a.ctx_lo = (unsigned short*)ctx_lo; a.lse = (float*)lse;
+    a.dctx = (const unsigned short*)dctx_hi; a.dctx_lo = (const unsigned short*)dctx_lo; a.delta = delta;
+    a.dqkv = (unsigned short*)dqkv_hi; a.dqkv_lo = (unsigned short*)dqkv_lo; a.klen = d_klen;
+    a.T = T; a.P = P; a.Tp = Tp; a.H = H; a.nh = nh; a.scale = 1.0f / sqrtf((float)(H / nh));
+    if (!qkv_lo || !ctx_lo || !dctx_lo || !dqkv_lo) { paa::set_error("paa_attn_bwd_split_len: lo planes required"); return PAA_ERR_ARG; }
     return paa::attn_bwd(a, B, H / nh, (hipStream_t)stream);
 }

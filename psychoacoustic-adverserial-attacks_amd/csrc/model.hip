@@ -67,21 +67,81 @@ struct EncL {
     float* lse = nullptr;
 };
 
-__global__ void k_copy_logits(const float* __restrict__ src, float* __restrict__ dst, int B, int T, int P, int V) {
+// Per-clip frame count of the length mode (nullable array): clamped to [1, T], so a bad entry never indexes out of bounds.
+__device__ __forceinline__ int clip_frames(const int32_t* __restrict__ frames, int b, int T) {
+    if (!frames) return T;
+    const int v = frames[b];
+    return v < 1 ? 1 : (v > T ? T : v);
+}
+
+// frames (nullable): rows t >= frames[b] of clip b are written as zeros
+__global__ void k_copy_logits(const float* __restrict__ src, float* __restrict__ dst, int B, int T, int P, int V,
+                              const int32_t* __restrict__ frames) {
     const int64_t n = (int64_t)B * T * V;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int v = (int)(i % V);
         const int64_t r = i / V;
         const int t = (int)(r % T), b = (int)(r / T);
-        dst[i] = src[((int64_t)b * P + t) * V + v];
+        dst[i] = t < clip_frames(frames, b, T) ? src[((int64_t)b * P + t) * V + v] : 0.f;
+    }
+}
+
+// T_b = feat_len(len_b): the conv stack's output length for len_b samples (arch.feat_lengths; HF
+// _get_feat_extract_output_lengths), on the device so that a captured graph follows the length buffer.  len_b is clamped to
+// [0, L] and T_b to [1, T].
+struct FrameGeom { int n; int k[8], s[8]; };
+__global__ void k_frames_from_lengths(const int32_t* __restrict__ lens, int B, int L, int T, FrameGeom g,
+                                      int32_t* __restrict__ frames) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int len = lens[b];
+    len = len < 0 ? 0 : (len > L ? L : len);
+    for (int i = 0; i < g.n; ++i) len = len >= g.k[i] ? (len - g.k[i]) / g.s[i] + 1 : 0;
+    frames[b] = len < 1 ? 1 : (len > T ? T : len);
+}
+
+// rows [T_b, T) of clip b of an f32 (B, P, cols) buffer (nullable) and of its bf16 planes (hi / lo or interleaved; nullable)
+// become zero; cols % 4 == 0.  One 16-byte (f32) / 8-byte (plane) vector store per thread and step.
+__global__ void k_zero_frames(float* __restrict__ x, Bf xb, const int32_t* __restrict__ frames, int B, int T, int P, int cols) {
+    const int c4 = cols >> 2;
+    const int64_t n = (int64_t)B * T * c4;
+    const float z[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4);
+        const int64_t r = i / c4;
+        const int t = (int)(r % T), b = (int)(r / T);
+        if (t < clip_frames(frames, b, T)) continue;
+        const size_t e = ((size_t)b * P + t) * cols + 4 * (size_t)c;
+        if (x) *reinterpret_cast<float4*>(x + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+        store_bf16x4(xb, e, z);
+    }
+}
+paa_status zero_frames(float* x, Bf xb, const int32_t* frames, int B, int T, int P, int cols, hipStream_t st) {
+    hipLaunchKernelGGL(k_zero_frames, dim3(std::min(cdiv((int64_t)B * T * (cols >> 2), 256), 2048)), dim3(256), 0, st, x, xb, frames,
+                       B, T, P, cols);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
+// p[r][i] = 0 for i >= len_r (len_r clamped to [0, L]): the tail of a per-clip perturbation row beyond its clip's end
+__global__ void k_mask_tail_rows(float* __restrict__ p, int rows, int L, const int32_t* __restrict__ lens) {
+    const int64_t n = (int64_t)rows * L;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / L), l = (int)(i - (int64_t)r * L);
+        int len = lens[r];
+        len = len < 0 ? 0 : (len > L ? L : len);
+        if (l >= len) p[i] = 0.f;
     }
 }
 
 // greedy CTC ids (loss_helpers.py:26 / :61, torch.argmax(logits, -1)): one thread per frame, first maximum wins, a NaN
 // counts as the maximum (torch semantics)
-__global__ void k_argmax_ids(const float* __restrict__ x, int64_t rows, int V, int16_t* __restrict__ ids) {
+// T > 0 with frames: row r is frame r % T of clip r / T, and frames t >= frames[clip] get the id `blank`
+__global__ void k_argmax_ids(const float* __restrict__ x, int64_t rows, int V, int16_t* __restrict__ ids,
+                             const int32_t* __restrict__ frames, int T, int blank) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
+    if (frames && (int)(r % T) >= clip_frames(frames, (int)(r / T), T)) { ids[r] = (int16_t)blank; return; }
     const float* row = x + r * V;
     float best = row[0];
     int bi = 0;
@@ -152,6 +212,11 @@ struct paa_model {
     float *dxa, *dxb, *dctx = nullptr, *dP = nullptr, *dh0, *dfn, *delta = nullptr;
     Bf dctxH{nullptr, nullptr};
     int S_cap;
+    // length mode (paa_model_set_lengths): the caller's per-clip sample counts (device, Bmax entries; null = off) and the
+    // frame counts T_b derived from them on the stream at the start of every call
+    const int32_t* lens = nullptr;
+    int32_t* frames = nullptr;
+    const int32_t* fr() const { return lens ? frames : nullptr; }
 };
 
 static const float* find(paa_model* m, const std::string& n, int64_t numel, paa_status* st) {
@@ -346,6 +411,7 @@ extern "C" paa_status paa_model_create(paa_model** out, const paa_arch* arch, co
         if (m->fused) { m->dctxH = take_bf(MH); m->delta = take(LS); }
         else { m->dctx = take(MH); m->dP = take(PM); }
         m->dfpreH = take_bf(MF, m->ail); m->dposH = take_bf(MH); m->dh0 = take(MH); m->dh0H = take_bf(MH); m->dfn = take(MC);
+        m->frames = reinterpret_cast<int32_t*>(take(B));
         if (!pass) {
             m->arena_floats = off;
             hipError_t e = hipMalloc(&m->arena, sizeof(float) * off);
@@ -408,10 +474,18 @@ static paa_status forward(paa_model* m, const float* clean, const float* p, int 
     const paa_arch& a = m->a;
     const int nc = a.n_conv, H = a.hidden, F = a.ffn, V = a.vocab, nh = a.heads, hd = H / nh, G = a.pos_groups, Hg = H / G;
     const int M = B * m->P, T = m->T, P = m->P, Tp = m->Tp;
+    if (m->lens) {                      // length mode: T_b from the length buffer, on the stream
+        FrameGeom g{};
+        g.n = nc;
+        for (int i = 0; i < nc; ++i) { g.k[i] = a.conv_kernel[i]; g.s[i] = a.conv_stride[i]; }
+        hipLaunchKernelGGL(k_frames_from_lengths, dim3(cdiv(B, 64)), dim3(64), 0, st, m->lens, B, m->L, T, g, m->frames);
+        PAA_LAUNCH_CHECK();
+    }
     // ---- feature encoder ----
     {
         ConvL& c = m->conv[0];
         Conv0Args ca{};
+        ca.lens = m->lens;
         ca.clean = clean; ca.p = p; ca.p_ld = p_ld; ca.grad_rows = p_ld != 0; ca.clamp = clamp; ca.B = B; ca.L = m->L; ca.T = c.T; ca.P = c.P; ca.C = c.cout;
         ca.k = c.k; ca.stride = c.s; ca.w = c.w0; ca.bias = c.b; ca.gamma = c.g; ca.beta = c.beta; ca.eps = 1e-5f;
         ca.pre = c.pre; ca.pre16 = c.pre16; ca.gate = c.gate; ca.actb = c.actb; ca.gn_stats = m->gn_stats; ca.row_stats = c.row_stats;
@@ -444,6 +518,7 @@ static paa_status forward(paa_model* m, const float* clean, const float* p, int 
         d.bias = m->fp_b; d.row_period = P; d.row_valid = T;
         PAA_TRY(gemm(d, st));
     }
+    if (m->lens) PAA_TRY(zero_frames(m->h0, m->h0H, m->frames, B, T, P, H, st));      // HF: hidden_states[~attention_mask] = 0
     // ---- positional conv (grouped, k taps, zero padded in time per clip) + GELU + residual ----
     float* enc_in = a.stable_ln ? m->enc[0].ln1_in : m->hsum;
     {
@@ -478,7 +553,7 @@ static paa_status forward(paa_model* m, const float* clean, const float* p, int 
             PAA_TRY(linear(m, attn_in, e.wqkv, e.bqkv, nullptr, e.qkvH, M, 3 * H, H, st));
             AttnArgs aa{};
             aa.qkv = e.qkvH.hi; aa.ctx = e.ctxH.hi; aa.lse = e.lse; aa.qkv_lo = e.qkvH.lo; aa.ctx_lo = e.ctxH.lo;
-            aa.T = T; aa.P = P; aa.Tp = Tp; aa.H = H; aa.nh = nh; aa.scale = scale;
+            aa.T = T; aa.P = P; aa.Tp = Tp; aa.H = H; aa.nh = nh; aa.scale = scale; aa.klen = m->fr();
             PAA_TRY(attn_fwd(aa, B, hd, st));
             ctxH = ro(e.ctxH);
         } else {
@@ -554,7 +629,7 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
             AttnArgs aa{};
             aa.qkv = e.qkvH.hi; aa.ctx = e.ctxH.hi; aa.lse = e.lse; aa.dctx = m->dctxH.hi; aa.delta = m->delta; aa.dqkv = m->dqkvH.hi;
             aa.qkv_lo = e.qkvH.lo; aa.ctx_lo = e.ctxH.lo; aa.dctx_lo = m->dctxH.lo; aa.dqkv_lo = m->dqkvH.lo;
-            aa.T = T; aa.P = P; aa.Tp = Tp; aa.H = H; aa.nh = nh; aa.scale = scale;
+            aa.T = T; aa.P = P; aa.Tp = Tp; aa.H = H; aa.nh = nh; aa.scale = scale; aa.klen = m->fr();
             PAA_TRY(attn_bwd(aa, B, hd, st));
         } else {
         PAA_TRY(linear(m, ro(dx2H), e.wo_t, nullptr, m->dctx, NOBF, M, H, H, st));
@@ -610,6 +685,8 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
         d.residual = dx; d.ld_res = H; d.res_s1 = (int64_t)P * H; d.res_s2 = Hg;
         PAA_TRY(gemm(d, st));
     }
+    // length mode: the positional conv's dgrad spreads into the rows the forward pass zeroed; their gradient is dropped
+    if (m->lens) PAA_TRY(zero_frames(m->dh0, m->dh0H, m->frames, B, T, P, H, st));
     // ---- feature projection backward ----
     const ConvL& cl = m->conv[nc - 1];
     PAA_TRY(linear(m, ro(m->dh0H), m->fp_wt, nullptr, m->dfn, NOBF, M, cl.cout, H, st));
@@ -655,6 +732,7 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
     {
         ConvL& c = m->conv[0];
         Conv0Args ca{};
+        ca.lens = m->lens;
         ca.clean = clean; ca.p = p; ca.p_ld = p_ld; ca.grad_rows = p_ld != 0; ca.clamp = clamp; ca.B = B; ca.L = m->L; ca.T = c.T; ca.P = c.P; ca.C = c.cout;
         ca.k = c.k; ca.stride = c.s; ca.w = c.w0; ca.bias = c.b; ca.gamma = c.g; ca.beta = c.beta; ca.eps = 1e-5f;
         ca.gn_stats = m->gn_stats; ca.gn_bsums = m->gn_bsums; ca.row_stats = c.row_stats; ca.dpre = m->gF[0]; ca.G = m->G;
@@ -680,12 +758,12 @@ static paa_status fwd_bwd_impl(paa_model* m, const float* d_clean, const float* 
     const int V = m->a.vocab;
     if (d_logits) {
         hipLaunchKernelGGL(k_copy_logits, dim3(std::min(cdiv((int64_t)B * m->T * V, 256), 2048)), dim3(256), 0, st,
-                           (const float*)m->logits, d_logits, B, m->T, m->P, V);
+                           (const float*)m->logits, d_logits, B, m->T, m->P, V, m->fr());
         PAA_LAUNCH_CHECK();
     }
     if (d_labels) {
         PAA_TRY(ctc(m->logits, d_labels, B, m->T, m->P, V, S_max, m->a.blank, (float)direction, m->nll,
-                    d_grad ? m->dlogits : nullptr, d_grad ? m->dlogitsH : NOBF, m->ctc_work, st));
+                    d_grad ? m->dlogits : nullptr, d_grad ? m->dlogitsH : NOBF, m->ctc_work, st, m->fr()));
         if (d_stats) PAA_TRY(sum_small(m->nll, B, d_stats, st));
     }
     if (d_grad) PAA_TRY(backward(m, d_clean, d_p, p_ld, clamp, B, d_grad, st));
@@ -717,11 +795,11 @@ static paa_status forward_impl(paa_model* m, const float* d_clean, const float* 
     const int V = m->a.vocab;
     if (d_logits) {
         hipLaunchKernelGGL(k_copy_logits, dim3(std::min(cdiv((int64_t)B * m->T * V, 256), 2048)), dim3(256), 0, st,
-                           (const float*)m->logits, d_logits, B, m->T, m->P, V);
+                           (const float*)m->logits, d_logits, B, m->T, m->P, V, m->fr());
         PAA_LAUNCH_CHECK();
     }
     if (d_labels) {
-        PAA_TRY(ctc(m->logits, d_labels, B, m->T, m->P, V, S_max, m->a.blank, 1.f, m->nll, nullptr, NOBF, m->ctc_work, st));
+        PAA_TRY(ctc(m->logits, d_labels, B, m->T, m->P, V, S_max, m->a.blank, 1.f, m->nll, nullptr, NOBF, m->ctc_work, st, m->fr()));
         if (d_stats) PAA_TRY(sum_small(m->nll, B, d_stats, st));
     }
     return PAA_OK;
@@ -742,9 +820,57 @@ extern "C" paa_status paa_model_forward_rows(paa_model* m, const float* d_clean,
 extern "C" paa_status paa_argmax_ids(const float* d_logits, int64_t rows, int V, int16_t* d_ids, void* stream) {
     if (!d_logits || !d_ids) PAA_FAIL(PAA_ERR_ARG, "paa_argmax_ids: null argument");
     if (rows < 1 || V < 1 || V > 32767) PAA_FAIL(PAA_ERR_SIZE, "paa_argmax_ids: rows=%lld V=%d", (long long)rows, V);
-    hipLaunchKernelGGL(k_argmax_ids, dim3(cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, d_logits, rows, V, d_ids);
+    hipLaunchKernelGGL(k_argmax_ids, dim3(cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, d_logits, rows, V, d_ids,
+                       (const int32_t*)nullptr, 0, 0);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
+}
+
+// ---- length mode ----
+extern "C" paa_status paa_model_set_lengths(paa_model* m, const int32_t* d_lengths) {
+    if (!m) PAA_FAIL(PAA_ERR_ARG, "paa_model_set_lengths: null model");
+    if (d_lengths && !m->fused)
+        PAA_FAIL(PAA_ERR_ARG, "paa_model_set_lengths: per-clip lengths need the fused attention path (head dim 64, got %d)",
+                 m->a.hidden / m->a.heads);
+    m->lens = d_lengths;
+    return PAA_OK;
+}
+extern "C" paa_status paa_model_frame_counts(paa_model* m, int B, int32_t* d_out, void* stream) {
+    if (!m || !d_out) PAA_FAIL(PAA_ERR_ARG, "paa_model_frame_counts: null argument");
+    if (!m->lens) PAA_FAIL(PAA_ERR_ARG, "paa_model_frame_counts: no lengths set (paa_model_set_lengths)");
+    if (B < 1 || B > m->Bmax) PAA_FAIL(PAA_ERR_SIZE, "batch %d exceeds max_batch %d", B, m->Bmax);
+    FrameGeom g{};
+    g.n = m->a.n_conv;
+    for (int i = 0; i < g.n; ++i) { g.k[i] = m->a.conv_kernel[i]; g.s[i] = m->a.conv_stride[i]; }
+    hipLaunchKernelGGL(k_frames_from_lengths, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, m->lens, B, m->L, m->T, g, d_out);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+extern "C" paa_status paa_argmax_ids_len(const float* d_logits, int B, int T, int V, const int32_t* d_frames, int blank,
+                                         int16_t* d_ids, void* stream) {
+    if (!d_logits || !d_ids || !d_frames) PAA_FAIL(PAA_ERR_ARG, "paa_argmax_ids_len: null argument");
+    if (B < 1 || T < 1 || V < 1 || V > 32767 || blank < 0 || blank >= V)
+        PAA_FAIL(PAA_ERR_SIZE, "paa_argmax_ids_len: B=%d T=%d V=%d blank=%d", B, T, V, blank);
+    const int64_t rows = (int64_t)B * T;
+    hipLaunchKernelGGL(k_argmax_ids, dim3(cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, d_logits, rows, V, d_ids, d_frames, T,
+                       blank);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+extern "C" paa_status paa_mask_tail_rows(float* d_p, int rows, int L, const int32_t* d_lengths, void* stream) {
+    if (!d_p || !d_lengths || rows < 1 || L < 1) PAA_FAIL(PAA_ERR_ARG, "paa_mask_tail_rows: null argument or empty shape");
+    hipLaunchKernelGGL(k_mask_tail_rows, dim3(std::min(cdiv((int64_t)rows * L, 256), 2048)), dim3(256), 0, (hipStream_t)stream, d_p,
+                       rows, L, d_lengths);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+// Test entry: rows [d_frames[b], T) of clip b of x (B, P, cols) f32 (nullable) and of its planes (hi, lo, il as the entries below)
+extern "C" paa_status paa_zero_frames(float* x, void* hi, void* lo, int il, const int32_t* d_frames, int B, int T, int P, int cols,
+                                      void* stream) {
+    if ((!x && !hi) || !d_frames || B < 1 || T < 1 || P < T || cols < 4 || (cols & 3) || (il && (cols & 31)))
+        PAA_FAIL(PAA_ERR_ARG, "paa_zero_frames: B=%d T=%d P=%d cols=%d", B, T, P, cols);
+    return zero_frames(x, Bf{(unsigned short*)hi, il ? nullptr : (unsigned short*)lo, il != 0}, d_frames, B, T, P, cols,
+                       (hipStream_t)stream);
 }
 
 // Test entry: out = dy * gelu'(pre) as the backward pass launches it (f32 and / or bf16 planes; il = the planes interleaved

@@ -49,10 +49,19 @@ struct Conv0Args {
     float* Mx;               //   (B, k, k)  sum_c W1_b[c][j] * s2_bc * rstd_bc * w[c][j']
     float* kc;               //   (B, 16)    sum_c W1_b[c][j] * (s2_bc * rstd_bc * mean_bc - s1_bc)
     float* part;             // scratch partials
+    const int32_t* lens;     // length mode: per-clip sample counts (device, B entries), or null.  Samples i >= lens[b] of clip b
+                             // enter as exact zeros ("attack the utterance, then pad") and get no input gradient
 };
+// the clip's sample count, clamped to [0, L] so a bad entry never indexes out of bounds (null: L)
+__device__ __forceinline__ int clip_len(const Conv0Args& a, int b) {
+    if (!a.lens) return a.L;
+    const int v = a.lens[b];
+    return v < 0 ? 0 : (v > a.L ? a.L : v);
+}
 // Input sample i of clip b: clamp(clean[b][i] + p[b * p_ld + i], -1, 1) (train.py:136) — or clean + p unclamped
 // (evaluation.py:16) — or clean alone when p is null.  Never materialised.
 __device__ __forceinline__ float in_sample(const Conv0Args& a, int b, int i) {
+    if (a.lens && i >= clip_len(a, b)) return 0.f;
     float v = a.clean[(size_t)b * a.L + i];
     if (a.p) {
         v += a.p[(size_t)b * a.p_ld + i];
@@ -73,7 +82,8 @@ void set_conv0_two_pass(bool on);     // paa_test_option(0, .)
 int64_t ctc_work_floats_per_clip(int T, int V, int S_max);
 int64_t conv0_part_floats(int B, int T, int C);
 paa_status ctc(const float* logits, const int32_t* labels, int B, int T, int Tpad, int V, int S_max, int blank,
-               float grad_scale, float* nll, float* dlogits, Bf dlb, float* work, hipStream_t st);
+               float grad_scale, float* nll, float* dlogits, Bf dlb, float* work, hipStream_t st,
+               const int32_t* frames = nullptr);   // per-clip frame counts in [1, T] (device), or null
 paa_status sum_small(const float* x, int n, float* out, hipStream_t st);
 
 // Fused attention (attention.hip): bf16 hi planes only (bf16 mode), head_dim 64.
@@ -91,6 +101,7 @@ struct AttnArgs {
     int T, P, Tp, H, nh;
     int nbh;                        // B * nh (set by the launcher)
     float scale;                    // head_dim^-0.5
+    const int32_t* klen;            // (B) per-clip key count in [1, T] (device), or null: every clip has T keys
 };
 paa_status attn_fwd(const AttnArgs& a, int B, int head_dim, hipStream_t st);
 paa_status attn_bwd(const AttnArgs& a, int B, int head_dim, hipStream_t st);

@@ -610,6 +610,7 @@ __global__ void k_input_grad(Conv0Args a, float* __restrict__ grad) {
             const float u = a.clean[(size_t)b * a.L + l] + (ROWS ? a.p[(size_t)b * a.p_ld + l] : pv);
             if (!(u >= -1.f && u <= 1.f)) gsum = 0.f;           // clamp backward: pass-through inside [-1, 1]
         }
+        if (l >= clip_len(a, b)) gsum = 0.f;                    // length mode: no term from beyond the clip's end
         if (ROWS) grad[(size_t)b * a.L + l] = gsum;
         else total += gsum;
     }
@@ -726,6 +727,7 @@ __global__ __launch_bounds__(256) void k_input_grad_gn(Conv0Args a, float* __res
             const float u = a.clean[(size_t)b * a.L + lc] + a.p[(ROWS ? (size_t)b * a.p_ld : 0) + lc];
             if (!(u >= -1.f && u <= 1.f)) gsum = 0.f;           // clamp backward: pass-through inside [-1, 1]
         }
+        if (lc >= clip_len(a, b)) gsum = 0.f;                   // length mode: no term from beyond the clip's end
         if (ROWS) { if (l < a.L) grad[(size_t)b * a.L + l] = gsum; }
         else total += gsum;
     }
@@ -836,16 +838,26 @@ __device__ __forceinline__ double lse3(double a, double b, double c) {
     return m + (double)__logf(__expf((float)(a - m)) + __expf((float)(b - m)) + __expf((float)(c - m)));
 }
 
+// Per-clip frame count (nullable): clip b aligns over its first frames[b] frames only, clamped to [1, T] so a bad entry cannot
+// index out of bounds; the work layout keeps the stride of the full T.  Null = T frames for every clip.
+__device__ __forceinline__ int ctc_frames(const int32_t* __restrict__ frames, int b, int T) {
+    if (!frames) return T;
+    const int v = frames[b];
+    return v < 1 ? 1 : (v > T ? T : v);
+}
+
 // 512 threads: waves 0-3 run the alpha recursion forwards while waves 4-7 run the beta recursion backwards (one
 // workgroup barrier per time step serves both); every row of both is stored.  The gradient phase then needs no
 // workgroup barrier at all: each wave takes one frame, sums the posterior occupancy per class with fixed-point
 // LDS atomics into its own counters and writes that frame's gradient row.
 __global__ __launch_bounds__(512) void k_ctc(const float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                           int T, int Tpad, int V, int S_max, int blank, float gscale,
+                                           int Tall, int Tpad, int V, int S_max, int blank, float gscale,
                                            float* __restrict__ nll_out, float* __restrict__ dlogits,
-                                           float* __restrict__ work, int64_t work_per_clip, Bf dlb) {
+                                           float* __restrict__ work, int64_t work_per_clip, Bf dlb,
+                                           const int32_t* __restrict__ frames) {
     extern __shared__ __attribute__((aligned(16))) double smd[];
     const int b = blockIdx.x, tid = threadIdx.x;
+    const int T = ctc_frames(frames, b, Tall);
     const int SPmax = 2 * S_max + 1;
     double* bufA0 = smd;                    // alpha rows (double buffered)
     double* bufA1 = smd + SPmax;
@@ -859,8 +871,8 @@ __global__ __launch_bounds__(512) void k_ctc(const float* __restrict__ logits, c
     const float* lg = logits + (size_t)b * Tpad * V;
     double* wk = reinterpret_cast<double*>(work) + (size_t)b * work_per_clip;
     double* lp = wk;                                         // [T][V]
-    double* alpha = lp + (size_t)T * V;                      // [T][SPmax]
-    double* beta = alpha + (size_t)T * SPmax;                // [T][SPmax]
+    double* alpha = lp + (size_t)Tall * V;                   // [Tall][SPmax]
+    double* beta = alpha + (size_t)Tall * SPmax;             // [Tall][SPmax]
 
     if (tid == 0) {
         int n = 0;
@@ -1023,10 +1035,11 @@ __device__ __forceinline__ CtcWork ctc_work(float* wk, int T, int V, int row) {
 
 // log-softmax of every frame of every clip in float64 (from float32 max / sum-exp pieces): 32 lanes per frame
 __global__ __launch_bounds__(256) void k_ctc_logsoftmax(const float* __restrict__ logits, int B, int T, int Tpad, int V,
-                                                        float* __restrict__ work, int64_t wpc) {
+                                                        float* __restrict__ work, int64_t wpc, const int32_t* __restrict__ frames) {
     const int f = blockIdx.x * 8 + (threadIdx.x >> 5);
     if (f >= B * T) return;
     const int b = f / T, t = f - b * T, c = threadIdx.x & 31;
+    if (t >= ctc_frames(frames, b, T)) return;       // frames past the clip's end are never read
     const float* lg = logits + ((size_t)b * Tpad + t) * V;
     double* lp = reinterpret_cast<double*>(work + (size_t)b * wpc) + (size_t)t * V;
     float mx = -INFINITY;
@@ -1064,13 +1077,15 @@ __device__ __forceinline__ double ctc_lse3(double x0, double x1, double x2) {
 
 // the two recursions of one clip: wave 0 alpha, wave 1 beta; LDS_TAB: the clip's lp table is first copied to LDS
 template <int NS, bool LDS_TAB>
-__global__ __launch_bounds__(128) void k_ctc_rec(const int32_t* __restrict__ labels, int T, int V, int S_max, int blank,
-                                                 float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc) {
+__global__ __launch_bounds__(128) void k_ctc_rec(const int32_t* __restrict__ labels, int Tall, int V, int S_max, int blank,
+                                                 float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc,
+        const int32_t* __restrict__ frames) {
     extern __shared__ __attribute__((aligned(16))) double smd[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = ctc_frames(frames, b, Tall);
     const int SPmax = 2 * S_max + 1;
     constexpr int ROW = 64 * NS;
-    const CtcWork w = ctc_work(work + (size_t)b * wpc, T, V, ROW);
+    const CtcWork w = ctc_work(work + (size_t)b * wpc, Tall, V, ROW);
     int* lab = reinterpret_cast<int*>(smd + (LDS_TAB ? (size_t)T * V : 0));      // [SPmax] extended labels
     __shared__ int s_len;
     // extended labels: valid labels are the non-negative entries, in order (HF masked_select).  The label row is first
@@ -1197,17 +1212,19 @@ __global__ __launch_bounds__(128) void k_ctc_rec(const int32_t* __restrict__ lab
 // every wave has finished reading a buffer before any wave passes the next barrier and overwrites it).  Same arithmetic per
 // state, same row layout in the work buffer (k_ctc_grad reads it unchanged): results are bit-identical to k_ctc_rec.
 template <int NS, bool LDS_TAB>
-__global__ __launch_bounds__(128 * NS) void k_ctc_rec_mw(const int32_t* __restrict__ labels, int T, int V, int S_max, int blank,
-                                                          float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc) {
+__global__ __launch_bounds__(128 * NS) void k_ctc_rec_mw(const int32_t* __restrict__ labels, int Tall, int V, int S_max, int blank,
+                                                          float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc,
+        const int32_t* __restrict__ frames) {
     static_assert(NS >= 2 && NS <= 8, "one wave per state slot: 4 .. 16 waves");
     extern __shared__ __attribute__((aligned(16))) double smd[];
     constexpr int NT = 128 * NS, ROW = 64 * NS;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int T = ctc_frames(frames, b, Tall);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool fwd = wave < NS;
     const int j = fwd ? wave : wave - NS;                       // state slot of this wave
     const int SPmax = 2 * S_max + 1;
-    const CtcWork w = ctc_work(work + (size_t)b * wpc, T, V, ROW);
+    const CtcWork w = ctc_work(work + (size_t)b * wpc, Tall, V, ROW);
     double* xch = smd + (LDS_TAB ? (size_t)T * V : 0);          // [2 directions][2 buffers][NS][64]
     int* lab = reinterpret_cast<int*>(xch + 4 * ROW);           // [SPmax] extended labels
     __shared__ int s_len;
@@ -1290,17 +1307,19 @@ __global__ __launch_bounds__(128 * NS) void k_ctc_rec_mw(const int32_t* __restri
 // k_ctc_rec_mw: bit-identical results.  At S = 450, T = 1499 (30 s clips) the one-wave-per-direction kernel evaluated 16 states per
 // lane one after the other: ~2 ms of a 73 ms step.
 template <int NS, int K, bool LDS_TAB>
-__global__ __launch_bounds__(128 * NS / K) void k_ctc_rec_mwk(const int32_t* __restrict__ labels, int T, int V, int S_max, int blank,
-                                                               float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc) {
+__global__ __launch_bounds__(128 * NS / K) void k_ctc_rec_mwk(const int32_t* __restrict__ labels, int Tall, int V, int S_max, int blank,
+                                                               float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc,
+        const int32_t* __restrict__ frames) {
     static_assert(K >= 2 && NS % K == 0 && NS / K >= 2 && 2 * NS / K <= 16, "K states per lane and wave, 4 .. 16 waves");
     extern __shared__ __attribute__((aligned(16))) double smd[];
     constexpr int NWD = NS / K, NT = 128 * NWD, ROW = 64 * NS;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int T = ctc_frames(frames, b, Tall);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool fwd = wave < NWD;
     const int jw = fwd ? wave : wave - NWD;                     // slot group of this wave
     const int SPmax = 2 * S_max + 1;
-    const CtcWork w = ctc_work(work + (size_t)b * wpc, T, V, ROW);
+    const CtcWork w = ctc_work(work + (size_t)b * wpc, Tall, V, ROW);
     double* xch = smd + (LDS_TAB ? (size_t)T * V : 0);          // [2 directions][2 buffers][NS][64]
     int* lab = reinterpret_cast<int*>(xch + 4 * ROW);           // [SPmax] extended labels
     __shared__ int s_len;
@@ -1418,16 +1437,17 @@ __global__ __launch_bounds__(128 * NS / K) void k_ctc_rec_mwk(const int32_t* __r
 
 // gradient rows: one wave per frame (grid: frames / 4 x clips)
 template <int NS>
-__global__ __launch_bounds__(256) void k_ctc_grad(int T, int Tpad, int V, float gscale, float* __restrict__ dlogits, Bf dlb,
-                                                  float* __restrict__ work, int64_t wpc) {
+__global__ __launch_bounds__(256) void k_ctc_grad(int Tall, int Tpad, int V, float gscale, float* __restrict__ dlogits, Bf dlb,
+                                                  float* __restrict__ work, int64_t wpc, const int32_t* __restrict__ frames) {
     extern __shared__ __attribute__((aligned(16))) unsigned occs[];     // [4][V]
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int t = blockIdx.x * 4 + wave;
     constexpr int ROW = 64 * NS;
-    const CtcWork w = ctc_work(work + (size_t)b * wpc, T, V, ROW);
+    const int T = ctc_frames(frames, b, Tall);
+    const CtcWork w = ctc_work(work + (size_t)b * wpc, Tall, V, ROW);
     float* dl = dlogits + (size_t)b * Tpad * V;
     const size_t dlo = (size_t)b * Tpad * V;
-    if (t >= T) {                         // pad frames [T, Tpad): zero gradient
+    if (t >= T) {                         // frames past the clip's end and pad frames, [T, Tpad): zero gradient
         if (t < Tpad) for (int c = lane; c < V; c += 64) { dl[(size_t)t * V + c] = 0.f; store_bf16(dlb, dlo + (size_t)t * V + c, 0.f); }
         return;
     }
@@ -1460,9 +1480,9 @@ __global__ __launch_bounds__(256) void k_ctc_grad(int T, int Tpad, int V, float 
 
 template <int NS>
 static paa_status launch_ctc_ws(const float* logits, const int32_t* labels, int B, int T, int Tpad, int V, int S_max, int blank,
-                                float gscale, float* nll, float* dlogits, Bf dlb, float* work, int64_t wpc, hipStream_t st) {
+                                float gscale, float* nll, float* dlogits, Bf dlb, float* work, int64_t wpc, const int32_t* frames, hipStream_t st) {
     const int SPmax = 2 * S_max + 1;
-    hipLaunchKernelGGL(k_ctc_logsoftmax, dim3(cdiv((int64_t)B * T, 8)), dim3(256), 0, st, logits, B, T, Tpad, V, work, wpc);
+    hipLaunchKernelGGL(k_ctc_logsoftmax, dim3(cdiv((int64_t)B * T, 8)), dim3(256), 0, st, logits, B, T, Tpad, V, work, wpc, frames);
     PAA_LAUNCH_CHECK();
     const size_t tab = sizeof(double) * (size_t)T * V;
     const size_t small = sizeof(int) * ((size_t)SPmax + S_max) + 64;
@@ -1475,11 +1495,11 @@ static paa_status launch_ctc_ws(const float* logits, const int32_t* labels, int 
             PAA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctc_rec_mw<NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
             attr_mw = true;
         }
-        if (ltab) hipLaunchKernelGGL((k_ctc_rec_mw<NS, true>), dim3(B), dim3(128 * NS), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc);
-        else hipLaunchKernelGGL((k_ctc_rec_mw<NS, false>), dim3(B), dim3(128 * NS), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc);
+        if (ltab) hipLaunchKernelGGL((k_ctc_rec_mw<NS, true>), dim3(B), dim3(128 * NS), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
+        else hipLaunchKernelGGL((k_ctc_rec_mw<NS, false>), dim3(B), dim3(128 * NS), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
         PAA_LAUNCH_CHECK();
         if (dlogits) {
-            hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc);
+            hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc, frames);
             PAA_LAUNCH_CHECK();
         }
         return PAA_OK;
@@ -1493,11 +1513,11 @@ static paa_status launch_ctc_ws(const float* logits, const int32_t* labels, int 
             PAA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctc_rec_mwk<NS, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
             attr_mwk = true;
         }
-        if (ltab) hipLaunchKernelGGL((k_ctc_rec_mwk<NS, 2, true>), dim3(B), dim3(128 * NS / 2), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc);
-        else hipLaunchKernelGGL((k_ctc_rec_mwk<NS, 2, false>), dim3(B), dim3(128 * NS / 2), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc);
+        if (ltab) hipLaunchKernelGGL((k_ctc_rec_mwk<NS, 2, true>), dim3(B), dim3(128 * NS / 2), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
+        else hipLaunchKernelGGL((k_ctc_rec_mwk<NS, 2, false>), dim3(B), dim3(128 * NS / 2), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
         PAA_LAUNCH_CHECK();
         if (dlogits) {
-            hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc);
+            hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc, frames);
             PAA_LAUNCH_CHECK();
         }
         return PAA_OK;
@@ -1507,13 +1527,13 @@ static paa_status launch_ctc_ws(const float* logits, const int32_t* labels, int 
     if (lds_tab) {
         static bool attr = false;
         if (!attr) { PAA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctc_rec<NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)); attr = true; }
-        hipLaunchKernelGGL((k_ctc_rec<NS, true>), dim3(B), dim3(128), lds, st, labels, T, V, S_max, blank, nll, work, wpc);
+        hipLaunchKernelGGL((k_ctc_rec<NS, true>), dim3(B), dim3(128), lds, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
     } else {
-        hipLaunchKernelGGL((k_ctc_rec<NS, false>), dim3(B), dim3(128), lds, st, labels, T, V, S_max, blank, nll, work, wpc);
+        hipLaunchKernelGGL((k_ctc_rec<NS, false>), dim3(B), dim3(128), lds, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
     }
     PAA_LAUNCH_CHECK();
     if (dlogits) {
-        hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc);
+        hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc, frames);
         PAA_LAUNCH_CHECK();
     }
     return PAA_OK;
@@ -1541,7 +1561,7 @@ int64_t ctc_work_floats_per_clip(int T, int V, int S_max) {
 }
 
 paa_status ctc(const float* logits, const int32_t* labels, int B, int T, int Tpad, int V, int S_max, int blank,
-               float grad_scale, float* nll, float* dlogits, Bf dlb, float* work, hipStream_t st) {
+               float grad_scale, float* nll, float* dlogits, Bf dlb, float* work, hipStream_t st, const int32_t* frames) {
     if (S_max < 1 || S_max > 4000) PAA_FAIL(PAA_ERR_SIZE, "ctc: S_max=%d out of range", S_max);
     if (V > 256) PAA_FAIL(PAA_ERR_SIZE, "ctc: vocab %d > 256", V);
     if ((uintptr_t)work & 7) PAA_FAIL(PAA_ERR_ARG, "ctc: work buffer must be 8-byte aligned");
@@ -1549,14 +1569,14 @@ paa_status ctc(const float* logits, const int32_t* labels, int B, int T, int Tpa
     const int64_t wpc = ctc_work_floats_per_clip(T, V, S_max);
     const int ns = ctc_ws_ns(SPmax);
     if (ns) {                         // wave-synchronous kernel: ns states per lane
-#define PAA_CTC_WS(N) case N: return launch_ctc_ws<N>(logits, labels, B, T, Tpad, V, S_max, blank, grad_scale, nll, dlogits, dlb, work, wpc, st)
+#define PAA_CTC_WS(N) case N: return launch_ctc_ws<N>(logits, labels, B, T, Tpad, V, S_max, blank, grad_scale, nll, dlogits, dlb, work, wpc, frames, st)
         switch (ns) { PAA_CTC_WS(1); PAA_CTC_WS(2); PAA_CTC_WS(4); PAA_CTC_WS(6); PAA_CTC_WS(8); PAA_CTC_WS(16); }
 #undef PAA_CTC_WS
     }
     const size_t lds = sizeof(double) * 4 * (size_t)SPmax + sizeof(int) * ((size_t)SPmax + 8 * V);
     if (lds > 160 * 1024) PAA_FAIL(PAA_ERR_SIZE, "ctc: label capacity %d needs %zu bytes of LDS", S_max, lds);
     hipLaunchKernelGGL(k_ctc, dim3(B), dim3(512), lds, st, logits, labels, T, Tpad, V, S_max, blank, grad_scale, nll,
-                       dlogits, work, wpc / 2, dlb);
+                       dlogits, work, wpc / 2, dlb, frames);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }
@@ -1648,6 +1668,12 @@ extern "C" int64_t paa_ctc_work_floats(int B, int T, int V, int S_max) { return 
 extern "C" paa_status paa_ctc(const float* logits, const int32_t* labels, int B, int T, int V, int S_max, int blank,
                               float grad_scale, float* nll, float* dlogits, float* work, void* stream) {
     return ctc(logits, labels, B, T, T, V, S_max, blank, grad_scale, nll, dlogits, Bf{nullptr, nullptr}, work, (hipStream_t)stream);
+}
+// paa_ctc with a per-clip frame count d_frames (device, B entries in [1, T]; null = paa_ctc): clip b aligns over its first
+// d_frames[b] frames, and its dlogits rows beyond are zero
+extern "C" paa_status paa_ctc_len(const float* logits, const int32_t* labels, const int32_t* d_frames, int B, int T, int V, int S_max,
+                                  int blank, float grad_scale, float* nll, float* dlogits, float* work, void* stream) {
+    return ctc(logits, labels, B, T, T, V, S_max, blank, grad_scale, nll, dlogits, Bf{nullptr, nullptr}, work, (hipStream_t)stream, d_frames);
 }
 // logits / dlogits (B, Tpad, V) with Tpad >= T frames per clip (pad frames: not read; dlogits and planes zeroed); dlb_hi / dlb_lo
 // planar bf16 planes of dlogits (nullable; they need dlogits)

@@ -195,10 +195,69 @@ class PaaModel:
         self.h = h
         self.frames = _lib.lib().paa_model_frames(h)
         self.workspace_bytes = _lib.lib().paa_model_workspace_bytes(h)
+        self._lengths = None          # persistent int32 (max_batch) buffer of set_lengths; allocated on first use
+        self._len_slots, self._len_events, self._len_i = None, None, 0      # pinned host slots behind its asynchronous copies
+        self.lengths_on = False
 
     @classmethod
     def from_hf(cls, hf_model, max_batch, length, dtype="bf16", device="cuda"):
         return cls(arch_from_hf_config(hf_model.config), hf_model.state_dict(), max_batch, length, dtype, device)
+
+    MIN_CLIP_SAMPLES = 400            # the shortest clip the length mode accepts (one STFT window; HF's minimum input is shorter)
+
+    def check_lengths(self, lengths, B=None):
+        """Host validation of per-clip sample counts: integers in [MIN_CLIP_SAMPLES, L], at most max_batch of them (exactly
+        B when given).  Returns them as a CPU int32 tensor."""
+        t = torch.as_tensor(lengths).detach().cpu()
+        if t.dim() != 1 or t.numel() < 1 or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError(f"lengths must be a 1-d integer sequence, got shape {tuple(t.shape)} dtype {t.dtype}")
+        if t.numel() > self.max_batch or (B is not None and t.numel() != B):
+            raise ValueError(f"{t.numel()} lengths for a batch of {B if B is not None else self.max_batch}")
+        lo, hi = int(t.min()), int(t.max())
+        if lo < self.MIN_CLIP_SAMPLES or hi > self.length:
+            raise ValueError(f"clip lengths must lie in [{self.MIN_CLIP_SAMPLES}, {self.length}], got [{lo}, {hi}]")
+        return t.to(torch.int32)
+
+    def set_lengths(self, lengths):
+        """Per-clip true sample counts for every later call, or None to switch the mode off.  The values are
+        validated here and copied into ONE persistent device buffer, which the kernels read on the stream: a captured graph
+        follows later set_lengths calls without re-capture (switching the mode on or off does need a new capture).  Entries
+        beyond len(lengths) are set to L.  The copy is asynchronous, out of a ring of pinned host slots (a slot is rewritten only
+        after the event behind its copy has completed), so a call per batch puts no host sync into a training loop.  Returns the
+        device buffer (or None)."""
+        lib = _lib.lib()
+        if lengths is None:
+            _lib.check(lib.paa_model_set_lengths(self.h, None))
+            self.lengths_on = False
+            return None
+        t = self.check_lengths(lengths)
+        if self._lengths is None:
+            self._lengths = torch.full((self.max_batch,), self.length, dtype=torch.int32, device=self.device)
+            self._len_slots = [torch.empty(self.max_batch, dtype=torch.int32).pin_memory() for _ in range(4)]
+            self._len_events = [None] * 4
+        if not self.lengths_on:
+            _lib.check(lib.paa_model_set_lengths(self.h, _lib.ptr(self._lengths)))     # refuses the non-fused attention path
+            self.lengths_on = True
+        k = self._len_i % len(self._len_slots)
+        self._len_i += 1
+        if self._len_events[k] is not None:
+            self._len_events[k].synchronize()
+        slot = self._len_slots[k]
+        slot.fill_(self.length)
+        slot[:t.numel()] = t
+        with torch.cuda.device(self.device):
+            self._lengths.copy_(slot, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        self._len_events[k] = ev
+        return self._lengths
+
+    def frame_counts(self, B):
+        """T_b of the current length buffer for the first B clips, as an int32 device tensor."""
+        out = torch.empty(B, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().paa_model_frame_counts(self.h, int(B), _lib.ptr(out), _lib.stream_ptr()))
+        return out
 
     def _checked(self, clean, p):
         """Raw pointers cross the C ABI: refuse anything that is not a contiguous float32 tensor on this model's GPU

@@ -26,6 +26,7 @@ def main(args) -> int:
     pgd.masking_route(args.norm_type, world)          # before any collective: every rank raises
     place.check_flags(args)                           # the same for what placement does not combine with at any length
     rir.check_flags(args)                             # and for room responses
+    pgd.check_clip_lengths(args)                      # and for true clip lengths
     if world > 1:
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
         torch.cuda.set_device(local)

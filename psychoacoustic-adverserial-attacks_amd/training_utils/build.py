@@ -13,6 +13,7 @@ from .. import synth
 from ..core import iso
 from ..model import PaaModel
 from . import place, rir
+from .pgd import unpack_batch
 from .train import perturbation_constraint
 
 
@@ -74,9 +75,33 @@ def create_optimizer(args, p):
     return optimizer, scheduler
 
 
+def lengths_on(args) -> bool:
+    """--clip_lengths true: loaders yield (x, texts, lengths) instead of (x, texts)."""
+    return str(getattr(args, "clip_lengths", "padded")) == "true"
+
+
+def synthetic_lengths(n: int, length: int, seed: int, first_clip: int = 0) -> torch.Tensor:
+    """True sample counts of the synthetic clips ``first_clip`` .. ``first_clip + n - 1``: uniform in [L/2, L] from synth's own
+    counter generator, keyed by the clip's global index — the same on every rank and in every run."""
+    lo = max(int(length) // 2, min(400, int(length)))
+    out = torch.empty(n, dtype=torch.int32)
+    for i in range(n):
+        u = float(synth.uniform(synth.key_of(f"len{first_clip + i}", int(seed)), 1)[0])
+        out[i] = min(int(length), lo + int(u * (int(length) - lo + 1)))
+    return out
+
+
+def zero_tails(x: torch.Tensor, lengths) -> torch.Tensor:
+    """x[b, len_b:] = 0, in place."""
+    for b, n in enumerate(lengths.tolist()):
+        x[b, int(n):] = 0
+    return x
+
+
 def synthetic_loader(args, batch: int, length: int, steps: int, rank: int = 0, world: int = 1):
     """Fixed-length synthetic batches: ``steps`` batches of ``batch`` clips per rank,
-    transcripts of lower-case words (=> <unk>/| labels)."""
+    transcripts of lower-case words (=> <unk>/| labels).  With --clip_lengths true every batch is
+    (x, texts, lengths): ``synthetic_lengths``, the tail of every clip zeroed."""
     words = ["the", "quick", "brown", "fox", "jumps", "over", "a", "lazy", "dog", "and", "runs", "away"]
     out = []
     for s in range(steps):
@@ -86,7 +111,11 @@ def synthetic_loader(args, batch: int, length: int, steps: int, rank: int = 0, w
         for b in range(batch):
             u = synth.uniform(synth.key_of(f"txt{first + b}", int(args.seed)), 24)
             texts.append(" ".join(words[int(v * len(words))] for v in u))
-        out.append((x, texts))
+        if lengths_on(args):
+            ln = synthetic_lengths(batch, length, int(args.seed), first)
+            out.append((zero_tails(x, ln), texts, ln))
+        else:
+            out.append((x, texts))
     return out
 
 
@@ -195,7 +224,15 @@ def collate_fixed(waves, length: int) -> torch.Tensor:
     return out
 
 
-def _batches(x, texts, batch_size):
+def collate_fixed_lengths(waves, length: int):
+    """``collate_fixed`` and the true sample count of every clip after the crop: ((N, length) float32, (N,) int32)."""
+    return collate_fixed(waves, length), torch.tensor([min(int(length), int(torch.as_tensor(w).numel())) for w in waves],
+                                                      dtype=torch.int32)
+
+
+def _batches(x, texts, batch_size, lengths=None):
+    if lengths is not None:
+        return [(x[i:i + batch_size], texts[i:i + batch_size], lengths[i:i + batch_size]) for i in range(0, len(texts), batch_size)]
     return [(x[i:i + batch_size], texts[i:i + batch_size]) for i in range(0, len(texts), batch_size)]
 
 
@@ -208,13 +245,14 @@ def shard_batches(batches, rank: int, world: int, keep_empty: bool = False):
     if world <= 1:
         return list(batches)
     out = []
-    for x, texts in batches:
+    for batch in batches:
+        x, texts, lengths = unpack_batch(batch)
         n = len(texts)
         if n < world and not keep_empty:
             continue
         lo = rank * n // world
         hi = (rank + 1) * n // world
-        out.append((x[lo:hi], texts[lo:hi]))
+        out.append((x[lo:hi], texts[lo:hi]) if lengths is None else (x[lo:hi], texts[lo:hi], lengths[lo:hi]))
     return out
 
 
@@ -252,7 +290,9 @@ def load_local_dataset(data_dir: str, sr: int):
 def create_data_loaders(args, rank: int = 0, world: int = 1):
     """build.py:104-220 without the network: --data_dir (local wavs) or synthetic clips; fixed-length collate at the
     ``relative_audio_length`` quantile; 80/10/10 split; --small_data keeps ~1 % (at least 3 batches' worth).
-    Returns (train, eval, test) lists of (batch (B, L) float32 CPU tensor, list[str]) and the clip length.
+    Returns (train, eval, test) lists of (batch (B, L) float32 CPU tensor, list[str]) and the clip length; with
+    --clip_lengths true the batches are (x, texts, lengths (B,) int32): the clips' own sample counts after the crop, or
+    ``synthetic_lengths`` with the tails zeroed.
     ``world`` > 1: global batches of ``batch_size * world`` clips, of which this rank gets its shard (``shard_batches``)."""
     if world > 1:
         import copy
@@ -271,7 +311,13 @@ def create_data_loaders(args, rank: int = 0, world: int = 1):
         if getattr(args, "small_data", False):
             keep = max(3 * bs, len(plan["train"]) // 100)
             plan = {k: (v[:keep] if isinstance(v, list) else v) for k, v in plan.items()}
-        mk = lambda ids: _batches(collate_fixed([waves[i] for i in ids], length), [texts[i] for i in ids], bs) if ids else []
+        def mk(ids):
+            if not ids:
+                return []
+            if lengths_on(args):
+                x, ln = collate_fixed_lengths([waves[i] for i in ids], length)
+                return _batches(x, [texts[i] for i in ids], bs, ln)
+            return _batches(collate_fixed([waves[i] for i in ids], length), [texts[i] for i in ids], bs)
         return mk(plan["train"]), mk(plan["eval"]), mk(plan["test"]), length
     else:
         length = int(round(float(getattr(args, "audio_seconds", 10.0)) * int(args.sr)))
@@ -287,6 +333,11 @@ def create_data_loaders(args, rank: int = 0, world: int = 1):
     if getattr(args, "small_data", False):
         n = min(n, max(3 * bs, n // 100))
     n_tr, n_ev = int(0.8 * n), int(0.1 * n)
+    if lengths_on(args):
+        ln = synthetic_lengths(len(texts), length, int(args.seed))
+        zero_tails(x, ln)
+        sl = lambda a, b: _batches(x[a:b], texts[a:b], bs, ln[a:b])
+        return sl(0, n_tr), sl(n_tr, n_tr + n_ev), sl(n_tr + n_ev, n), length
     tr = _batches(x[:n_tr], texts[:n_tr], bs)
     ev = _batches(x[n_tr:n_tr + n_ev], texts[n_tr:n_tr + n_ev], bs)
     te = _batches(x[n_tr + n_ev:n], texts[n_tr + n_ev:n], bs)

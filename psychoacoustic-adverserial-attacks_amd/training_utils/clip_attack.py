@@ -13,6 +13,9 @@ With ``args.masking_loss_alpha`` = alpha > 0 clip b's objective
 One launch sequence per step (``paa_model_fwd_bwd_rows`` -> ``paa_sign_step`` / ``paa_adam_step`` over B*L elements ->
 ``paa_project_rows`` per norm) and no collective: clips are independent, so ranks never exchange gradients.  Everything else —
 the Adam bookkeeping, the masking loss, the device WER counters, the warm-up of ``capture()`` — is ``pgd._StepperCore``'s.
+
+True clip lengths: with ``lengths=`` the model attacks the utterance and then pads, and ``paa_mask_tail_rows``
+re-zeroes delta_b[len_b:] after every ``paa_project_rows`` (the sign and Adam updates keep a zero tail: its gradient is zero).
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ import numpy as np
 import torch
 
 from .. import _lib, runtime, synth
-from .pgd import N_STATS, ST_LOSS, _StepperCore
+from .pgd import N_STATS, ST_LOSS, _StepperCore, lengths_refusal
 
 
 class ClipStepper(_StepperCore):
@@ -72,6 +75,8 @@ class ClipStepper(_StepperCore):
             self._update(delta, grad, B * L)
             for prm in self._prm:
                 _lib.check(lib.paa_project_rows(self.proj.h, prm, _lib.ptr(delta), _lib.ptr(delta), B, _lib.ptr(clean), L, st))
+                if self.lengths_on:
+                    _lib.check(lib.paa_mask_tail_rows(_lib.ptr(delta), B, L, _lib.ptr(self.model._lengths), st))
         if self.device_wer:
             self.stats_log.push(self.stats)
         r["loss"] = self.stats[ST_LOSS]
@@ -79,23 +84,25 @@ class ClipStepper(_StepperCore):
         return r
 
     def step(self, delta: torch.Tensor, clean: torch.Tensor, labels: torch.Tensor, want_logits=True, logits_out=None,
-             refs=None):
+             refs=None, lengths=None):
         """In place on ``delta`` (B, L).  Returns dict(loss: 0-d device tensor, the sum over the clips, logits, grad (B, L)).
-        ``refs`` as PgdStepper.step."""
+        ``refs`` / ``lengths`` as PgdStepper.step."""
         if refs is not None:
             self.set_refs(refs)
+        if lengths is not None:
+            self.set_lengths(lengths)
         delta, clean = self._checked(delta, clean)
         self._check_p(delta)
         self._pre_step()
         return self._body(delta, clean, labels, want_logits, logits_out)
 
-    def capture(self, delta, clean, labels, logits_out=None, refs=None):
-        """One step on fixed buffers as ONE hipGraph (``refs`` as PgdStepper.capture).  Returns (graph, result dict);
+    def capture(self, delta, clean, labels, logits_out=None, refs=None, lengths=None):
+        """One step on fixed buffers as ONE hipGraph (``refs`` / ``lengths`` as PgdStepper.capture).  Returns (graph, result dict);
         ``graph.replay()`` re-runs the step in place on ``delta`` with whatever ``clean`` / ``labels`` hold.  With Adam the graph is
         wrapped so that every replay first pushes the step's scalars, and the warm-up step is undone (delta, moments and step
         count as before the call)."""
         delta, clean = self._checked(delta, clean)
-        lab, logits_out = self._warm_up(delta, clean, labels, logits_out, refs)
+        lab, logits_out = self._warm_up(delta, clean, labels, logits_out, refs, lengths)
         return self._capture_body(delta, clean, lab, logits_out)
 
 
@@ -110,9 +117,34 @@ def init_rows(length: int, indices, seed: int = 5) -> np.ndarray:
     return out
 
 
-def project_rows(delta: torch.Tensor, clean: torch.Tensor, args, interp=None, spl_thresh=None) -> torch.Tensor:
+def _lengths_dev(lengths, B, L, dev):
+    """Host-validated per-clip sample counts ([1, L], one per clip) as an int32 device tensor."""
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda and lengths.dtype == torch.int32 and lengths.numel() >= B:
+        return lengths[:B].contiguous()
+    t = torch.as_tensor(lengths).detach().cpu()
+    if t.dim() != 1 or t.numel() != B or t.is_floating_point():
+        raise ValueError(f"lengths must hold {B} integers, got shape {tuple(t.shape)} dtype {t.dtype}")
+    if int(t.min()) < 1 or int(t.max()) > L:
+        raise ValueError(f"clip lengths must lie in [1, {L}], got [{int(t.min())}, {int(t.max())}]")
+    return t.to(torch.int32).to(dev)
+
+
+def mask_tail_rows(delta: torch.Tensor, lengths) -> torch.Tensor:
+    """delta_b[len_b:] = 0 for every row, in place (paa_mask_tail_rows)."""
+    B, L = delta.shape
+    ln = _lengths_dev(lengths, B, L, delta.device)
+    with torch.cuda.device(delta.device):
+        _lib.check(_lib.lib().paa_mask_tail_rows(_lib.ptr(delta), B, L, _lib.ptr(ln), _lib.stream_ptr()))
+    return delta
+
+
+def project_rows(delta: torch.Tensor, clean: torch.Tensor, args, interp=None, spl_thresh=None, lengths=None) -> torch.Tensor:
     """perturbation_constraint (train.py:69-99) on every row of ``delta`` (B, L) against its own clip of ``clean`` (B, L),
-    in place; the norms of ``args.norm_type`` in order."""
+    in place; the norms of ``args.norm_type`` in order.  ``lengths``: delta_b[len_b:] is re-zeroed after every projection."""
+    if lengths is not None:
+        why = lengths_refusal(args)
+        if why is not None:
+            raise ValueError(why)
     delta = runtime.as_f32_cuda(delta, "delta")
     clean = runtime.as_f32_cuda(clean, "clean_audio")
     if delta.dim() != 2 or tuple(delta.shape) != tuple(clean.shape):
@@ -127,11 +159,14 @@ def project_rows(delta: torch.Tensor, clean: torch.Tensor, args, interp=None, sp
                 pr.set_spl_thresh(spl_thresh)
             _lib.check(_lib.lib().paa_project_rows(pr.h, runtime.params_of(args, n), _lib.ptr(delta), _lib.ptr(delta), B,
                                                    _lib.ptr(clean), L, _lib.stream_ptr()))
+            if lengths is not None:
+                mask_tail_rows(delta, lengths)
     return delta
 
 
-def compose_rows(clean: torch.Tensor, delta: torch.Tensor) -> torch.Tensor:
-    """clamp(clean_b + delta_b, -1, 1) for every clip (the adversarial waveforms the entry point writes)."""
+def compose_rows(clean: torch.Tensor, delta: torch.Tensor, lengths=None) -> torch.Tensor:
+    """clamp(clean_b + delta_b, -1, 1) for every clip (the adversarial waveforms the entry point writes); with ``lengths``,
+    exactly 0 for the samples i >= len_b (attack the utterance, then pad)."""
     clean = runtime.as_f32_cuda(clean, "clean_audio")
     delta = runtime.as_f32_cuda(delta, "delta")
     B, L = clean.shape
@@ -139,11 +174,14 @@ def compose_rows(clean: torch.Tensor, delta: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(clean.device):
         _lib.check(_lib.lib().paa_compose_clamp_rows(_lib.ptr(clean), _lib.ptr(delta), delta.shape[0] if delta.dim() == 2 else 1,
                                                      _lib.ptr(out), B, L, _lib.stream_ptr()))
+    if lengths is not None:
+        mask_tail_rows(out, lengths)
     return out
 
 
-def clip_nll(model, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """Per-clip CTC loss (B,) of logits (B, T, V) on the device (paa_ctc, HF reduction 'sum' per clip)."""
+def clip_nll(model, logits: torch.Tensor, labels: torch.Tensor, frames=None) -> torch.Tensor:
+    """Per-clip CTC loss (B,) of logits (B, T, V) on the device (paa_ctc, HF reduction 'sum' per clip); ``frames`` (B) int32 on
+    the device (``model.frame_counts``): clip b aligns over its first frames[b] frames (paa_ctc_len)."""
     lab = labels.to(device=logits.device, dtype=torch.int32).contiguous()
     B, T, V = logits.shape
     S = lab.shape[1]
@@ -151,6 +189,12 @@ def clip_nll(model, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     work = torch.empty(int(L.paa_ctc_work_floats(B, T, V, S)), dtype=torch.float32, device=logits.device)
     nll = torch.empty(B, dtype=torch.float32, device=logits.device)
     with torch.cuda.device(logits.device):
-        _lib.check(L.paa_ctc(_lib.ptr(logits.contiguous()), _lib.ptr(lab), B, T, V, S, int(model.arch.pad_token_id), 1.0,
-                             _lib.ptr(nll), None, _lib.ptr(work), _lib.stream_ptr()))
+        if frames is None:
+            _lib.check(L.paa_ctc(_lib.ptr(logits.contiguous()), _lib.ptr(lab), B, T, V, S, int(model.arch.pad_token_id), 1.0,
+                                 _lib.ptr(nll), None, _lib.ptr(work), _lib.stream_ptr()))
+        else:
+            if frames.dtype != torch.int32 or frames.device != logits.device or frames.numel() < B:
+                raise ValueError(f"frames must be int32 ({B},) on the device of the logits")
+            _lib.check(L.paa_ctc_len(_lib.ptr(logits.contiguous()), _lib.ptr(lab), _lib.ptr(frames), B, T, V, S,
+                                     int(model.arch.pad_token_id), 1.0, _lib.ptr(nll), None, _lib.ptr(work), _lib.stream_ptr()))
     return nll

@@ -49,33 +49,47 @@ def _pert(pp, B):
     return pp.rows(B) if isinstance(pp, _PlacedEval) else pp
 
 
-def _evaluate_device(args, eval_data_loader, pp, model, processor, canon) -> Scores:
+def _set_lengths(model, lengths, B):
+    """This batch's true sample counts into the model's length buffer -> its frame counts T_b (device int32), or None when the
+    batch carries none (--clip_lengths padded)."""
+    if lengths is None:
+        return None
+    model.set_lengths(lengths)
+    return model.frame_counts(B)
+
+
+def _evaluate_device(args, eval_data_loader, pp, model, processor, canon, lengths_mode=False) -> Scores:
     """evaluate with the WER counted on the device (--device_wer): forward -> paa_argmax_ids + paa_wer_counts -> one row of
     [CTC loss, ..., word errors, reference words] appended to a device log; no .item() and no host decode in the loop, ONE
     readback at the end (and, sharded over ranks, one all-reduce of the rows instead of two).  A batch whose references do not fit
     the device rows takes the host route for its counters."""
     from .pgd import N_STATS, ST_LOSS, ST_WER_ERR, ST_WER_REF, StatsLog
+    from .pgd import batch_lengths
     from .train import log_host_route, wer_of_rows
     dev = model.device
+    blank = int(model.arch.pad_token_id)
     log = StatsLog(dev, 1024, N_STATS)
     st = torch.zeros(N_STATS, dtype=torch.float32, device=dev)
     canon = canon.to(dev)
     chunks, host, n = [], {}, 0
-    for data, target_texts in eval_data_loader:
+    for batch in eval_data_loader:
+        data, target_texts, lengths = batch_lengths(batch, lengths_mode)
         if len(target_texts) == 0:           # an empty shard of a short global batch: a row of zeros for the all-reduce
             st.zero_()
         else:
             data = data.to(args.device, torch.float32).contiguous()
             labels = loss_helpers.make_labels(target_texts, processor, args, len(data))
+            frames = _set_lengths(model, lengths, len(data))
             r = model.forward(data, _pert(pp, len(data)), labels, clamp=False)
             st[ST_LOSS].copy_(r["loss"])
             refs = loss_helpers.encode_refs(target_texts)
             if refs is None:
                 log_host_route("evaluate", f"a reference needs more than {loss_helpers.R_CAP} entries")
-                host[n] = loss_helpers.wer_counts(*loss_helpers.wer_texts(r["logits"], target_texts, processor))
+                host[n] = loss_helpers.wer_counts(*loss_helpers.wer_texts(r["logits"], target_texts, processor, frames, blank))
                 st[ST_WER_ERR:ST_WER_REF + 1].zero_()
             else:
-                loss_helpers.wer_counts_device(r["logits"], refs, canon, sums=st[ST_WER_ERR:ST_WER_REF + 1])
+                loss_helpers.wer_counts_device(r["logits"], refs, canon, sums=st[ST_WER_ERR:ST_WER_REF + 1], frames=frames,
+                                               blank=blank)
         log.push(st)
         n += 1
         if n % log.cap == 0:
@@ -95,26 +109,33 @@ def _evaluate_device(args, eval_data_loader, pp, model, processor, canon) -> Sco
 
 
 def evaluate(args, eval_data_loader, p, model, processor, wer_metric, perturbed=False, epoch_number=-1) -> Scores:
+    from .pgd import batch_lengths, check_clip_lengths
+    lengths_mode = check_clip_lengths(args)          # refusals of --clip_lengths true: before any launch or collective
     ctc_scores, wer_scores, counts = [], [], []
     pp = None
     if perturbed and isinstance(p, torch.Tensor):
         pp = p.detach().to(model.device, torch.float32).reshape(1, -1).contiguous()
         if place.placement_on(args) or rir.rir_on(args):
             pp = _PlacedEval(args, model, pp)
+    if not lengths_mode and model.lengths_on:
+        model.set_lengths(None)                      # padded means padded, whatever an earlier caller left behind
+    blank = int(model.arch.pad_token_id)
     if getattr(args, "device_wer", False):
         from .train import device_wer_canon
         canon = device_wer_canon(args, processor, wer_metric, "evaluate")
         if canon is not None:
-            return _evaluate_device(args, eval_data_loader, pp, model, processor, canon)
-    for data, target_texts in eval_data_loader:
+            return _evaluate_device(args, eval_data_loader, pp, model, processor, canon, lengths_mode)
+    for batch in eval_data_loader:
+        data, target_texts, lengths = batch_lengths(batch, lengths_mode)
         if len(target_texts) == 0:           # an empty shard of a short global batch (build.shard_batches): zeros for the all-reduce
             ctc_scores.append(0.0); wer_scores.append(0.0); counts.append((0, 0))
             continue
         data = data.to(args.device, torch.float32).contiguous()
         labels = loss_helpers.make_labels(target_texts, processor, args, len(data))
+        frames = _set_lengths(model, lengths, len(data))
         r = model.forward(data, _pert(pp, len(data)), labels, clamp=False)
         ctc_scores.append(float(r["loss"].item()))
-        pred_texts, ref_texts = loss_helpers.wer_texts(r["logits"], target_texts, processor)
+        pred_texts, ref_texts = loss_helpers.wer_texts(r["logits"], target_texts, processor, frames, blank)
         e, w = loss_helpers.wer_counts(pred_texts, ref_texts)
         counts.append((e, w))
         wer_scores.append(float(wer_metric.compute(predictions=pred_texts, references=ref_texts)) if wer_metric is not None

@@ -97,6 +97,10 @@ def create_arg_parser():
                         help='random: every clip of every step sees the perturbation at a circular shift of its own')
     parser.add_argument('--place_gain_db', type=_place_gain_db, default=0.0,
                         help='G in [0, 20]: every clip of every step sees the perturbation at a gain uniform in [-G, +G] dB')
+    # true clip lengths (extension); the default leaves every object and file as it is
+    parser.add_argument('--clip_lengths', type=str, choices=["padded", "true"], default="padded",
+                        help='true: batches carry every clip\'s own sample count and the model masks the padding as HuggingFace does '
+                             'with an attention_mask (compose, attention keys, CTC length, decode); padded: the padding is audio')
     # room responses on the placement layer (extension); the default leaves the step as it is
     parser.add_argument('--rir_bank', type=str, default="none",
                         help='none | synthetic | PATH (.npy or weights-only .pt holding a float (N, K) array): every clip of every '

@@ -22,8 +22,19 @@
     only; runs the placement launches too,     paa_rir_apply (adjoint)                                    between the backward pass and
     at shift 0 / gain 1 when placement is off)                                                            paa_place_reduce
 
-A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off and room responses off are the plain step, bit
-for bit.
+    true clip lengths (``lengths=`` /          inside paa_model_fwd_bwd{,_rows}: frame counts, zeroed      DESIGN.md §6h
+    ``set_lengths``)                           frames, masked compose / attention / CTC
+                                               paa_model_frame_counts, paa_argmax_ids_len                 in place of paa_argmax_ids (device WER)
+                                               paa_mask_tail_rows (per-clip step only)                    after every paa_project_rows
+
+A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off and lengths off are the
+plain step, bit for bit.
+
+True clip lengths: ``step`` / ``capture`` take ``lengths=`` like ``labels`` — per-clip sample counts, validated on
+the host and copied into the model's ONE persistent device buffer (``PaaModel.set_lengths``), which every kernel reads on the
+stream: a captured graph follows ``set_lengths`` without re-capture.  ``lengths=None`` leaves the model as it is (off by default);
+``set_lengths(None)`` switches the mode off.  Whether the mode is on is fixed by ``capture()``.  The masking norm, the masking loss,
+placement and room responses are refused under lengths (``lengths_refusal``).
 
 The packed vector is ``[ grad (Lp) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, masking loss, 0 ]`` in
 float32; the 8 stat slots are defined HERE (ST_*) and documented in include/paa_hip.h (paa_model_fwd_bwd, d_stats).  Every rank
@@ -87,6 +98,47 @@ def adam_unsupported(optimizer):
     if any(isinstance(x, torch.Tensor) for x in (g["lr"], *g["betas"], g["eps"])):
         return "tensor hyper-parameters"
     return None
+
+
+def lengths_refusal(args):
+    """None, or why ``args`` cannot run with true clip lengths (``--clip_lengths true``): the masking norm and the masking loss
+    take a batch-minimum threshold over clips that have already ended, and placement / room responses move the perturbation
+    across the clip's end — each needs a design of its own."""
+    if "masking" in str(getattr(args, "norm_type", "")).split("+"):
+        return "--clip_lengths true does not support --norm_type masking"
+    if float(getattr(args, "masking_loss_alpha", 0.0) or 0.0) > 0:
+        return "--clip_lengths true does not support --masking_loss_alpha > 0"
+    if place.placement_on(args):
+        return "--clip_lengths true does not support placement (--perturbation_seconds, --place_shift, --place_gain_db)"
+    if rir.rir_on(args):
+        return "--clip_lengths true does not support --rir_bank"
+    return None
+
+
+def unpack_batch(batch):
+    """A loader item, (x, texts) or (x, texts, lengths) -> (x, texts, lengths | None): consumers accept both tuple forms."""
+    if len(batch) == 3:
+        return batch[0], batch[1], batch[2]
+    x, texts = batch
+    return x, texts, None
+
+
+def batch_lengths(batch, lengths_mode: bool):
+    """(x, texts, lengths) of a loader item in either tuple form; --clip_lengths true needs the lengths, padded ignores them."""
+    x, texts, lengths = unpack_batch(batch)
+    if lengths_mode and lengths is None:
+        raise ValueError("--clip_lengths true needs loaders that yield (x, texts, lengths)")
+    return x, texts, (lengths if lengths_mode else None)
+
+
+def check_clip_lengths(args):
+    """Refusals of ``--clip_lengths true``, raised before any launch or collective; True when the mode is on."""
+    on = str(getattr(args, "clip_lengths", "padded")) == "true"
+    if on:
+        why = lengths_refusal(args)
+        if why is not None:
+            raise ValueError(why)
+    return on
 
 
 def masking_route(norm_type, world: int) -> None:
@@ -188,6 +240,39 @@ class _StepperCore:
         self._ring = _HostRing(4, self.dev) if (self.collective or optimizer is not None) else None
         self._init_masking_loss()
         self._init_device_wer(device_wer, canon, r_cap, log_cap)
+        self._lengths_captured = None        # capture() records whether the captured launch sequence runs in the length mode
+
+    # ---- true clip lengths ------------------------------------------------------------------------------------------
+    @property
+    def lengths_on(self):
+        return bool(self.model.lengths_on)
+
+    def set_lengths(self, lengths):
+        """Per-clip sample counts from the next step on (host-validated, copied into the model's persistent buffer; a captured
+        graph follows it), or None to switch the mode off.  Refused for the modes ``lengths_refusal`` names, and — like the
+        masking loss — the mode cannot be switched on or off after ``capture()``."""
+        on = lengths is not None
+        if on:
+            why = lengths_refusal(self.args)
+            if why is None and self.mask_alpha > 0:
+                why = "--clip_lengths true does not support --masking_loss_alpha > 0"
+            if why is not None:
+                raise ValueError(why)
+        if self._lengths_captured is not None and on != self._lengths_captured:
+            raise ValueError("clip lengths cannot be switched on or off after capture(): the captured launch sequence "
+                             f"{'runs' if self._lengths_captured else 'does not run'} in the length mode; capture the step again")
+        with torch.cuda.device(self.dev):
+            return self.model.set_lengths(lengths)
+
+    def _frames(self, B):
+        """T_b of the model's current length buffer in a fixed int32 buffer (one launch, capturable); None with lengths off."""
+        if not self.lengths_on:
+            return None
+        if getattr(self, "frames_buf", None) is None:
+            self.frames_buf = torch.ones(int(self.model.max_batch), dtype=torch.int32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().paa_model_frame_counts(self.model.h, int(B), _lib.ptr(self.frames_buf), _lib.stream_ptr()))
+        return self.frames_buf
 
     # ---- on-device WER counters and the stats log ----------------------------------------------------------------
     def _init_device_wer(self, device_wer, canon=None, r_cap=None, log_cap=4096):
@@ -221,7 +306,8 @@ class _StepperCore:
         from ..core import loss_helpers
         self.wer_batch = B
         loss_helpers.wer_counts_device(logits, self.refs[:B], self.canon, out=self.wer_rows[:B],
-                                       sums=self.stats[ST_WER_ERR:ST_WER_REF + 1], ids_out=self.ids[: B * logits.shape[1]])
+                                       sums=self.stats[ST_WER_ERR:ST_WER_REF + 1], ids_out=self.ids[: B * logits.shape[1]],
+                                       frames=self._frames(B), blank=int(self.model.arch.pad_token_id))
 
     def read_log(self):
         """The stats rows of the steps since the last call, oldest first: CPU float32 (n, N_STATS), global sums after the
@@ -248,6 +334,8 @@ class _StepperCore:
         alpha = float(alpha)
         if alpha < 0:
             raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
+        if alpha > 0 and getattr(getattr(self, "model", None), "lengths_on", False):
+            raise ValueError("--clip_lengths true does not support --masking_loss_alpha > 0")
         if self._alpha_captured is not None and (alpha > 0) != self._alpha_captured:
             raise ValueError("masking_loss_alpha cannot switch between 0 and > 0 after capture(): the captured launch sequence "
                              f"{'holds' if self._alpha_captured else 'does not hold'} the loss term; capture the step again")
@@ -331,12 +419,17 @@ class _StepperCore:
         """The device tensors a step advances and the warm-up step of capture() hands back."""
         return [self.stats_log.cursor] if self.device_wer else []
 
-    def _warm_up(self, p, clean, labels, logits_out, refs):
+    def _warm_up(self, p, clean, labels, logits_out, refs, lengths=None):
         """What capture() does before it opens a graph: fixes the buffers the graph will point into (-> labels, logits_out), runs
         one eager step on a side stream, as torch's capture rules require, and undoes it — ``p``, the optimizer state and its
         step count, the log cursor (the log holds replayed steps only) and the leaf's ``_replay_state`` are as before."""
         lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
         self._alpha_captured = self.mask_alpha > 0
+        if lengths is not None:
+            self.set_lengths(lengths)
+        if self.lengths_on:
+            self._frames(clean.shape[0])                  # allocates the frame-count buffer outside the capture
+        self._lengths_captured = self.lengths_on
         saved = None
         if self.optimizer is not None:
             self._check_p(p)
@@ -537,12 +630,15 @@ class PgdStepper(_StepperCore):
         if self.device_wer:
             self.stats_log.push(self.stats)
 
-    def step(self, p: torch.Tensor, clean: torch.Tensor, labels: torch.Tensor, want_logits=True, logits_out=None, refs=None):
+    def step(self, p: torch.Tensor, clean: torch.Tensor, labels: torch.Tensor, want_logits=True, logits_out=None, refs=None,
+             lengths=None):
         """In place on ``p`` (1, L).  Returns dict(loss: 0-d device tensor, summed over ALL ranks, logits).  ``refs``
         (device_wer only): this batch's reference rows, copied to the fixed buffer first (``set_refs``); None keeps what the
-        buffer holds."""
+        buffer holds.  ``lengths``: this batch's true sample counts (``set_lengths``); None leaves the model as it is."""
         if refs is not None:
             self.set_refs(refs)
+        if lengths is not None:
+            self.set_lengths(lengths)
         p = runtime.as_f32_cuda(p, "p")
         clean = runtime.as_f32_cuda(clean, "clean_audio")
         if p.numel() != self.Lp or clean.shape[-1] != self.L:
@@ -567,7 +663,7 @@ class PgdStepper(_StepperCore):
         r["loss"] = self.stats[ST_LOSS]
         return r
 
-    def capture(self, p, clean, labels, logits_out=None, refs=None):
+    def capture(self, p, clean, labels, logits_out=None, refs=None, lengths=None):
         """Capture one step on fixed buffers into hipGraphs (the launch sequence allocates nothing and never
         synchronises, so it is capturable as is).  With device_wer, ``refs`` fills the fixed reference buffer (refresh it with
         ``set_refs`` before a replay) and the warm-up step's log row is taken back: the log holds replayed steps only.  Returns
@@ -585,8 +681,11 @@ class PgdStepper(_StepperCore):
         logits out of bounds.
 
         With placement the draw is inside the graph (the first one of the split form) and the warm-up step's draw is taken back:
-        the device step counter is as before the call, so the first replay draws what the first eager step would have."""
-        lab, logits_out = self._warm_up(p, clean, labels, logits_out, refs)
+        the device step counter is as before the call, so the first replay draws what the first eager step would have.
+
+        ``lengths`` as ``step``; the graph reads the model's length buffer, so ``set_lengths`` before a replay changes the clips'
+        lengths without re-capture."""
+        lab, logits_out = self._warm_up(p, clean, labels, logits_out, refs, lengths)
         if not self.collective:
             return self._capture_body(p, clean, lab, logits_out)
         # No collective may be in flight while a capture is open (the process group's watchdog thread polls its events), and the

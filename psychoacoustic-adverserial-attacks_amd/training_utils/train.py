@@ -14,7 +14,7 @@ import torch
 from .. import _lib, runtime
 from ..core import loss_helpers
 from . import place, rir
-from .pgd import FREQ_NORMS, PgdStepper, adam_unsupported
+from .pgd import FREQ_NORMS, PgdStepper, adam_unsupported, batch_lengths, check_clip_lengths
 
 logger = logging.getLogger(__name__)
 
@@ -153,6 +153,10 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
                                   "or --optimizer_type pgd")
     place.check(args, L, Lp, eager_adam)
     rir.check(args, eager_adam)
+    lengths_mode = check_clip_lengths(args)          # refusals of --clip_lengths true: before any launch or collective
+    if lengths_mode and eager_adam:
+        raise NotImplementedError("--clip_lengths true needs the device step: use the defaults of torch.optim.Adam(lr=...) or "
+                                  "--optimizer_type pgd")
     mask_scores = []
     canon = None if eager_adam else device_wer_canon(args, processor, wer_metric, "train_epoch")
     if eager_adam and getattr(args, "device_wer", False):
@@ -167,18 +171,22 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
             stepper.set_place_step(int(epoch) * len(train_data_loader))
         if stepper.rir_on:            # the same for the room draw's counter
             stepper.set_rir_step(int(epoch) * len(train_data_loader))
+    if not lengths_mode and stepper.lengths_on:
+        stepper.set_lengths(None)             # a model left in the length mode by an earlier caller: padded means padded
     if canon is not None:
-        return _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alpha)
-    for clean_audio, target_texts in train_data_loader:
+        return _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alpha, lengths_mode)
+    blank = int(model.arch.pad_token_id)
+    for batch in train_data_loader:
+        clean_audio, target_texts, lengths = batch_lengths(batch, lengths_mode)
         t0 = time.perf_counter()
         clean_audio = clean_audio.to(args.device, torch.float32, non_blocking=True).contiguous()   # train.py:129
         labels = loss_helpers.make_labels(target_texts, processor, args, len(clean_audio))
         if args.optimizer_type == "pgd":
             if isinstance(p, torch.nn.Parameter) or p.requires_grad:
                 p = p.detach()
-            r = stepper.step(p, clean_audio, labels)
+            r = stepper.step(p, clean_audio, labels, lengths=lengths)
         elif not eager_adam:
-            r = stepper.step(p.data, clean_audio, labels)          # p.grad = -grad, as train.py:170 leaves it
+            r = stepper.step(p.data, clean_audio, labels, lengths=lengths)     # p.grad = -grad, as train.py:170 leaves it
         else:
             if p.dtype != torch.float32 or not p.is_cuda:
                 raise TypeError(f"the Adam branch needs a float32 perturbation on the GPU, got {p.dtype} on {p.device}")
@@ -191,7 +199,8 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
         ctc_scores.append(float(r["loss"].item()))                                   # train.py:146
         if mask_alpha > 0:
             mask_scores.append(float(r["masking_loss"].item()))
-        pred_texts, ref_texts = loss_helpers.wer_texts(r["logits"], target_texts, processor)       # train.py:149-153
+        frames = model.frame_counts(len(clean_audio)) if lengths_mode else None
+        pred_texts, ref_texts = loss_helpers.wer_texts(r["logits"], target_texts, processor, frames, blank)   # train.py:149-153
         e, w = loss_helpers.wer_counts(pred_texts, ref_texts)
         wer_counts.append((e, w))
         stepper.set_wer_counts(e, w)          # rides behind the next step's gradient (stats[3:5] = sums over ranks)
@@ -204,7 +213,7 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
                             avg_masking_loss=_avg(mask_scores) if mask_alpha > 0 else None)
 
 
-def _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alpha) -> TrainEpochResult:
+def _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alpha, lengths_mode=False) -> TrainEpochResult:
     """train_epoch with the WER counted on the device (--device_wer): the loop body launches the step and nothing else — no
     .item(), no id download, no host decode — and the per-step CTC loss, masking loss and word counters come back in ONE
     readback of the stepper's stats log at the end of the epoch (already global sums with several ranks: they rode the step's
@@ -212,7 +221,8 @@ def _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alp
     WER, one rank only."""
     rows, host_wer, n = [], {}, 0
     stepper.stats_log.cursor.zero_()          # stream-ordered: rows a caller left unread do not count as this epoch's
-    for clean_audio, target_texts in train_data_loader:
+    for batch in train_data_loader:
+        clean_audio, target_texts, lengths = batch_lengths(batch, lengths_mode)
         clean_audio = clean_audio.to(args.device, torch.float32, non_blocking=True).contiguous()   # train.py:129
         labels = loss_helpers.make_labels(target_texts, processor, args, len(clean_audio))
         refs = loss_helpers.encode_refs(target_texts, stepper.r_cap)
@@ -226,11 +236,13 @@ def _train_epoch_device(args, train_data_loader, p, stepper, processor, mask_alp
         if args.optimizer_type == "pgd":
             if isinstance(p, torch.nn.Parameter) or p.requires_grad:
                 p = p.detach()
-            r = stepper.step(p, clean_audio, labels, refs=refs)
+            r = stepper.step(p, clean_audio, labels, refs=refs, lengths=lengths)
         else:
-            r = stepper.step(p.data, clean_audio, labels, refs=refs)          # p.grad = -grad, as train.py:170 leaves it
+            r = stepper.step(p.data, clean_audio, labels, refs=refs, lengths=lengths)   # p.grad = -grad, as train.py:170 leaves it
         if not fits:
-            host_wer[n] = loss_helpers.wer_counts(*loss_helpers.wer_texts(r["logits"], target_texts, processor))
+            frames = stepper.model.frame_counts(len(clean_audio)) if lengths_mode else None
+            host_wer[n] = loss_helpers.wer_counts(*loss_helpers.wer_texts(r["logits"], target_texts, processor, frames,
+                                                                          int(stepper.model.arch.pad_token_id)))
         n += 1
         if n % stepper.stats_log.cap == 0:
             rows.append(stepper.read_log())
