@@ -21,7 +21,7 @@ import torch
 
 from .core import iso, loss_helpers
 from .core.masking import masking_loss
-from .training_utils import build, parser, pgd, place, rir, save
+from .training_utils import build, modes, parser, save
 from .training_utils.clip_attack import ClipStepper, clip_nll, compose_rows, init_rows, project_rows
 
 SPLITS = ("test", "val", "train")
@@ -44,13 +44,13 @@ def clip_batches(batches, rank: int = 0, world: int = 1):
     lengths]).  The index of a clip is its position in the split, whatever the batch size or the number of ranks."""
     tagged, first = [], 0
     for batch in batches:
-        x, texts, lengths = pgd.unpack_batch(batch)
+        x, texts, lengths = build.unpack_batch(batch)
         idx = list(range(first, first + len(texts)))
         first += len(texts)
         tagged.append((x, list(zip(idx, texts))) if lengths is None else (x, list(zip(idx, texts)), lengths))
     out = []
     for shard in build.shard_batches(tagged, rank, world, keep_empty=True):
-        x, pairs, lengths = pgd.unpack_batch(shard)
+        x, pairs, lengths = build.unpack_batch(shard)
         if len(pairs):
             item = (x, [t for _, t in pairs], [i for i, _ in pairs])
             out.append(item if lengths is None else item + (lengths,))
@@ -159,8 +159,7 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
     linf = dm.abs().amax(dim=1).cpu()
     sig = xm.double().pow(2).sum(dim=1).cpu()
     noise = dm.double().pow(2).sum(dim=1).cpu()
-    mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
-    mloss = masking_loss(delta, x, args)[0].cpu() if mask_alpha > 0 else None
+    mloss = masking_loss(delta, x, args)[0].cpu() if modes.Modes.of(args).alpha > 0 else None
     records = []
     for b in range(B):
         rec = {"index": int(idx[b]), "clean_wer": clean_w[b], "adv_wer": adv_w[b],
@@ -177,24 +176,14 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
 
 
 def main(args) -> int:
-    place.refuse_for_clips(args)
-    rir.refuse_for_clips(args)
-    lengths_mode = pgd.check_clip_lengths(args)          # refusals of --clip_lengths true: before any launch or collective
+    # what per-clip perturbations do not run with, and the refusals of --clip_lengths true: before any launch or collective
+    lengths_mode = modes.check(modes.Modes.of(args), ("place_clips", "rir_clips") + modes.LENGTHS).lengths_on
     if not torch.cuda.is_available():
         raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")
     if not str(args.device).startswith("cuda"):
         args.device = "cuda"
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    if world > 1:
-        local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
-        torch.cuda.set_device(local)
-        args.device = f"cuda:{local}"
-        if not torch.distributed.is_initialized():
-            backend = os.environ.get("PAA_DIST_BACKEND", "nccl")
-            if backend == "nccl":
-                torch.distributed.init_process_group("nccl", device_id=torch.device(args.device))
-            else:
-                torch.distributed.init_process_group(backend)
+    build.start_process_group(args, world)
     args.attack_size_string = build.attack_size_string(args)
     root = getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,

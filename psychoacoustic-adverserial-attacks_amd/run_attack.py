@@ -12,7 +12,7 @@ import sys
 import torch
 
 from .core import iso
-from .training_utils import build, evaluation, parser, pgd, place, rir, save, scoring_helpers, train
+from .training_utils import build, evaluation, modes, parser, place, rir, save, scoring_helpers, train
 
 
 def main(args) -> int:
@@ -23,22 +23,14 @@ def main(args) -> int:
     # launched by torch.distributed.run with several ranks: one process per GPU, RCCL ("nccl") over xGMI, utterances
     # sharded over ranks; every rank keeps the same p, rank 0 writes the files
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    pgd.masking_route(args.norm_type, world)          # before any collective: every rank raises
-    place.check_flags(args)                           # the same for what placement does not combine with at any length
-    rir.check_flags(args)                             # and for room responses
-    pgd.check_clip_lengths(args)                      # and for true clip lengths
-    if world > 1:
-        local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
-        torch.cuda.set_device(local)
-        args.device = f"cuda:{local}"
-        if not torch.distributed.is_initialized():
-            backend = os.environ.get("PAA_DIST_BACKEND", "nccl")
-            if backend == "nccl":
-                torch.distributed.init_process_group("nccl", device_id=torch.device(args.device))
-            else:
-                torch.distributed.init_process_group(backend)
-        if rank != 0:
-            args.silent = True
+    # refusals before any collective, so that every rank raises
+    m = modes.check(modes.Modes.of(args), ("route",), modes.Ctx(world))
+    place.check_flags(args)
+    rir.check_flags(args)
+    mask_alpha = modes.check(m, modes.LENGTHS).alpha
+    build.start_process_group(args, world)
+    if world > 1 and rank != 0:
+        args.silent = True
     logger, start_epoch = build.create_logger(args)
     logger.info("Using device: %s", args.device)
     interp = iso.build_weight_interpolator()
@@ -58,7 +50,6 @@ def main(args) -> int:
     writer = rank == 0
     optimizer, scheduler = (build.create_optimizer(args, p) if args.optimizer_type == "adam" else (None, None))
     hist = {k: [] for k in ("train_ctc", "train_wer", "clean_ctc", "clean_wer", "pert_ctc", "pert_wer")}
-    mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
     extra = {}          # results.json keys of the masking-threshold loss term: present only when masking_loss_alpha > 0
     place_extra = place.results_extra(args, p.shape[-1])          # and those of placement, present only when it is on
     place_extra.update(rir.results_extra(args))                   # and those of room responses, likewise

@@ -13,8 +13,7 @@ from .. import synth
 from ..core import iso
 from ..model import PaaModel
 from . import place, rir
-from .pgd import unpack_batch
-from .train import perturbation_constraint
+from .modes import Modes
 
 
 def init_phon_threshold_tensor(args):
@@ -28,6 +27,7 @@ def init_perturbation(args, length, spl_thresh, interp, first_batch_data):
     projection.  Resume: a (1, L) float32 tensor saved with torch.save (loaded with weights_only=True).  With placement on
     (training_utils/place.py) the perturbation has Lp = place.perturbation_length(args, length) samples; the initial
     projection then sees the first batch only when Lp equals the clip length."""
+    from .train import perturbation_constraint
     clip_length, length = length, (place.perturbation_length(args, length) if place.placement_on(args) else length)
     place.check(args, clip_length, length)
     if length != clip_length:
@@ -77,7 +77,38 @@ def create_optimizer(args, p):
 
 def lengths_on(args) -> bool:
     """--clip_lengths true: loaders yield (x, texts, lengths) instead of (x, texts)."""
-    return str(getattr(args, "clip_lengths", "padded")) == "true"
+    return Modes.of(args).lengths_on
+
+
+def unpack_batch(batch):
+    """A loader item, (x, texts) or (x, texts, lengths) -> (x, texts, lengths | None): consumers accept both tuple forms."""
+    if len(batch) == 3:
+        return batch[0], batch[1], batch[2]
+    x, texts = batch
+    return x, texts, None
+
+
+def batch_lengths(batch, lengths_mode: bool):
+    """(x, texts, lengths) of a loader item in either tuple form; --clip_lengths true needs the lengths, padded ignores them."""
+    x, texts, lengths = unpack_batch(batch)
+    if lengths_mode and lengths is None:
+        raise ValueError("--clip_lengths true needs loaders that yield (x, texts, lengths)")
+    return x, texts, (lengths if lengths_mode else None)
+
+
+def start_process_group(args, world: int) -> None:
+    """Several ranks: bind this one to its GPU (LOCAL_RANK) and join the process group, RCCL ("nccl") unless PAA_DIST_BACKEND."""
+    if world <= 1:
+        return
+    local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
+    torch.cuda.set_device(local)
+    args.device = f"cuda:{local}"
+    if not torch.distributed.is_initialized():
+        backend = os.environ.get("PAA_DIST_BACKEND", "nccl")
+        if backend == "nccl":
+            torch.distributed.init_process_group("nccl", device_id=torch.device(args.device))
+        else:
+            torch.distributed.init_process_group(backend)
 
 
 def synthetic_lengths(n: int, length: int, seed: int, first_clip: int = 0) -> torch.Tensor:
@@ -135,7 +166,7 @@ def attack_size_string(args) -> str:
 def masking_loss_suffix(args) -> str:
     """Run-directory suffix of the masking-threshold loss term: "_ml<alpha>" when masking_loss_alpha > 0, else empty, so a
     run without the term keeps the directory it always had (and resumes from it)."""
-    alpha = float(getattr(args, "masking_loss_alpha", 0.0))
+    alpha = Modes.of(args).alpha
     return f"_ml{alpha:g}" if alpha > 0 else ""
 
 

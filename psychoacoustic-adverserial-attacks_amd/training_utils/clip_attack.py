@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from .. import _lib, runtime, synth
-from .pgd import N_STATS, ST_LOSS, _StepperCore, lengths_refusal
+from .modes import LENGTHS, Modes, check, replace
+from .pgd import N_STATS, ST_LOSS, _StepperCore
 
 
 class ClipStepper(_StepperCore):
@@ -141,10 +142,9 @@ def mask_tail_rows(delta: torch.Tensor, lengths) -> torch.Tensor:
 def project_rows(delta: torch.Tensor, clean: torch.Tensor, args, interp=None, spl_thresh=None, lengths=None) -> torch.Tensor:
     """perturbation_constraint (train.py:69-99) on every row of ``delta`` (B, L) against its own clip of ``clean`` (B, L),
     in place; the norms of ``args.norm_type`` in order.  ``lengths``: delta_b[len_b:] is re-zeroed after every projection."""
+    m = Modes.of(args)
     if lengths is not None:
-        why = lengths_refusal(args)
-        if why is not None:
-            raise ValueError(why)
+        check(replace(m, lengths_on=True), LENGTHS)
     delta = runtime.as_f32_cuda(delta, "delta")
     clean = runtime.as_f32_cuda(clean, "clean_audio")
     if delta.dim() != 2 or tuple(delta.shape) != tuple(clean.shape):
@@ -152,7 +152,7 @@ def project_rows(delta: torch.Tensor, clean: torch.Tensor, args, interp=None, sp
     B, L = delta.shape
     pr = runtime.get_proj(args, delta.device, B, L, interp)
     with torch.cuda.device(delta.device):
-        for n in str(args.norm_type).split("+"):
+        for n in m.norms:
             if n not in _lib.NORM_IDS:
                 raise ValueError(f"Unknown norm_type: {n!r}")
             if n == "max_phon":

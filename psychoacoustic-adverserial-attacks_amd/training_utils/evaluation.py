@@ -5,7 +5,8 @@ from __future__ import annotations
 import torch
 
 from ..core import loss_helpers
-from . import place, rir
+from . import modes, place, rir
+from .build import batch_lengths
 from .scoring_helpers import Scores
 
 
@@ -16,32 +17,14 @@ class _PlacedEval:
     rooms; with placement itself off the rows are the perturbation at shift 0 and gain 1."""
 
     def __init__(self, args, model, pp):
-        rank = 0
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            rank = torch.distributed.get_rank()
-        nb, L = int(model.max_batch), int(model.length)
-        seed = getattr(args, "place_seed", None)
-        seed = int(getattr(args, "seed", 5) if seed is None else seed)
-        place.check(args, L, pp.numel())
-        self.pp = pp
-        self.placer = place.Placer(model.device, nb, L, pp.numel(), seed, place.STREAM_EVAL, place.shift_on(args),
-                                   place.gain_db(args), clip_base=rank * nb, with_grad=False)
-        self.reverb = None
-        if not place.placement_on(args):
-            self.placer.set_placement([0] * nb)
-        if rir.rir_on(args):
-            rir.check(args)
-            self.reverb = rir.Reverb(model.device, rir.bank_of(args), nb, L, rir.draw_seed(args), place.STREAM_EVAL,
-                                     clip_base=rank * nb, with_grad=False)
+        rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
+        place.check(args, int(model.length), pp.numel())
+        place.shift_on(args), place.gain_db(args)          # rooms alone still place: these two flags are read before the rooms'
+        rir.check(args)
+        self.pp, self.placed = pp, rir.PlacedRows(args, model, pp.numel(), place.STREAM_EVAL, False, rank)
 
     def rows(self, B):
-        if not self.placer.explicit:
-            self.placer.draw(B)
-        rows = self.placer.place(self.pp, B)
-        if self.reverb is not None:
-            self.reverb.draw(B)
-            rows = self.reverb.apply(self.placer.rows, B)
-        return rows
+        return self.placed.rows(self.pp, B)
 
 
 def _pert(pp, B):
@@ -64,7 +47,6 @@ def _evaluate_device(args, eval_data_loader, pp, model, processor, canon, length
     readback at the end (and, sharded over ranks, one all-reduce of the rows instead of two).  A batch whose references do not fit
     the device rows takes the host route for its counters."""
     from .pgd import N_STATS, ST_LOSS, ST_WER_ERR, ST_WER_REF, StatsLog
-    from .pgd import batch_lengths
     from .train import log_host_route, wer_of_rows
     dev = model.device
     blank = int(model.arch.pad_token_id)
@@ -109,18 +91,18 @@ def _evaluate_device(args, eval_data_loader, pp, model, processor, canon, length
 
 
 def evaluate(args, eval_data_loader, p, model, processor, wer_metric, perturbed=False, epoch_number=-1) -> Scores:
-    from .pgd import batch_lengths, check_clip_lengths
-    lengths_mode = check_clip_lengths(args)          # refusals of --clip_lengths true: before any launch or collective
+    m = modes.check(modes.Modes.of(args), modes.LENGTHS)          # refusals of --clip_lengths true: before any launch or collective
+    lengths_mode = m.lengths_on
     ctc_scores, wer_scores, counts = [], [], []
     pp = None
     if perturbed and isinstance(p, torch.Tensor):
         pp = p.detach().to(model.device, torch.float32).reshape(1, -1).contiguous()
-        if place.placement_on(args) or rir.rir_on(args):
+        if m.place_on or m.rir_on:
             pp = _PlacedEval(args, model, pp)
     if not lengths_mode and model.lengths_on:
         model.set_lengths(None)                      # padded means padded, whatever an earlier caller left behind
     blank = int(model.arch.pad_token_id)
-    if getattr(args, "device_wer", False):
+    if m.device_wer:
         from .train import device_wer_canon
         canon = device_wer_canon(args, processor, wer_metric, "evaluate")
         if canon is not None:

@@ -1,0 +1,94 @@
+"""Which modes of the PGD step are on and which may run together: decided here and nowhere else.  ``Modes.of(args)``
+reads every mode flag once; ``RULES`` is the table of refusals: the mode a rule belongs to, its condition over (modes, context), the
+exception and its message.  ``check`` walks the rules it is given and raises the first that applies; the order of a walk, and of the
+walks of an entry point, decides which refusal wins."""
+from __future__ import annotations
+
+from collections import namedtuple
+from dataclasses import dataclass, replace  # noqa: F401  (replace: how a caller forces a mode on)
+
+GAIN_DB_MAX = 20.0
+
+
+@dataclass(frozen=True)
+class Modes:
+    norms: tuple                   # --norm_type, '+'-separated, in the written order
+    masking_norm: bool
+    alpha: float                   # --masking_loss_alpha
+    place_on: bool                 # perturbation_seconds set, place_shift == "random" or place_gain_db > 0
+    place_shift: str
+    gain_db: float
+    rir_on: bool                   # rir_bank other than "none"
+    lengths_on: bool               # --clip_lengths true
+    device_wer: bool
+    optimizer_type: str
+
+    @classmethod
+    def of(cls, args=None, **flags):
+        """The record of ``args`` (any object; a missing flag is off), ``flags`` overriding."""
+        get = lambda k, d: flags.get(k, getattr(args, k, d))
+        _num = lambda v: float(v) if isinstance(v, (int, float, str)) else v      # no number: kept, and raises where it is compared
+        norms = tuple(str(get("norm_type", "")).split("+"))
+        shift, gain, alpha = get("place_shift", "none"), _num(get("place_gain_db", 0.0)), _num(get("masking_loss_alpha", 0.0) or 0.0)
+        on = get("perturbation_seconds", None) is not None or shift == "random" or (isinstance(gain, float) and gain > 0)
+        return cls(norms, "masking" in norms, alpha, on, shift, gain, str(get("rir_bank", "none")) != "none",
+                   str(get("clip_lengths", "padded")) == "true", bool(get("device_wer", False)), get("optimizer_type", None))
+
+    shift_on = property(lambda m: m.place_shift == "random")
+    masking = property(lambda m: m.masking_norm or m.alpha > 0)      # either pairs delta's frames with the clean clip's
+
+
+# eager_adam: torch's own optimizer.step() runs the update, not the device step; L / Lp: clip / perturbation length, where known
+Ctx = namedtuple("Ctx", "world eager_adam L Lp", defaults=(1, False, None, None))
+# mode: the field of Modes that must be on for the rule to apply, or None; when(modes, ctx); msg: formatted with m = modes, c = ctx
+Rule = namedtuple("Rule", "mode when exc msg")
+_PAIRS = ": both pair the perturbation's frames with the clean clip's frames"
+_DEVICE_STEP = " the device step: use the defaults of torch.optim.Adam(lr=...) or --optimizer_type pgd"
+_NO_LEN = "--clip_lengths true does not support "
+_UNIVERSAL = "the universal perturbation (paa_amd.run_attack); per-clip perturbations have no "
+NIE = NotImplementedError
+RULES = {
+    "route": Rule("masking_norm", lambda m, c: c.world > 1, NIE, "the masking norm is not implemented for data-parallel universal "
+                  "perturbations (world size {c.world}): the bound would need a MIN-reduction across ranks; use one rank, or per-clip "
+                  "perturbations (paa_amd.attack_clips)"),
+    "alpha_range": Rule(None, lambda m, c: m.alpha < 0, ValueError, "masking_loss_alpha must be >= 0, got {m.alpha}"),
+    "alpha_eager": Rule(None, lambda m, c: c.eager_adam and m.alpha > 0, NIE, "masking_loss_alpha > 0 needs" + _DEVICE_STEP),
+    # placement
+    "shift_range": Rule("place_on", lambda m, c: m.place_shift not in ("none", "random"), ValueError,
+                        "place_shift must be 'none' or 'random', got {m.place_shift!r}"),
+    "gain_range": Rule("place_on", lambda m, c: not 0.0 <= m.gain_db <= GAIN_DB_MAX, ValueError,
+                       f"place_gain_db must be in [0, {GAIN_DB_MAX:g}], got {{m.gain_db}}"),
+    "place_masking": Rule("place_on", lambda m, c: m.masking, NIE, "placement (perturbation_seconds / place_shift / place_gain_db) is "
+                          "not implemented with the masking norm or masking_loss_alpha > 0" + _PAIRS),
+    "place_snr_tv": Rule("place_on", lambda m, c: c.Lp != c.L and any(n in ("snr", "tv") for n in m.norms), NIE,
+                         "the snr / tv norms need a perturbation as long as the clips (Lp = {c.Lp}, L = {c.L}): their bound "
+                         "compares the two sample for sample"),
+    "place_eager": Rule("place_on", lambda m, c: c.eager_adam, NIE, "placement needs" + _DEVICE_STEP),
+    "place_clips": Rule("place_on", lambda m, c: True, NIE,
+                        "--perturbation_seconds / --place_shift / --place_gain_db apply to " + _UNIVERSAL + "placement"),
+    # room responses
+    "rir_masking": Rule("rir_on", lambda m, c: m.masking, NIE,
+                        "room responses (rir_bank) are not implemented with the masking norm or masking_loss_alpha > 0" + _PAIRS),
+    "rir_eager": Rule("rir_on", lambda m, c: c.eager_adam, NIE, "room responses (rir_bank) need" + _DEVICE_STEP),
+    "rir_clips": Rule("rir_on", lambda m, c: True, NIE, "--rir_bank applies to " + _UNIVERSAL + "room responses yet"),
+    # true clip lengths: each of these needs a design of its own before it may meet them
+    "len_masking": Rule("lengths_on", lambda m, c: m.masking_norm, ValueError, _NO_LEN + "--norm_type masking"),
+    "len_alpha": Rule("lengths_on", lambda m, c: m.alpha > 0, ValueError, _NO_LEN + "--masking_loss_alpha > 0"),
+    "len_place": Rule("lengths_on", lambda m, c: m.place_on, ValueError,
+                      _NO_LEN + "placement (--perturbation_seconds, --place_shift, --place_gain_db)"),
+    "len_rir": Rule("lengths_on", lambda m, c: m.rir_on, ValueError, _NO_LEN + "--rir_bank"),
+    "len_eager": Rule("lengths_on", lambda m, c: c.eager_adam, NIE, "--clip_lengths true needs" + _DEVICE_STEP),
+}
+
+PLACE_FLAGS = ("shift_range", "gain_range", "place_masking")
+PLACE = PLACE_FLAGS + ("place_snr_tv", "place_eager")
+ROOMS = ("rir_masking", "rir_eager")
+LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir")
+
+
+def check(m: Modes, keys, c: Ctx = Ctx()) -> Modes:
+    """Raises the first of the rules ``keys`` that applies; returns ``m``."""
+    for r in map(RULES.get, keys):
+        if (r.mode is None or getattr(m, r.mode)) and r.when(m, c):
+            raise r.exc(r.msg.format(m=m, c=c))
+    return m

@@ -30,11 +30,8 @@
 A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off and lengths off are the
 plain step, bit for bit.
 
-True clip lengths: ``step`` / ``capture`` take ``lengths=`` like ``labels`` — per-clip sample counts, validated on
-the host and copied into the model's ONE persistent device buffer (``PaaModel.set_lengths``), which every kernel reads on the
-stream: a captured graph follows ``set_lengths`` without re-capture.  ``lengths=None`` leaves the model as it is (off by default);
-``set_lengths(None)`` switches the mode off.  Whether the mode is on is fixed by ``capture()``.  The masking norm, the masking loss,
-placement and room responses are refused under lengths (``lengths_refusal``).
+Which modes may run together, and which refusal wins when several apply, is decided in one table: training_utils/modes.py.  What
+a mode means is written where it is built: place.py, rir.py (§6g), ``set_lengths`` and PaaModel.set_lengths (§6h).
 
 The packed vector is ``[ grad (Lp) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, masking loss, 0 ]`` in
 float32; the 8 stat slots are defined HERE (ST_*) and documented in include/paa_hip.h (paa_model_fwd_bwd, d_stats).  Every rank
@@ -45,24 +42,10 @@ Slots 1, 2 and 5 are there because project_snr / project_tv use whole-GLOBAL-bat
 the SNR target norm the global ``clean.numel()``: ``paa_batch_stats`` writes this rank's sums and clip count, the all-reduce adds
 them (the count is a small integer, exact in f32) and ``paa_project_ext`` reads the sums on the device, so ranks may hold different
 numbers of clips, in any step.  Slots 3 and 4 carry the word errors / reference words: of the PREVIOUS step, counted on the host
-(train.py:149-153 runs one step behind the GPU; ``set_wer_counts``), or of THIS step with ``device_wer``, counted on a
-fixed ``refs`` buffer that is handled like ``labels``; ``paa_stats_push`` then appends the global stats to a device log whose cursor
-advances on the device, so a captured graph appends a row per replay and an epoch needs ONE readback (``read_log``).  Slot 6 is
-sum_b l_b of the masking loss: the step optimises direction * CTC(x + delta) - alpha * sum_b l_b(delta), and
-``paa_masking_loss`` subtracts alpha * grad(sum_b l_b) from the gradient BEFORE the all-reduce (the term is additive over clips).
-
-Host -> device scalars of a step travel through a ring of pinned slots (``_HostRing``) by asynchronous copies, so captured graphs
-follow them on replay: the host's WER counters, Adam's (-lr / (1 - beta1^t), sqrt(1 - beta2^t)) — computed as torch does, with the
-moments and the step count kept in ``optimizer.state[p]`` (build.py:352-359, train.py:165-175), so ``optimizer.state_dict()`` and a
-later plain ``optimizer.step()`` see the steps taken here, and a StepLR lr is picked up — and alpha (``set_masking_alpha``).
-
-Placement (training_utils/place.py): the perturbation has ``Lp`` samples, the clips ``L``; clip b is composed with
-a_b * delta[(i + s_b) mod Lp] and ``paa_place_reduce`` is the adjoint gather-sum into the packed gradient; the update and the
-projections run on (1, Lp).  The draw's step counter lives on the device, so a captured graph draws anew on every replay.
-
-Room responses (training_utils/rir.py): the placed rows pass through a causal FIR h_{c_b} per clip before the model
-and the gradient rows through its adjoint before ``paa_place_reduce``; the room draw has a device counter of its own.  With
-placement off the rows are placed at Lp = L with explicit zero shifts and unit gains, and ``place_on`` stays False.
+(``set_wer_counts``), or of THIS step with ``device_wer``, which also appends the global stats to a device log
+(``read_log``: ONE readback per epoch).  Slot 6 is sum_b l_b of the masking loss, whose gradient ``paa_masking_loss``
+subtracts BEFORE the all-reduce.  Host -> device scalars of a step (the host's WER counters, Adam's step scalars, alpha) travel
+through a ring of pinned slots (``_HostRing``) by asynchronous copies, so captured graphs follow them on replay.
 """
 from __future__ import annotations
 
@@ -71,7 +54,9 @@ import contextlib
 import torch
 
 from .. import _lib, runtime
-from . import place, rir
+from . import modes, place, rir
+from .build import batch_lengths, unpack_batch  # noqa: F401  (re-exported)
+from .modes import Ctx, Modes, replace
 
 FREQ_NORMS = ("fletcher_munson", "min_max_freqs", "max_phon")
 N_STATS = 8
@@ -101,54 +86,21 @@ def adam_unsupported(optimizer):
 
 
 def lengths_refusal(args):
-    """None, or why ``args`` cannot run with true clip lengths (``--clip_lengths true``): the masking norm and the masking loss
-    take a batch-minimum threshold over clips that have already ended, and placement / room responses move the perturbation
-    across the clip's end — each needs a design of its own."""
-    if "masking" in str(getattr(args, "norm_type", "")).split("+"):
-        return "--clip_lengths true does not support --norm_type masking"
-    if float(getattr(args, "masking_loss_alpha", 0.0) or 0.0) > 0:
-        return "--clip_lengths true does not support --masking_loss_alpha > 0"
-    if place.placement_on(args):
-        return "--clip_lengths true does not support placement (--perturbation_seconds, --place_shift, --place_gain_db)"
-    if rir.rir_on(args):
-        return "--clip_lengths true does not support --rir_bank"
-    return None
-
-
-def unpack_batch(batch):
-    """A loader item, (x, texts) or (x, texts, lengths) -> (x, texts, lengths | None): consumers accept both tuple forms."""
-    if len(batch) == 3:
-        return batch[0], batch[1], batch[2]
-    x, texts = batch
-    return x, texts, None
-
-
-def batch_lengths(batch, lengths_mode: bool):
-    """(x, texts, lengths) of a loader item in either tuple form; --clip_lengths true needs the lengths, padded ignores them."""
-    x, texts, lengths = unpack_batch(batch)
-    if lengths_mode and lengths is None:
-        raise ValueError("--clip_lengths true needs loaders that yield (x, texts, lengths)")
-    return x, texts, (lengths if lengths_mode else None)
+    """None, or why ``args`` cannot run with true clip lengths (``--clip_lengths true``), whether or not the flag is set."""
+    m = Modes.of(args, clip_lengths="true")
+    return next((modes.RULES[k].msg for k in modes.LENGTHS if modes.RULES[k].when(m, Ctx())), None)
 
 
 def check_clip_lengths(args):
     """Refusals of ``--clip_lengths true``, raised before any launch or collective; True when the mode is on."""
-    on = str(getattr(args, "clip_lengths", "padded")) == "true"
-    if on:
-        why = lengths_refusal(args)
-        if why is not None:
-            raise ValueError(why)
-    return on
+    return modes.check(Modes.of(args), modes.LENGTHS).lengths_on
 
 
 def masking_route(norm_type, world: int) -> None:
     """The masking norm bounds the universal perturbation by the minimum of every clip's bound: with several ranks that is a
     MIN over the ranks' shards, which the step's one SUM all-reduce does not carry.  Raises NotImplementedError (on every
     rank, before any collective) for a data-parallel masking run; one rank, force_collective included, is fine."""
-    if world > 1 and "masking" in str(norm_type).split("+"):
-        raise NotImplementedError("the masking norm is not implemented for data-parallel universal perturbations (world "
-                                  f"size {world}): the bound would need a MIN-reduction across ranks; use one rank, or "
-                                  "per-clip perturbations (paa_amd.attack_clips)")
+    modes.check(Modes.of(norm_type=norm_type), ("route",), Ctx(world))
 
 
 class StatsLog:
@@ -218,7 +170,8 @@ class _StepperCore:
     def __init__(self, model, args, length, interp, spl_thresh, optimizer, device_wer, canon, r_cap, log_cap, proj_rows, proj_len):
         self.model, self.args, self.L = model, args, int(length)
         self.dev = model.device
-        self.norms = str(args.norm_type).split("+")
+        self.modes = Modes.of(args)
+        self.norms = list(self.modes.norms)
         for n in self.norms:
             if n not in _lib.NORM_IDS:
                 raise ValueError(f"Unknown norm_type: {n!r}")                  # train.py:98
@@ -249,15 +202,12 @@ class _StepperCore:
 
     def set_lengths(self, lengths):
         """Per-clip sample counts from the next step on (host-validated, copied into the model's persistent buffer; a captured
-        graph follows it), or None to switch the mode off.  Refused for the modes ``lengths_refusal`` names, and — like the
-        masking loss — the mode cannot be switched on or off after ``capture()``."""
+        graph follows it), or None to switch the mode off.  Refused for the modes the table's "lengths" entry names, and — like
+        the masking loss — the mode cannot be switched on or off after ``capture()``."""
         on = lengths is not None
         if on:
-            why = lengths_refusal(self.args)
-            if why is None and self.mask_alpha > 0:
-                why = "--clip_lengths true does not support --masking_loss_alpha > 0"
-            if why is not None:
-                raise ValueError(why)
+            m = modes.check(replace(self.modes, lengths_on=True), modes.LENGTHS)
+            modes.check(replace(m, alpha=self.mask_alpha), modes.LENGTHS)          # an alpha set after construction
         if self._lengths_captured is not None and on != self._lengths_captured:
             raise ValueError("clip lengths cannot be switched on or off after capture(): the captured launch sequence "
                              f"{'runs' if self._lengths_captured else 'does not run'} in the length mode; capture the step again")
@@ -320,11 +270,8 @@ class _StepperCore:
         self.alpha_dev = None
         self._alpha_captured = None          # capture() records whether the captured launch sequence holds the term
         self._mask_prm = runtime.params_of(self.args, "masking")          # paa_masking_loss reads masking_margin_db only
-        alpha = float(getattr(self.args, "masking_loss_alpha", 0.0))
-        if alpha < 0:
-            raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
-        if alpha > 0:
-            self.set_masking_alpha(alpha)
+        if self.modes.alpha != 0:
+            self.set_masking_alpha(self.modes.alpha)
 
     def set_masking_alpha(self, alpha: float):
         """Weight of the masking-threshold loss term from the next step on.  The value goes to a one-float device tensor by a
@@ -332,10 +279,8 @@ class _StepperCore:
         the term is in the launch sequence at all (alpha > 0) is fixed by ``capture()``: switching it on or off afterwards
         raises."""
         alpha = float(alpha)
-        if alpha < 0:
-            raise ValueError(f"masking_loss_alpha must be >= 0, got {alpha}")
-        if alpha > 0 and getattr(getattr(self, "model", None), "lengths_on", False):
-            raise ValueError("--clip_lengths true does not support --masking_loss_alpha > 0")
+        lengths_on = bool(getattr(getattr(self, "model", None), "lengths_on", False))
+        modes.check(replace(getattr(self, "modes", None) or Modes.of(), alpha=alpha, lengths_on=lengths_on), ("alpha_range", "len_alpha"))
         if self._alpha_captured is not None and (alpha > 0) != self._alpha_captured:
             raise ValueError("masking_loss_alpha cannot switch between 0 and > 0 after capture(): the captured launch sequence "
                              f"{'holds' if self._alpha_captured else 'does not hold'} the loss term; capture the step again")
@@ -475,20 +420,19 @@ class PgdStepper(_StepperCore):
         ``length`` is the clip length L.  With placement on (module docstring) the perturbation has ``p_length`` samples (default:
         ``place.perturbation_length(args, L)``); with placement off it has L."""
         L = int(length)
-        self.place_on = place.placement_on(args)
-        self.rir_on = rir.rir_on(args)
-        rir.check(args)                                                          # refusals: before any launch or collective
-        self.Lp = L
-        if self.place_on:
-            self.Lp = int(p_length) if p_length is not None else place.perturbation_length(args, L)
-            place.check(args, L, self.Lp)                                        # refusals: before any launch or collective
-        elif p_length is not None and int(p_length) != L:
-            raise ValueError(f"p_length {p_length} != clip length {L} needs placement on (perturbation_seconds)")
         self.group, self.interp = group, interp
         self.world = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.world = torch.distributed.get_world_size(group)
-        masking_route(args.norm_type, self.world)
+        rir.check(args)                                                          # refusals: before any launch or collective
+        m = Modes.of(args)
+        self.place_on, self.rir_on, self.Lp = m.place_on, m.rir_on, L
+        if m.place_on:
+            self.Lp = int(p_length) if p_length is not None else place.perturbation_length(args, L)
+        elif p_length is not None and int(p_length) != L:
+            raise ValueError(f"p_length {p_length} != clip length {L} needs placement on (perturbation_seconds)")
+        place.check(args, L, self.Lp)
+        modes.check(m, ("route",), Ctx(self.world))
         self.collective = self.world > 1 or bool(force_collective)
         if self.collective and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
             raise RuntimeError("force_collective needs an initialised torch.distributed process group")
@@ -498,35 +442,19 @@ class PgdStepper(_StepperCore):
         self.grad = self.packed[: self.Lp].view(1, self.Lp)
         self.stats = self.packed[self.Lp:]
         if self.place_on or self.rir_on:
-            self._init_placement()
+            rank = torch.distributed.get_rank(self.group) if self.world > 1 else 0
+            self.placed = rir.PlacedRows(args, model, self.Lp, place.STREAM_TRAIN, True, rank, L)
+            pl = self.placer = self.placed.placer
+            self.shift, self.gain, self.counter, self.rows, self.grad_rows = pl.shift, pl.gain, pl.counter, pl.rows, pl.grad_rows
         if self.rir_on:
-            self._init_rir()
+            rv = self.reverb = self.placed.reverb
+            self.room, self.rir_counter, self.wet_rows = rv.index, rv.counter, rv.rows
 
     def _check_adam_shape(self):
         if self.adam_p.numel() != self.Lp:
             raise ValueError(f"optimizer parameter has {self.adam_p.numel()} elements, expected {self.Lp}")
 
     # ---- random placement of the perturbation ----------------------------------------------------------------------
-    def _init_placement(self):
-        rank = 0
-        if self.world > 1:
-            rank = torch.distributed.get_rank(self.group)
-        nb = int(self.model.max_batch)
-        seed = getattr(self.args, "place_seed", None)
-        seed = int(getattr(self.args, "seed", 5) if seed is None else seed)
-        self.placer = place.Placer(self.dev, nb, self.L, self.Lp, seed, place.STREAM_TRAIN, place.shift_on(self.args),
-                                   place.gain_db(self.args), clip_base=rank * nb)
-        if not self.place_on:               # room responses alone: the rows are delta itself, and nothing is drawn
-            self.placer.set_placement([0] * nb)
-        self.shift, self.gain, self.counter = self.placer.shift, self.placer.gain, self.placer.counter
-        self.rows, self.grad_rows = self.placer.rows, self.placer.grad_rows
-
-    def _init_rir(self):
-        pl = self.placer
-        self.reverb = rir.Reverb(self.dev, rir.bank_of(self.args), pl.max_batch, self.L, rir.draw_seed(self.args), place.STREAM_TRAIN,
-                                 clip_base=pl.clip_base)
-        self.room, self.rir_counter, self.wet_rows = self.reverb.index, self.reverb.counter, self.reverb.rows
-
     def _reverb(self):
         if not self.rir_on:
             raise RuntimeError("the stepper was built with room responses off (rir_bank)")
@@ -567,23 +495,6 @@ class PgdStepper(_StepperCore):
         if self.rir_on:
             self.reverb.clip_base = int(v)
 
-    def _placed_fwd_bwd(self, p, clean, labels, want_logits, out):
-        """draw -> rows [-> room draw -> rows through the rooms] -> forward / backward with one gradient row per clip [-> the
-        rooms' adjoint] -> adjoint gather-sum into self.grad."""
-        B, pl = clean.shape[0], self.placer
-        if not pl.explicit:
-            pl.draw(B)
-        rows = pl.place(p, B)
-        if self.rir_on:
-            if not self.reverb.explicit:
-                self.reverb.draw(B)
-            rows = self.reverb.apply(pl.rows, B)
-        out["grad"] = pl.grad_rows[:B]
-        r = self.model.fwd_bwd(clean, rows, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
-        pl.reduce(B, self.grad, self.reverb.adjoint(pl.grad_rows, B) if self.rir_on else None)
-        r["grad_rows"], r["grad"] = r["grad"], self.grad
-        return r
-
     def _replay_state(self):
         return super()._replay_state() + ([self.counter] if self.place_on else []) + ([self.rir_counter] if self.rir_on else [])
 
@@ -599,10 +510,14 @@ class PgdStepper(_StepperCore):
         out = {"grad": self.grad, "stats": self.stats}
         if logits_out is not None:
             out["logits"] = logits_out
-        if self.place_on or self.rir_on:
-            r = self._placed_fwd_bwd(p, clean, labels, want_logits, out)
-        else:
-            r = self.model.fwd_bwd(clean, p, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
+        placed = self.place_on or self.rir_on          # rir.PlacedRows: one gradient row per clip, then their adjoint into self.grad
+        if placed:
+            out["grad"] = self.grad_rows[:B]
+        r = self.model.fwd_bwd(clean, self.placed.rows(p, B) if placed else p, labels, self.direction, want_grad=True,
+                               want_logits=want_logits, out=out)
+        if placed:
+            self.placed.reduce(B, self.grad)
+            r["grad_rows"], r["grad"] = r["grad"], self.grad
         if self.mask_alpha > 0:
             self._masking_loss(p, clean, self.grad)
             r["masking_loss"] = self.stats[ST_MASK_LOSS]
@@ -652,7 +567,7 @@ class PgdStepper(_StepperCore):
     def _fit_proj(self, B):
         """The masking norm and the masking loss keep one bound per clip of the batch: grow the projection workspace to the
         batch (allocates, so it happens in an eager step; capture() runs one first)."""
-        if ("masking" in self.norms or self.mask_alpha > 0) and self.proj.max_batch < B:
+        if (self.modes.masking_norm or self.mask_alpha > 0) and self.proj.max_batch < B:
             self.proj = runtime.get_proj(self.args, self.dev, B, self.L, self.interp)
 
     def _body(self, p, clean, labels, want_logits=True, logits_out=None):

@@ -14,36 +14,31 @@ place_gain_db > 0; OFF leaves every caller exactly as it was.
 from __future__ import annotations
 
 import logging
+from dataclasses import replace
 
 import torch
 
 from .. import _lib
+from . import modes
+from .modes import Ctx, Modes
 
 logger = logging.getLogger(__name__)
 
 STREAM_TRAIN, STREAM_EVAL = 0, 1
-GAIN_DB_MAX = 20.0
 _FREQ_NORMS = ("fletcher_munson", "min_max_freqs", "max_phon")
 _hop_warned = set()
 
 
 def placement_on(args) -> bool:
-    return (getattr(args, "perturbation_seconds", None) is not None or getattr(args, "place_shift", "none") == "random"
-            or float(getattr(args, "place_gain_db", 0.0)) > 0)
+    return Modes.of(args).place_on
 
 
 def shift_on(args) -> bool:
-    mode = getattr(args, "place_shift", "none")
-    if mode not in ("none", "random"):
-        raise ValueError(f"place_shift must be 'none' or 'random', got {mode!r}")
-    return mode == "random"
+    return modes.check(replace(Modes.of(args), place_on=True), ("shift_range",)).shift_on
 
 
 def gain_db(args) -> float:
-    g = float(getattr(args, "place_gain_db", 0.0))
-    if not 0.0 <= g <= GAIN_DB_MAX:
-        raise ValueError(f"place_gain_db must be in [0, {GAIN_DB_MAX:g}], got {g}")
-    return g
+    return modes.check(replace(Modes.of(args), place_on=True), ("gain_range",)).gain_db
 
 
 def perturbation_length(args, clip_length: int) -> int:
@@ -60,30 +55,15 @@ def perturbation_length(args, clip_length: int) -> int:
 def check_flags(args) -> None:
     """The refusals that need no length: flag values outside their ranges, and the masking norm / masking loss.  A no-op with
     placement off."""
-    if not placement_on(args):
-        return
-    shift_on(args), gain_db(args)
-    norms = str(args.norm_type).split("+")
-    if "masking" in norms or float(getattr(args, "masking_loss_alpha", 0.0)) > 0:
-        raise NotImplementedError("placement (perturbation_seconds / place_shift / place_gain_db) is not implemented with the masking "
-                                  "norm or masking_loss_alpha > 0: both pair the perturbation's frames with the clean clip's frames")
+    modes.check(Modes.of(args), modes.PLACE_FLAGS)
 
 
 def check(args, L: int, Lp: int, eager_adam: bool = False) -> None:
     """What placement does not combine with, for clips of L and a perturbation of Lp samples; raises before any launch or
     collective.  A no-op with placement off."""
-    if not placement_on(args):
-        return
-    check_flags(args)
-    norms = str(args.norm_type).split("+")
-    if Lp != L and any(n in ("snr", "tv") for n in norms):
-        raise NotImplementedError(f"the snr / tv norms need a perturbation as long as the clips (Lp = {Lp}, L = {L}): their bound "
-                                  "compares the two sample for sample")
-    if eager_adam:
-        raise NotImplementedError("placement needs the device step: use the defaults of torch.optim.Adam(lr=...) or "
-                                  "--optimizer_type pgd")
+    m = modes.check(Modes.of(args), modes.PLACE, Ctx(1, eager_adam, L, Lp))
     hop = int(getattr(args, "hop_length", 256))
-    if Lp % hop and any(n in _FREQ_NORMS for n in norms) and (Lp, hop) not in _hop_warned:
+    if m.place_on and Lp % hop and any(n in _FREQ_NORMS for n in m.norms) and (Lp, hop) not in _hop_warned:
         _hop_warned.add((Lp, hop))
         logger.warning("perturbation length %d is no multiple of hop_length %d: the frequency-domain projection zeroes its last %d "
                        "samples every step", Lp, hop, Lp % hop)
@@ -91,9 +71,7 @@ def check(args, L: int, Lp: int, eager_adam: bool = False) -> None:
 
 def refuse_for_clips(args) -> None:
     """paa_amd.attack_clips: one perturbation row per clip has no placement."""
-    if placement_on(args):
-        raise NotImplementedError("--perturbation_seconds / --place_shift / --place_gain_db apply to the universal perturbation "
-                                  "(paa_amd.run_attack); per-clip perturbations have no placement")
+    modes.check(Modes.of(args), ("place_clips",))
 
 
 def suffix(args) -> str:
@@ -114,7 +92,7 @@ def results_extra(args, Lp: int) -> dict:
     """results.json keys of a run with placement (none otherwise)."""
     if not placement_on(args):
         return {}
-    return {"perturbation_length": int(Lp), "place_shift": str(getattr(args, "place_shift", "none")), "place_gain_db": gain_db(args)}
+    return {"perturbation_length": int(Lp), "place_shift": str(Modes.of(args).place_shift), "place_gain_db": gain_db(args)}
 
 
 class Placer:

@@ -21,6 +21,8 @@ import numpy as np
 import torch
 
 from .. import _lib, synth
+from . import modes, place
+from .modes import Ctx, Modes
 
 MAX_TAPS = 16384                      # PAA_RIR_MAX_TAPS of include/paa_hip.h
 MAX_COUNT = 65536
@@ -28,7 +30,7 @@ _BANKS = {}
 
 
 def rir_on(args) -> bool:
-    return str(getattr(args, "rir_bank", "none")) != "none"
+    return Modes.of(args).rir_on
 
 
 def _synthetic_flags(args):
@@ -50,35 +52,21 @@ def _synthetic_flags(args):
 
 
 def check_flags(args) -> None:
-    """The refusals that need no stepper: flag values outside their ranges, and the masking norm / masking loss.  A no-op with the
-    mode off."""
-    if not rir_on(args):
-        return
-    if str(args.rir_bank) == "synthetic":
-        _synthetic_flags(args)
-    else:
-        bank_of(args)                       # a file: read and checked here, on the host
-    norms = str(args.norm_type).split("+")
-    if "masking" in norms or float(getattr(args, "masking_loss_alpha", 0.0)) > 0:
-        raise NotImplementedError("room responses (rir_bank) are not implemented with the masking norm or masking_loss_alpha > 0: "
-                                  "both pair the perturbation's frames with the clean clip's frames")
+    """The refusals that need no stepper: flag values outside their ranges, the masking norm / loss.  A no-op with the mode off."""
+    check(args)
 
 
 def check(args, eager_adam: bool = False) -> None:
     """What the mode does not combine with; raises before any launch or collective.  A no-op with the mode off."""
-    if not rir_on(args):
-        return
-    check_flags(args)
-    if eager_adam:
-        raise NotImplementedError("room responses (rir_bank) need the device step: use the defaults of torch.optim.Adam(lr=...) or "
-                                  "--optimizer_type pgd")
+    m = Modes.of(args)
+    if m.rir_on:          # the synthetic bank's flags range-checked, or a bank file read and checked, here on the host
+        _synthetic_flags(args) if str(args.rir_bank) == "synthetic" else bank_of(args)
+    modes.check(m, modes.ROOMS, Ctx(1, eager_adam))
 
 
 def refuse_for_clips(args) -> None:
     """paa_amd.attack_clips: reverberation of per-clip perturbations is not part of this."""
-    if rir_on(args):
-        raise NotImplementedError("--rir_bank applies to the universal perturbation (paa_amd.run_attack); per-clip perturbations "
-                                  "have no room responses yet")
+    modes.check(Modes.of(args), ("rir_clips",))
 
 
 def synthetic_rt60(N: int, rt60_lo: float, rt60_hi: float, seed: int) -> np.ndarray:
@@ -230,6 +218,38 @@ class Reverb:
     def adjoint(self, grad_rows, B: int):
         """The model's gradient rows (B, L) -> self.grad_rows[:B], the gradient with respect to the rows ``apply`` read."""
         return self._launch(grad_rows, self.grad_rows, B, 1)
+
+
+class PlacedRows:
+    """The rows the model sees at one site (the training step, or one evaluation) with placement and / or room responses on: a
+    ``place.Placer`` and, with room responses on, a ``Reverb``, both keyed by ``draw_seed`` and the global clip id ``rank *
+    max_batch + b``.  With placement off the rows are placed at explicit zero shifts and unit gains, and nothing is drawn."""
+
+    def __init__(self, args, model, Lp: int, stream_id: int, with_grad: bool = True, rank: int = 0, L=None):
+        m, nb, L, seed = Modes.of(args), int(model.max_batch), int(model.length if L is None else L), draw_seed(args)
+        self.placer = place.Placer(model.device, nb, L, Lp, seed, stream_id, place.shift_on(args), place.gain_db(args),
+                                   clip_base=rank * nb, with_grad=with_grad)
+        if not m.place_on:
+            self.placer.set_placement([0] * nb)
+        self.reverb = Reverb(model.device, bank_of(args), nb, L, seed, stream_id, clip_base=rank * nb,
+                             with_grad=with_grad) if m.rir_on else None
+
+    def rows(self, p, B: int):
+        """draw -> rows [-> room draw -> rows through the rooms]; an explicit placement / explicit rooms skip their draw."""
+        pl, rv = self.placer, self.reverb
+        if not pl.explicit:
+            pl.draw(B)
+        rows = pl.place(p, B)
+        if rv is not None:
+            if not rv.explicit:
+                rv.draw(B)
+            rows = rv.apply(pl.rows, B)
+        return rows
+
+    def reduce(self, B: int, grad):
+        """The model's gradient rows (``placer.grad_rows``) [-> the rooms' adjoint] -> adjoint gather-sum into ``grad``."""
+        pl, rv = self.placer, self.reverb
+        pl.reduce(B, grad, rv.adjoint(pl.grad_rows, B) if rv is not None else None)
 
 
 def reverberate(rows, bank, index):

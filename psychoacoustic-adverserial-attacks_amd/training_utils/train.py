@@ -13,8 +13,9 @@ import torch
 
 from .. import _lib, runtime
 from ..core import loss_helpers
-from . import place, rir
-from .pgd import FREQ_NORMS, PgdStepper, adam_unsupported, batch_lengths, check_clip_lengths
+from . import modes, place, rir
+from .modes import Ctx, Modes
+from .pgd import FREQ_NORMS, PgdStepper, adam_unsupported, batch_lengths
 
 logger = logging.getLogger(__name__)
 
@@ -80,7 +81,8 @@ def wer_of_rows(rows):
 def perturbation_constraint(p: torch.Tensor, clean_audio, args, interp, spl_thresh) -> torch.Tensor:
     """train.py:69-99.  Returns a new tensor; ``p`` is left untouched.  ``args.norm_type`` may be a
     '+'-joined list (extension, applied in the written order)."""
-    norms = str(args.norm_type).split("+")
+    m = Modes.of(args)
+    norms = m.norms
     for n in norms:
         if n not in _lib.NORM_IDS:
             raise ValueError(f"Unknown norm_type: {n!r}")                                   # train.py:98
@@ -97,7 +99,7 @@ def perturbation_constraint(p: torch.Tensor, clean_audio, args, interp, spl_thre
     if clean is not None and clean.shape[-1] != L:
         raise ValueError(f"clean_audio length {clean.shape[-1]} != perturbation length {L}")
     # the masking norm keeps one bound per clean clip before their minimum: the workspace holds the whole batch
-    nb_ws = clean.shape[0] if clean is not None and clean.dim() == 2 and "masking" in norms else 0
+    nb_ws = clean.shape[0] if clean is not None and clean.dim() == 2 and m.masking_norm else 0
     pr = runtime.get_proj(args, q.device, max(rows, nb_ws), L, interp)
     out_len = L
     with torch.cuda.device(q.device):
@@ -121,12 +123,10 @@ def adam_route(optimizer, world: int) -> str:
     torch.optim.Adam build.py:352-359 creates, "eager" (torch's own optimizer.step) for any other optimizer on one rank.
     With several ranks only the device step exists: NotImplementedError names the option it does not cover."""
     why = adam_unsupported(optimizer)
-    if why is None:
-        return "device"
-    if world > 1:
+    if why is not None and world > 1:          # about the optimizer object, not the mode flags: not in modes.RULES
         raise NotImplementedError(f"the data-parallel Adam step does not implement {why}; use the defaults of "
                                   "torch.optim.Adam(lr=...) or a single rank")
-    return "eager"
+    return "device" if why is None else "eager"
 
 
 def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, processor, interp, wer_metric,
@@ -139,27 +139,23 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
     if args.optimizer_type == "adam" and optimizer is None:
         raise ValueError("Adam optimizer selected but optimizer is None")                          # train.py:167
     Lp = p.shape[-1]
-    L = int(model.length) if place.placement_on(args) else Lp          # placement: p has a length of its own (place.py)
+    m = Modes.of(args)
+    L = int(model.length) if m.place_on else Lp          # placement: p has a length of its own (place.py)
     world = 1
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         world = torch.distributed.get_world_size()
     # The eager torch chain stays only for a one-rank run whose optimizer the device step does not implement (weight decay,
     # AMSGrad, ...): there it is what the reference runs, and the data-parallel machinery has nothing to add.
     eager_adam = args.optimizer_type == "adam" and adam_route(optimizer, world) == "eager"
-    step_opt = optimizer if args.optimizer_type == "adam" and not eager_adam else None
-    mask_alpha = float(getattr(args, "masking_loss_alpha", 0.0))
-    if eager_adam and mask_alpha > 0:
-        raise NotImplementedError("masking_loss_alpha > 0 needs the device step: use the defaults of torch.optim.Adam(lr=...) "
-                                  "or --optimizer_type pgd")
+    modes.check(m, ("alpha_eager",), Ctx(world, eager_adam))          # refusals: before any launch or collective
     place.check(args, L, Lp, eager_adam)
     rir.check(args, eager_adam)
-    lengths_mode = check_clip_lengths(args)          # refusals of --clip_lengths true: before any launch or collective
-    if lengths_mode and eager_adam:
-        raise NotImplementedError("--clip_lengths true needs the device step: use the defaults of torch.optim.Adam(lr=...) or "
-                                  "--optimizer_type pgd")
+    modes.check(m, modes.LENGTHS + ("len_eager",), Ctx(world, eager_adam))
+    step_opt = optimizer if args.optimizer_type == "adam" and not eager_adam else None
+    mask_alpha, lengths_mode = m.alpha, m.lengths_on
     mask_scores = []
     canon = None if eager_adam else device_wer_canon(args, processor, wer_metric, "train_epoch")
-    if eager_adam and getattr(args, "device_wer", False):
+    if eager_adam and m.device_wer:
         log_host_route("train_epoch", "the optimizer runs torch's own step")
     stepper = getattr(model, "_stepper", None)
     if stepper is None or stepper.args is not args or stepper.L != L or stepper.Lp != Lp or stepper.optimizer is not step_opt \
