@@ -181,6 +181,41 @@ paa_status paa_compose_clamp(const float* d_clean, const float* d_p, float* d_ou
  * row.  One launch sequence for all rows; the workspace is the one paa_proj_create sized (rows <= max_batch, L <= max_len). */
 paa_status paa_project_rows(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
                             const float* d_clean, int L, void* stream);
+/* ---- per-clip bound search (extension; additions to ABI 350) ------------------------------------------------
+ * paa_project_rows_scaled: paa_project_rows with row r's bound tightened by s = d_scale[r], a device (rows) f32 array read on the
+ * stream (a captured graph follows the buffer).  f32 arithmetic, part of the contract:
+ *   linf             clamp to +-(linf_size * s)
+ *   l2               eps = l2_size * s
+ *   tv               eps = (tv_epsilon * s) * TV(clean_r)
+ *   fletcher_munson  eps = fm_epsilon * s (fused and generic frame geometry alike)
+ *   snr              the row is left alone iff cur >= snr_db - 20 log10f(s); else its target norm is sqrtf(sp / snr_linear * numel) * s
+ *   max_phon         the per-bin threshold is thr + 20 log10f(s) dB
+ *   min_max_freqs    has no size: s is ignored
+ *   masking          PAA_ERR_BAD_NORM (a per-clip threshold with a moving margin is a change of its own)
+ * d_scale == NULL is paa_project_rows: the same launches, the same bits.  s = 1.0f gives the bits of the unscaled call for every
+ * norm (x * 1.0f, log10f(1.0f) = 0 and thr + 0.0f are exact).  A value that is not a finite positive number is treated as 1.0f on
+ * the device, so it cannot produce NaN rows.  In place and out of place, workspace, PAA_ERR_SIZE / PAA_ERR_NEED_CLEAN /
+ * PAA_ERR_ARG as paa_project_rows; with a scale, rows = 1 runs the row launches (the same bits as the one-row call at s = 1).
+ * No atomics. */
+paa_status paa_project_rows_scaled(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
+                                   const float* d_clean, int L, const float* d_scale /* device (rows) */, void* stream);
+/* Decide / keep / shrink, per clip b, with step = *d_step and (e, w, _) = d_counts[b] (what paa_wer_counts wrote for the step):
+ *   success   targeted: e == 0 && w > 0;  untargeted: w > 0 && e * 1000 >= wer_milli * w   (exact integer compares)
+ *   on success  d_best[b] <- d_delta[b] (the whole row: 16-byte accesses where both row bases are 16-byte aligned, element by
+ *               element otherwise), d_best_scale[b] <- d_scale[b], d_best_step[b] <- step,
+ *               d_scale[b] <- fmaxf(d_scale[b] * shrink, floor_scale)
+ *   on failure  nothing of clip b is written: not its d_best row, not its scalars
+ *   afterwards  *d_step = step + 1 ON THE DEVICE, so a captured graph counts on.
+ * The step's counters belong to the delta that ENTERED the step, so the call sits after paa_wer_counts and BEFORE the update: it
+ * records the delta that produced the success with the scale that delta was projected under (d_best[b] satisfies the bound at
+ * d_best_scale[b]).  Two launches (a one-workgroup decide kernel writing per-row flags, then a (chunks, B) copy grid): no block
+ * reads what another block of its launch writes.  Capturable, allocates nothing, no atomics; the flags are a fixed per-device
+ * array, so calls on different streams of one device must not overlap.  PAA_ERR_ARG before any launch: a null pointer, B < 1
+ * (or B > 65535), L < 1, shrink outside (0, 1), floor_scale outside (0, 1], wer_milli < 1. */
+paa_status paa_clip_search(const float* d_delta /* (B, L) */, int B, int L, const int32_t* d_counts /* (B, 3) paa_wer_counts */,
+                           int targeted, int wer_milli, float shrink, float floor_scale,
+                           float* d_scale /* (B) in/out */, float* d_best /* (B, L) */, float* d_best_scale /* (B) */,
+                           int32_t* d_best_step /* (B) */, int32_t* d_step /* [1] */, void* stream);
 /* train.py:136 with one perturbation row per clip: out[b] = clamp(clean[b] + p[b], -1, 1); d_p (p_rows, L), p_rows in
  * {1, B}; p_rows = 1 is paa_compose_clamp. */
 paa_status paa_compose_clamp_rows(const float* d_clean, const float* d_p, int p_rows, float* d_out, int B, int L,

@@ -85,6 +85,10 @@ _SIGS = {
     "paa_compose_clamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "paa_project_rows": (C.c_int, [C.c_void_p, C.POINTER(PaaParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                    C.c_void_p]),
+    "paa_project_rows_scaled": (C.c_int, [C.c_void_p, C.POINTER(PaaParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p]),
+    "paa_clip_search": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float] +
+                        [C.c_void_p] * 6),
     "paa_compose_clamp_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "paa_model_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(PaaArch), C.POINTER(PaaTensor), C.c_int, C.c_int,
                                    C.c_int, C.c_int]),

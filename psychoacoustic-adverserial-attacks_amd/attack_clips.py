@@ -8,6 +8,10 @@ Writes ``clip_results.json`` (one record per clip, then the summary means) and i
 ``--num_items_to_inspect`` adversarial clips into the run directory.  Launched with several ranks (WORLD_SIZE / RANK), the
 clips of every global batch are sharded over the ranks (build.shard_batches), each rank attacks its shard without any
 collective, and one gather after the last batch brings the records to rank 0, which writes the file.
+
+``--bound_search shrink`` answers "how small a perturbation makes this clip fall?": the moment a clip's attack
+succeeds its delta is remembered and its bound is multiplied by ``--search_shrink``; the record then describes the smallest
+successful delta (``found``, ``found_step``, ``bound_scale``, ``last_scale``), or the last iterate of a clip that never fell.
 """
 from __future__ import annotations
 
@@ -30,12 +34,23 @@ TARGET_FIELD = "target_wer"
 MASK_FIELD = "final_masking_loss"          # l_b(delta_b) of the finished perturbation (masking_loss_alpha > 0 only)
 LENGTH_FIELD = "length"                     # the clip's true sample count (--clip_lengths true only)
 SUMMARY_FIELDS = ("clean_wer", "adv_wer", "final_ctc", "l2", "linf", "snr_db")
+# --bound_search shrink only: found (the step's own counters said "success" at least once), the step of the reported delta (-1: not
+# found), the scale that delta satisfies (best_scale, or the last scale when not found) and the scale the search ended at
+SEARCH_FIELDS = ("found", "found_step", "bound_scale", "last_scale")
 
 
 def create_arg_parser():
     p = parser.create_arg_parser()
     p.add_argument("--pgd_steps", type=int, default=100, help="per-clip attack: device steps per batch")
     p.add_argument("--split", type=str, choices=list(SPLITS), default="test", help="per-clip attack: the split attacked")
+    p.add_argument("--bound_search", type=str, choices=["off", "shrink"], default="off",
+                   help="shrink: the moment a clip's attack succeeds, keep that perturbation and multiply the clip's bound by "
+                        "--search_shrink; the record reports the smallest successful perturbation")
+    p.add_argument("--search_shrink", type=float, default=0.8, help="bound search: factor applied to a clip's bound on success, in (0, 1)")
+    p.add_argument("--search_floor", type=float, default=0.01, help="bound search: smallest bound scale, in (0, 1]")
+    p.add_argument("--search_success_wer", type=float, default=0.5,
+                   help="bound search, untargeted: success is per-clip WER >= this (rounded to thousandths); targeted success is "
+                        "always the target transcript exactly")
     return p
 
 
@@ -78,7 +93,12 @@ def gather_records(records, world: int = 1, group=None):
 def summarize(records, targeted: bool = False):
     keys = SUMMARY_FIELDS + ((TARGET_FIELD,) if targeted else ())
     n = len(records)
-    return {k: (sum(float(r[k]) for r in records) / n if n else float("nan")) for k in keys} | {"clips": n}
+    out = {k: (sum(float(r[k]) for r in records) / n if n else float("nan")) for k in keys} | {"clips": n}
+    if records and "found" in records[0]:          # --bound_search shrink: the share of clips that fell, the mean scale they fell at
+        hit = [r for r in records if r["found"]]
+        out["success_rate"] = len(hit) / n
+        out["mean_bound_scale"] = sum(float(r["bound_scale"]) for r in hit) / len(hit) if hit else float("nan")
+    return out
 
 
 def results_dict(records, args):
@@ -112,11 +132,29 @@ def _device_wers(args, processor, logits, texts, frames=None, blank=0):
     return [e / max(w, 1) for e, w, _ in loss_helpers.wer_counts_device(logits, refs, canon, frames=frames, blank=blank).cpu().tolist()]
 
 
+def search_route(args, processor, texts):
+    """(SearchConfig, canon table, the step's reference rows) of a batch under --bound_search shrink; the references are the target
+    transcript in targeted mode.  Raises the table's refusal when the device WER route is not available."""
+    cfg = modes.SearchConfig.of(args)
+    m = modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS, modes.Ctx(search=cfg))
+    judged = [" ".join([args.target] * args.target_reps)] * len(texts) if cfg.targeted else texts
+    canon = loss_helpers.canon_table(processor)
+    refs = loss_helpers.encode_refs(judged) if canon is not None else None
+    why = ("the vocabulary is not one character per token" if canon is None else
+           f"a reference needs more than {loss_helpers.R_CAP} entries" if refs is None else None)
+    modes.check(m, ("search_route",), modes.Ctx(search=cfg, wer_why=why))
+    return cfg, canon, refs
+
+
 def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper=None, lengths=None):
     """Attack one batch of clips (x (B, L) on the device) and return (records, delta, adversarial waveforms).  ``lengths``
     (--clip_lengths true): the clips' true sample counts — the model masks the padding, delta_b[len_b:] stays zero, and the
-    record's norms and SNR are those of delta_b[:len_b] against x_b[:len_b]."""
+    record's norms and SNR are those of delta_b[:len_b] against x_b[:len_b].  With --bound_search shrink the delta returned,
+    scored and composed is the REPORTED one: ``best_b`` of a clip that fell, the last iterate of the others."""
     B, L = x.shape
+    search = None
+    if modes.Modes.of(args).search_on:       # refusals first: before any launch of the batch
+        search, canon, search_refs = search_route(args, processor, texts)
     labels = loss_helpers.make_labels(texts, processor, args, B)
     delta = torch.from_numpy(init_rows(L, idx, int(args.seed))).to(x.device)
     frames, blank = None, int(model.arch.pad_token_id)
@@ -127,16 +165,33 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
     elif model.lengths_on:
         model.set_lengths(None)
     project_rows(delta, x, args, interp, spl_thresh, lengths)             # build.py:301-304, per clip
+    skw = {} if search is None else dict(device_wer=True, canon=canon, search=search)      # the search runs on the device WER route
     if args.optimizer_type == "adam":
         optimizer = torch.optim.Adam([delta], lr=args.lr)
-        stepper = ClipStepper(model, args, L, interp, spl_thresh, optimizer=optimizer)
+        stepper = ClipStepper(model, args, L, interp, spl_thresh, optimizer=optimizer, **skw)
     elif stepper is None:
-        stepper = ClipStepper(model, args, L, interp, spl_thresh)
-    for _ in range(int(args.pgd_steps)):
-        stepper.step(delta.data, x, labels, want_logits=False)          # reads the model's length buffer, set above
-    delta = delta.detach()
+        stepper = ClipStepper(model, args, L, interp, spl_thresh, **skw)
+    if search is None:
+        for _ in range(int(args.pgd_steps)):
+            stepper.step(delta.data, x, labels, want_logits=False)          # reads the model's length buffer, set above
+        delta = delta.detach()
+    else:
+        stepper.set_refs(search_refs)
+        stepper.search_reset(B)
+        stepper.stats_log.cursor.zero_()                                    # nobody reads the per-step log here: keep it from filling
+        step_logits = torch.empty(B, model.frames, model.arch.vocab_size, dtype=torch.float32, device=x.device)
+        for _ in range(int(args.pgd_steps)):
+            stepper.step(delta.data, x, labels, logits_out=step_logits)
+        found_step = stepper.best_step[:B].clone()
+        hit = found_step >= 0
+        delta = torch.where(hit[:, None], stepper.best[:B], delta.detach())
+        bound_scale = torch.where(hit, stepper.best_scale[:B], stepper.scale[:B]).cpu()
+        last_scale, found_step = stepper.scale[:B].cpu(), found_step.cpu()
     clean_out = model.forward(x, None, labels)
-    adv_out = model.forward(x, delta, labels, clamp=True)
+    if search is None:
+        adv_out = model.forward(x, delta, labels, clamp=True)
+    else:       # ``found`` came from the step's own forward pass: score the reported delta through the very call the step makes
+        adv_out = model.fwd_bwd(x, delta, labels, stepper.direction, want_grad=False, want_logits=True)
     clean_nll = clip_nll(model, clean_out["logits"], labels, frames).cpu()
     adv_nll = clip_nll(model, adv_out["logits"], labels, frames).cpu()
     refs = loss_helpers.clean_transcripts(texts)
@@ -171,6 +226,9 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
             rec[MASK_FIELD] = float(mloss[b])
         if lengths is not None:
             rec[LENGTH_FIELD] = int(lengths[b])
+        if search is not None:
+            rec |= {"found": bool(found_step[b] >= 0), "found_step": int(found_step[b]), "bound_scale": float(bound_scale[b]),
+                    "last_scale": float(last_scale[b])}
         records.append(rec)
     return records, delta, compose_rows(x, delta, lengths), stepper
 
@@ -178,6 +236,7 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
 def main(args) -> int:
     # what per-clip perturbations do not run with, and the refusals of --clip_lengths true: before any launch or collective
     lengths_mode = modes.check(modes.Modes.of(args), ("place_clips", "rir_clips") + modes.LENGTHS).lengths_on
+    modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS, modes.Ctx(search=modes.SearchConfig.of(args)))
     if not torch.cuda.is_available():
         raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")
     if not str(args.device).startswith("cuda"):

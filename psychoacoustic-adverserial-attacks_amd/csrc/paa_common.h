@@ -54,6 +54,14 @@ inline int device_cus() {
     return cache[dev];
 }
 
+// Per-row bound scale (paa_project_rows_scaled): sc == nullptr is the unscaled projection; a value that is not a finite positive
+// number acts as 1.0f, so a stray scale cannot turn a row into NaN.  Uniform over a workgroup (row = blockIdx.y).
+__device__ __forceinline__ float row_scale(const float* __restrict__ sc, int row) {
+    if (!sc) return 1.f;
+    const float s = sc[row];
+    return (s > 0.f && s < INFINITY) ? s : 1.f;
+}
+
 // ---- wave (64 lanes) / block reductions --------------------------------------------------------
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {

@@ -107,6 +107,7 @@ struct FrameArgs {
     const float* thr_max;  // [1]
     int L, T, N, log2n, hop, F;
     float bin_hz, min_f, max_f, phon_ref;
+    const float* rscale; // (rows) per-row bound scale, nullable [PHON: the threshold moves by 20 log10(s) dB]
 };
 
 // One workgroup = one STFT frame: window -> FFT -> OP on the F one-sided bins -> inverse FFT -> window.
@@ -143,6 +144,7 @@ __global__ __launch_bounds__(FFT_NT) void k_frame(FrameArgs a) {
         return;
     }
     double acc = 0.0;
+    const float thr_row = (OP == OP_PHON && a.rscale) ? 20.f * log10f(row_scale(a.rscale, row)) : 0.f;
     for (int k = tid; k < F; k += FFT_NT) {
         float2 v = X[k];
         if (OP == OP_MINMAX) {
@@ -154,7 +156,8 @@ __global__ __launch_bounds__(FFT_NT) void k_frame(FrameArgs a) {
             // projections.py:138-159
             const float mag = hypotf(v.x, v.y);
             const float mag_db = 20.f * log10f(mag + 1e-8f);
-            const float thr = (a.thr[k] - a.thr_max[0]) + a.phon_ref;
+            float thr = (a.thr[k] - a.thr_max[0]) + a.phon_ref;
+            if (a.rscale) thr += thr_row;
             const float db = (mag_db > thr) ? thr : mag_db;
             const float mc = exp10f(db / 20.f);
             const float ang = atan2f(v.y, v.x);
@@ -223,12 +226,16 @@ __global__ void k_ola(const float* __restrict__ frames, const float* __restrict_
 }
 
 // projections.py:116-133 project_fm_norm: scale = eps / max(norm, 1e-8) if norm > eps else 1
-// ROWS: one workgroup per row, row r sums part[r * n, (r + 1) * n) and writes its scale to scal[r] (no norm slot).
+// ROWS: one workgroup per row, row r sums part[r * n, (r + 1) * n) and writes its scale to scal[r] (no norm slot); rscale
+// (nullable): row r's eps is eps * rscale[r].
 template <bool ROWS>
 __global__ __launch_bounds__(RED_NT) void k_fm_finalize(const double* __restrict__ part, int n, float eps,
-                                                      float* __restrict__ scal) {
+                                                      float* __restrict__ scal, const float* __restrict__ rscale = nullptr) {
     __shared__ double red[RED_NT / 64];
-    if (ROWS) part += (size_t)blockIdx.x * n;
+    if (ROWS) {
+        part += (size_t)blockIdx.x * n;
+        eps = eps * row_scale(rscale, blockIdx.x);
+    }
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += RED_NT) s += part[i];
     s = block_sum<double, RED_NT>(s, red);
@@ -247,12 +254,15 @@ __global__ __launch_bounds__(RED_NT) void k_fm_finalize(const double* __restrict
 // Second launch of a fused spectral projection: dst = src * scale, the scale being the predicated FM factor computed from
 // the per-workgroup partial sums of the first launch (every block re-sums the few hundred partials: no third launch);
 // npart = 0: plain copy (min_max_freqs / max_phon, in-place form only).
-// ROWS: blockIdx.y is the row; n and npart are per row, and each row is scaled by the norm of its own partials.
+// ROWS: blockIdx.y is the row; n and npart are per row, and each row is scaled by the norm of its own partials; rscale
+// (nullable): row r's eps is eps * rscale[r].
 template <bool ROWS>
 __global__ __launch_bounds__(RED_NT) void k_spec_finish(const float* __restrict__ src, float* __restrict__ dst, int64_t n,
-                                                      const double* __restrict__ part, int npart, float eps, float* __restrict__ scal) {
+                                                      const double* __restrict__ part, int npart, float eps, float* __restrict__ scal,
+                                                      const float* __restrict__ rscale = nullptr) {
     __shared__ double red[RED_NT / 64];
     if (ROWS) {
+        eps = eps * row_scale(rscale, blockIdx.y);
         src += (size_t)blockIdx.y * n;
         dst += (size_t)blockIdx.y * n;
         part += (size_t)blockIdx.y * npart;
@@ -331,6 +341,7 @@ struct ApplyArgs {
     const float* ext;   // optional device [sum clean^2, TV(clean)] supplied by the caller (data-parallel runs)
     const float* ext_clips;   // optional device [1]: number of clean clips over ALL ranks (an exact small integer in f32);
     double clip_len;          //   numel_clean = ext_clips[0] * clip_len then replaces the host value above
+    const float* rscale;      // ROWS: optional device (rows) per-row bound scale s (paa_project_rows_scaled): l2 / tv eps * s, snr_db - 20 log10(s)
 };
 
 // p = src * scale (src == p: in place; otherwise the out-of-place form reads the caller's source directly — no copy in front)
@@ -352,20 +363,25 @@ __global__ __launch_bounds__(RED_NT) void k_apply_scale(const float* src, float*
     if (a.ext) s1 = (double)a.ext[NORM == PAA_NORM_TV ? 1 : 0];
     const double numel_clean = a.ext_clips ? (double)a.ext_clips[0] * a.clip_len : a.numel_clean;
     float scale = 1.f;
+    // the row's bound scale: x * 1.0f and x - 20 log10f(1.0f) are exact, so s = 1 gives the bits of the unscaled projection
+    const float rs = ROWS ? row_scale(a.rscale, blockIdx.y) : 1.f;
     if (NORM == PAA_NORM_L2) {                     // projections.py:41-46 (s2 = sum p^2)
         const float norm = sqrtf((float)s2);
-        if (norm > a.eps) scale = a.eps / norm;
+        const float eps = a.eps * rs;
+        if (norm > eps) scale = eps / norm;
     } else if (NORM == PAA_NORM_SNR) {             // projections.py:11-35 (s1 = sum clean^2, s2 = sum p^2)
         const float sp = (float)(s1 / numel_clean);
         const float np_ = (float)(s2 / a.numel_p);
         const float cur = 10.f * log10f(sp / (np_ + 1e-12f));
-        if (!(cur >= a.snr_db)) {
-            const float target = sqrtf(sp / a.snr_linear * (float)numel_clean);
+        float want = a.snr_db;
+        if (ROWS && a.rscale) want = a.snr_db - 20.f * log10f(rs);
+        if (!(cur >= want)) {
+            const float target = sqrtf(sp / a.snr_linear * (float)numel_clean) * rs;
             const float cn = sqrtf((float)s2);
             if (!(cn < 1e-8f)) scale = target / cn;
         }
     } else if (NORM == PAA_NORM_TV) {              // projections.py:56-66 (s1 = TV(clean), s2 = TV(p))
-        const float eps = a.eps * (float)s1;
+        const float eps = (a.eps * rs) * (float)s1;
         const float tv = (float)s2;
         if (tv > eps) scale = eps / tv;
     }
@@ -388,6 +404,15 @@ __global__ __launch_bounds__(RED_NT) void k_apply_scale(const float* src, float*
 __global__ void k_clamp(const float* src, float* p, int64_t n, float lo, float hi) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         p[i] = fminf(fmaxf(src[i], lo), hi);       // torch.clamp propagates NaN; fminf/fmaxf do not: see DESIGN.md
+}
+
+// linf with a per-row bound scale: row blockIdx.y is clamped to +-(lim * s_row)
+__global__ void k_clamp_rows(const float* src, float* p, int L, float lim, const float* __restrict__ rscale) {
+    const float hi = lim * row_scale(rscale, blockIdx.y);
+    src += (size_t)blockIdx.y * L;
+    p += (size_t)blockIdx.y * L;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < L; i += gridDim.x * blockDim.x)
+        p[i] = fminf(fmaxf(src[i], -hi), hi);
 }
 
 __global__ void k_sign_step(float* __restrict__ p, const float* __restrict__ g, float lr, int n) {
@@ -813,13 +838,21 @@ extern "C" paa_status paa_project_to(paa_proj* h, const paa_params* prm, const f
 // perturbation_constraint(src[r][None], clean[r][None], args) projects it (train.py:69-99) — l2 / fletcher_munson from the
 // row's own norm, snr from clean row r's own mean power (clean.numel() = L), tv from TV(clean[r]).  The launch sequence
 // is the one of a one-row projection with a row grid dimension; no launch per row.
+// d_scale (nullable, device (rows)): the per-row bound scale of paa_project_rows_scaled; null launches what it always launched.
 static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
-                                    const float* d_clean, int L, hipStream_t st) {
+                                    const float* d_clean, int L, hipStream_t st, const float* d_scale = nullptr) {
     const int nt = prm->norm_type;
     const int64_t n = (int64_t)rows * L;
     const bool in_place = d_src == d_dst;
+    const char* who = d_scale ? "paa_project_rows_scaled" : "paa_project_rows";
     switch (nt) {
         case PAA_NORM_LINF:
+            if (d_scale) {
+                hipLaunchKernelGGL(k_clamp_rows, dim3(std::min(cdiv((int64_t)L, 256), 256), rows), dim3(256), 0, st, d_src, d_dst, L,
+                                   prm->linf_size, d_scale);
+                PAA_LAUNCH_CHECK();
+                return PAA_OK;
+            }
             hipLaunchKernelGGL(k_clamp, dim3(std::min(cdiv(n, 256), 2048)), dim3(256), 0, st, d_src, d_dst, n, -prm->linf_size,
                                prm->linf_size);
             PAA_LAUNCH_CHECK();
@@ -836,7 +869,7 @@ static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const fl
             const int g1 = nc ? std::min(cdiv(nc, (int64_t)RED_NT * 16), 2048) : 0;
             const int g2 = std::min(cdiv((int64_t)L, (int64_t)RED_NT * 8), 1024);
             if ((size_t)rows * (g1 + g2) * 2 > h->frames_floats)
-                PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d L=%d exceeds the workspace", rows, L);
+                PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d exceeds the workspace", who, rows, L);
             double* part = reinterpret_cast<double*>(h->d_frames);     // the frame workspace is idle for these norms
             if (nt == PAA_NORM_TV)
                 hipLaunchKernelGGL((k_reduce2<RED_TV, true>), dim3(g1 + g2, rows), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_src,
@@ -847,7 +880,7 @@ static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const fl
             PAA_LAUNCH_CHECK();
             ApplyArgs a{};
             a.part = part; a.g1 = g1; a.g2 = g2; a.scal = h->d_scal;
-            a.numel_clean = (double)nc; a.numel_p = (double)L; a.clip_len = (double)L;
+            a.numel_clean = (double)nc; a.numel_p = (double)L; a.clip_len = (double)L; a.rscale = d_scale;
             a.snr_db = prm->snr_db; a.snr_linear = (float)pow(10.0, (double)prm->snr_db / 10.0);
             a.eps = (nt == PAA_NORM_L2) ? prm->l2_size : prm->tv_epsilon;
             const dim3 grid(std::min(cdiv((int64_t)L, (int64_t)RED_NT * 4), 128), rows);
@@ -861,7 +894,7 @@ static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const fl
         case PAA_NORM_MIN_MAX_FREQS:
         case PAA_NORM_MAX_PHON:
         case PAA_NORM_MASKING: {
-            PAA_TRY(check_rows(h, rows, L, "paa_project_rows"));
+            PAA_TRY(check_rows(h, rows, L, who));
             const bool fm = nt == PAA_NORM_FLETCHER_MUNSON;
             const int T = 1 + L / h->hop;
             if (nt == PAA_NORM_MASKING)        // row r under its own clip's bound
@@ -870,14 +903,14 @@ static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const fl
                 SpecArgs a = spec_args(h, L, T, L);
                 a.mask = h->d_mask; a.mask_rs = (int64_t)T * h->F;
                 a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
-                a.x = d_src;
+                a.x = d_src; a.rscale = d_scale;
                 a.out = in_place ? h->d_frames : d_dst;
                 int npart = 0;
                 PAA_TRY(spec_project(a, spec_op_of(nt), rows, &npart, st));
                 if (fm) {                                      // each row re-sums only its own partials
                     hipLaunchKernelGGL(k_spec_finish<true>, dim3(std::min(cdiv((int64_t)L, (int64_t)RED_NT * 4), 128), rows),
                                        dim3(RED_NT), 0, st, (const float*)a.out, d_dst, (int64_t)L, (const double*)a.part,
-                                       npart / rows, prm->fm_epsilon, h->d_scal);
+                                       npart / rows, prm->fm_epsilon, h->d_scal, d_scale);
                     PAA_LAUNCH_CHECK();
                 } else if (in_place) {
                     hipLaunchKernelGGL(k_spec_finish<false>, dim3(std::min(cdiv(n, (int64_t)RED_NT * 4), 1024)), dim3(RED_NT), 0, st,
@@ -887,9 +920,9 @@ static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const fl
                 return PAA_OK;
             }
             if (!in_place) PAA_HIP(hipMemcpyAsync(d_dst, d_src, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
-            if (fm && rows > 2 * MAX_PART) PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d exceeds %d", rows, 2 * MAX_PART);
+            if (fm && rows > 2 * MAX_PART) PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d exceeds %d", who, rows, 2 * MAX_PART);
             FrameArgs a = frame_args(h, L, T);
-            a.x = d_dst;
+            a.x = d_dst; a.rscale = d_scale;
             a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
             float* scal = nullptr;
             if (nt == PAA_NORM_MIN_MAX_FREQS) PAA_TRY(launch_frames<OP_MINMAX>(h, a, rows, st));
@@ -898,7 +931,7 @@ static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const fl
                 PAA_TRY(launch_frames<OP_FM>(h, a, rows, st));
                 scal = reinterpret_cast<float*>(h->d_part);           // rows scales, below the frame partials
                 hipLaunchKernelGGL(k_fm_finalize<true>, dim3(rows), dim3(RED_NT), 0, st, (const double*)a.part, T, prm->fm_epsilon,
-                                   scal);
+                                   scal, d_scale);
                 PAA_LAUNCH_CHECK();
             }
             hipLaunchKernelGGL(k_ola<true>, dim3(cdiv(L, 256), rows), dim3(256), 0, st, h->d_frames, h->d_win, (const float*)scal,
@@ -911,23 +944,36 @@ static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const fl
     }
 }
 
-extern "C" paa_status paa_project_rows(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
-                                       const float* d_clean, int L, void* stream) {
-    if (!h || !prm || !d_src || !d_dst) PAA_FAIL(PAA_ERR_ARG, "paa_project_rows: null argument");
-    if (rows < 1 || L < 2) PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d L=%d", rows, L);
+static paa_status project_rows_entry(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
+                                     const float* d_clean, int L, const float* d_scale, void* stream, const char* who) {
+    if (!h || !prm || !d_src || !d_dst) PAA_FAIL(PAA_ERR_ARG, "%s: null argument", who);
+    if (rows < 1 || L < 2) PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d", who, rows, L);
     if (rows > h->max_batch || L > h->max_len)
-        PAA_FAIL(PAA_ERR_SIZE, "paa_project_rows: rows=%d L=%d exceeds max_batch=%d / max_len=%d", rows, L, h->max_batch, h->max_len);
+        PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d exceeds max_batch=%d / max_len=%d", who, rows, L, h->max_batch, h->max_len);
     if (prm->norm_type < PAA_NORM_L2 || prm->norm_type > PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", prm->norm_type);
     if (d_src != d_dst) {
         const float* lo = d_src < d_dst ? d_src : d_dst;
         const float* hi = d_src < d_dst ? d_dst : d_src;
-        if (lo + (int64_t)rows * L > hi) PAA_FAIL(PAA_ERR_ARG, "paa_project_rows: source and destination overlap");
+        if (lo + (int64_t)rows * L > hi) PAA_FAIL(PAA_ERR_ARG, "%s: source and destination overlap", who);
     }
-    if (rows == 1) {              // one row: the universal projection of that row, the same launches
+    if (d_scale && prm->norm_type == PAA_NORM_MASKING)
+        PAA_FAIL(PAA_ERR_BAD_NORM, "paa_project_rows_scaled: the masking norm takes no bound scale (norm_type %d)", prm->norm_type);
+    if (rows == 1 && !d_scale) {  // one row: the universal projection of that row, the same launches
         if (d_src == d_dst) return project_impl(h, prm, d_dst, 1, d_clean, d_clean ? 1 : 0, L, nullptr, 0.0, stream);
         return project_impl(h, prm, d_dst, 1, d_clean, d_clean ? 1 : 0, L, nullptr, 0.0, stream, d_src);
     }
-    return project_rows_impl(h, prm, d_src, d_dst, rows, d_clean, L, (hipStream_t)stream);
+    // with a scale one row takes the row form too: its reductions are those of the one-row call, partial for partial
+    return project_rows_impl(h, prm, d_src, d_dst, rows, d_clean, L, (hipStream_t)stream, d_scale);
+}
+
+extern "C" paa_status paa_project_rows(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
+                                       const float* d_clean, int L, void* stream) {
+    return project_rows_entry(h, prm, d_src, d_dst, rows, d_clean, L, nullptr, stream, "paa_project_rows");
+}
+
+extern "C" paa_status paa_project_rows_scaled(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
+                                              const float* d_clean, int L, const float* d_scale, void* stream) {
+    return project_rows_entry(h, prm, d_src, d_dst, rows, d_clean, L, d_scale, stream, "paa_project_rows_scaled");
 }
 
 // core/projections.py:68-159 called directly on a spectrum (the reference's project_min_max_freqs / project_fm_norm /

@@ -35,6 +35,7 @@ struct SpecArgs {
     float* wout;           // (rows, T, F) hinge weight W; nullable
     double* lpart;         // loss partials, (clips, lstride): one double per (clip, workgroup, wave)
     int nclip, per_clip, lstride;
+    const float* rscale;   // PHON, row projections: (rows) per-row bound scale s, nullable; the threshold moves by 20 log10(s) dB
 };
 
 // rows x (L) waveform -> per-bin op -> waveform (train.py:38-66 _project_frequency_domain with _align_to), in place allowed

@@ -96,6 +96,12 @@ __device__ __forceinline__ void wave_fft512(v2f (&x)[8], v2f* xb, const LaneTw& 
     pk_dft8<S>(x);
 }
 
+// thr_off of row `row` under the per-row bound scale (paa_project_rows_scaled): + 20 log10(s), exactly + 0.0f for s = 1; a scale
+// that is not a finite positive number acts as 1.  Uniform over the workgroup.
+__device__ __forceinline__ float phon_row_off(const float* __restrict__ rscale, int row) {
+    return 20.f * log10f(row_scale(rscale, row));
+}
+
 struct BinCtx {
     const float* fm; const float* thr; float thr_off;      // thr_off = phon_ref - max(thr)
     float bin_hz, min_f, max_f;
@@ -382,6 +388,7 @@ __global__ __launch_bounds__(NW * 64) void k_spec_fused(SpecArgs a) {
     float* park = reinterpret_cast<float*>(xbuf + NW * XB);   // [NW][1024] (FPW = 2)
     BinCtx c;
     c.fm = a.fm; c.thr = a.thr; c.thr_off = a.phon_ref - (OP == SOP_PHON ? a.thr_max[0] : 0.f);
+    if (OP == SOP_PHON && a.rscale) c.thr_off += phon_row_off(a.rscale, row);
     c.bin_hz = a.bin_hz; c.min_f = a.min_f; c.max_f = a.max_f;
     if (OP == SOP_FM && NFR >= 16) {
         // batched shape: the 10 x 513 weight table goes to LDS once per workgroup: the per-bin lookups (row chosen by the bin's own level)
@@ -497,6 +504,7 @@ __global__ __launch_bounds__(NW * 64) void k_spec_run(SpecArgs a, int bpr) {
     float* carry = reinterpret_cast<float*>(xbuf + NW * XB);  // [3][1024]: frame slots NW-3 .. NW-1 of the previous iteration
     BinCtx c;
     c.fm = a.fm; c.thr = a.thr; c.thr_off = a.phon_ref - (OP == SOP_PHON ? a.thr_max[0] : 0.f);
+    if (OP == SOP_PHON && a.rscale) c.thr_off += phon_row_off(a.rscale, row);
     c.bin_hz = a.bin_hz; c.min_f = a.min_f; c.max_f = a.max_f;
     if (OP == SOP_FM) {
         float* fml = reinterpret_cast<float*>(xbuf + TAIL) + 64;

@@ -16,6 +16,11 @@ the Adam bookkeeping, the masking loss, the device WER counters, the warm-up of 
 
 True clip lengths: with ``lengths=`` the model attacks the utterance and then pads, and ``paa_mask_tail_rows``
 re-zeroes delta_b[len_b:] after every ``paa_project_rows`` (the sign and Adam updates keep a zero tail: its gradient is zero).
+
+Bound search: with ``search=SearchConfig(...)`` every clip carries a bound scale s_b (1 after ``search_reset``).
+``paa_clip_search`` sits between the device WER counters and the update: a clip whose counters say "success" has its delta_b (the
+one that entered the step), s_b and the step number kept in ``best`` / ``best_scale`` / ``best_step`` and its s_b shrunk; the
+projections then run as ``paa_project_rows_scaled`` under the new scales.  No host sync, so the step stays one capturable sequence.
 """
 from __future__ import annotations
 
@@ -23,7 +28,7 @@ import numpy as np
 import torch
 
 from .. import _lib, runtime, synth
-from .modes import LENGTHS, Modes, check, replace
+from .modes import LENGTHS, SEARCH_FLAGS, Ctx, Modes, SearchConfig, check, replace  # noqa: F401  (SearchConfig: re-exported)
 from .pgd import N_STATS, ST_LOSS, _StepperCore
 
 
@@ -31,9 +36,17 @@ class ClipStepper(_StepperCore):
     """The per-clip step: ``step(delta, clean, labels)`` updates ``delta`` (B, L) in place, row b from clip b alone."""
 
     def __init__(self, model, args, length: int, interp=None, spl_thresh=None, optimizer=None, device_wer=False, canon=None,
-                 r_cap=None, log_cap=4096):
+                 r_cap=None, log_cap=4096, search=None):
         """``device_wer`` / ``canon`` / ``r_cap`` / ``log_cap`` as PgdStepper's; ``wer_rows[:B]`` keeps the per-clip (errors,
-        reference words, hypothesis words) of the last step."""
+        reference words, hypothesis words) of the last step.  ``search``: a ``SearchConfig`` switches the per-clip bound search on
+        (module docstring); it needs ``device_wer=True``, and ``refs`` are then the transcripts success is judged against (the
+        target transcript in targeted mode).  Call ``search_reset(B)`` before the first step of every batch."""
+        self.search = search
+        if search is not None:
+            check(replace(Modes.of(args), search_on=True), SEARCH_FLAGS, Ctx(search=search))
+            if not device_wer:
+                raise ValueError("the bound search decides success from the on-device WER counters: build the stepper with "
+                                 "device_wer=True")
         self.max_batch = int(model.max_batch)
         super().__init__(model, args, length, interp, spl_thresh, optimizer, device_wer, canon, r_cap, log_cap, self.max_batch,
                          int(length))
@@ -41,6 +54,30 @@ class ClipStepper(_StepperCore):
         self.grad = self.grad_buf[: self.L].view(1, self.L)
         self.stats = torch.zeros(N_STATS, dtype=torch.float32, device=self.dev)
         self.mask_rows = torch.zeros(self.max_batch, dtype=torch.float32, device=self.dev)      # l_b of the last step
+        if search is not None:
+            nb = self.max_batch
+            self.scale = torch.ones(nb, dtype=torch.float32, device=self.dev)          # s_b the next projection runs under
+            self.best = torch.zeros(nb, self.L, dtype=torch.float32, device=self.dev)  # delta_b of clip b's last success
+            self.best_scale = torch.ones(nb, dtype=torch.float32, device=self.dev)     # ... the scale it was projected under
+            self.best_step = torch.full((nb,), -1, dtype=torch.int32, device=self.dev)  # ... its step, -1: no success yet
+            self.search_step = torch.zeros(1, dtype=torch.int32, device=self.dev)      # device step counter
+
+    def search_reset(self, B=None):
+        """A new batch: scale = 1, best_step = -1, step = 0 (stream-ordered fills, outside any graph).  ``best`` rows and
+        ``best_scale`` need no reset: they are read only where best_step >= 0."""
+        if self.search is None:
+            raise RuntimeError("the stepper was built without a bound search (search=SearchConfig(...))")
+        B = self.max_batch if B is None else int(B)
+        self.scale[:B].fill_(1.0)
+        self.best_scale[:B].fill_(1.0)
+        self.best_step[:B].fill_(-1)
+        self.search_step.zero_()
+
+    def _replay_state(self):
+        st = super()._replay_state()
+        if self.search is not None:
+            st += [self.scale, self.best, self.best_scale, self.best_step, self.search_step]
+        return st
 
     def _check_adam_shape(self):
         if self.adam_p.dim() != 2 or self.adam_p.shape[1] != self.L or self.adam_p.shape[0] > self.max_batch:
@@ -73,9 +110,19 @@ class ClipStepper(_StepperCore):
             self._wer(r["logits"], B)
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr()
+            sc = self.search
+            if sc is not None:       # the counters are those of the delta that entered the step: keep it BEFORE the update
+                _lib.check(lib.paa_clip_search(_lib.ptr(delta), B, L, _lib.ptr(self.wer_rows), int(bool(sc.targeted)),
+                                               int(sc.wer_milli), float(sc.shrink), float(sc.floor_scale), _lib.ptr(self.scale),
+                                               _lib.ptr(self.best), _lib.ptr(self.best_scale), _lib.ptr(self.best_step),
+                                               _lib.ptr(self.search_step), st))
             self._update(delta, grad, B * L)
             for prm in self._prm:
-                _lib.check(lib.paa_project_rows(self.proj.h, prm, _lib.ptr(delta), _lib.ptr(delta), B, _lib.ptr(clean), L, st))
+                if sc is not None:
+                    _lib.check(lib.paa_project_rows_scaled(self.proj.h, prm, _lib.ptr(delta), _lib.ptr(delta), B, _lib.ptr(clean),
+                                                           L, _lib.ptr(self.scale), st))
+                else:
+                    _lib.check(lib.paa_project_rows(self.proj.h, prm, _lib.ptr(delta), _lib.ptr(delta), B, _lib.ptr(clean), L, st))
                 if self.lengths_on:
                     _lib.check(lib.paa_mask_tail_rows(_lib.ptr(delta), B, L, _lib.ptr(self.model._lengths), st))
         if self.device_wer:
@@ -101,9 +148,14 @@ class ClipStepper(_StepperCore):
         """One step on fixed buffers as ONE hipGraph (``refs`` / ``lengths`` as PgdStepper.capture).  Returns (graph, result dict);
         ``graph.replay()`` re-runs the step in place on ``delta`` with whatever ``clean`` / ``labels`` hold.  With Adam the graph is
         wrapped so that every replay first pushes the step's scalars, and the warm-up step is undone (delta, moments and step
-        count as before the call)."""
+        count as before the call).  With a bound search the warm-up step is undone with either update — delta and the search
+        buffers (scale, best, best_scale, best_step, step) are as before the call, so the first replay is the step an eager
+        call would have been."""
         delta, clean = self._checked(delta, clean)
+        keep = delta.detach().clone() if self.search is not None else None
         lab, logits_out = self._warm_up(delta, clean, labels, logits_out, refs, lengths)
+        if keep is not None:
+            delta.detach().copy_(keep)
         return self._capture_body(delta, clean, lab, logits_out)
 
 
@@ -139,9 +191,26 @@ def mask_tail_rows(delta: torch.Tensor, lengths) -> torch.Tensor:
     return delta
 
 
-def project_rows(delta: torch.Tensor, clean: torch.Tensor, args, interp=None, spl_thresh=None, lengths=None) -> torch.Tensor:
+def _scale_dev(scale, B, dev):
+    """The per-row bound scales as a float32 (B) device tensor.  A host array is validated (finite, > 0); a device tensor is
+    taken as it is: the kernels treat a value that is not a finite positive number as 1."""
+    if isinstance(scale, torch.Tensor) and scale.is_cuda:
+        if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() < B or not scale.is_contiguous():
+            raise ValueError(f"scale must be a contiguous float32 tensor of at least {B} elements, got {scale.dtype} "
+                             f"{tuple(scale.shape)}")
+        return scale.to(dev)
+    s = np.asarray(scale.cpu() if isinstance(scale, torch.Tensor) else scale, dtype=np.float64).reshape(-1)
+    if s.size != B:
+        raise ValueError(f"scale must hold one value per row ({B}), got {s.size}")
+    if not (np.isfinite(s).all() and (s > 0).all()):
+        raise ValueError(f"every bound scale must be finite and > 0, got {s.tolist()}")
+    return torch.from_numpy(s.astype(np.float32)).to(dev)
+
+
+def project_rows(delta: torch.Tensor, clean: torch.Tensor, args, interp=None, spl_thresh=None, lengths=None, scale=None) -> torch.Tensor:
     """perturbation_constraint (train.py:69-99) on every row of ``delta`` (B, L) against its own clip of ``clean`` (B, L),
-    in place; the norms of ``args.norm_type`` in order.  ``lengths``: delta_b[len_b:] is re-zeroed after every projection."""
+    in place; the norms of ``args.norm_type`` in order.  ``lengths``: delta_b[len_b:] is re-zeroed after every projection.
+    ``scale`` (B): row b's bound is tightened by scale[b] (paa_project_rows_scaled)."""
     m = Modes.of(args)
     if lengths is not None:
         check(replace(m, lengths_on=True), LENGTHS)
@@ -151,14 +220,19 @@ def project_rows(delta: torch.Tensor, clean: torch.Tensor, args, interp=None, sp
         raise ValueError(f"delta {tuple(delta.shape)} and clean_audio {tuple(clean.shape)} must both be (B, L)")
     B, L = delta.shape
     pr = runtime.get_proj(args, delta.device, B, L, interp)
+    sc = None if scale is None else _scale_dev(scale, B, delta.device)
     with torch.cuda.device(delta.device):
         for n in m.norms:
             if n not in _lib.NORM_IDS:
                 raise ValueError(f"Unknown norm_type: {n!r}")
             if n == "max_phon":
                 pr.set_spl_thresh(spl_thresh)
-            _lib.check(_lib.lib().paa_project_rows(pr.h, runtime.params_of(args, n), _lib.ptr(delta), _lib.ptr(delta), B,
-                                                   _lib.ptr(clean), L, _lib.stream_ptr()))
+            if sc is None:
+                _lib.check(_lib.lib().paa_project_rows(pr.h, runtime.params_of(args, n), _lib.ptr(delta), _lib.ptr(delta), B,
+                                                       _lib.ptr(clean), L, _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().paa_project_rows_scaled(pr.h, runtime.params_of(args, n), _lib.ptr(delta), _lib.ptr(delta), B,
+                                                              _lib.ptr(clean), L, _lib.ptr(sc), _lib.stream_ptr()))
             if lengths is not None:
                 mask_tail_rows(delta, lengths)
     return delta

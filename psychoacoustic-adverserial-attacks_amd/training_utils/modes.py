@@ -22,6 +22,7 @@ class Modes:
     lengths_on: bool               # --clip_lengths true
     device_wer: bool
     optimizer_type: str
+    search_on: bool = False        # --bound_search other than "off" (attack_clips only)
 
     @classmethod
     def of(cls, args=None, **flags):
@@ -32,19 +33,53 @@ class Modes:
         shift, gain, alpha = get("place_shift", "none"), _num(get("place_gain_db", 0.0)), _num(get("masking_loss_alpha", 0.0) or 0.0)
         on = get("perturbation_seconds", None) is not None or shift == "random" or (isinstance(gain, float) and gain > 0)
         return cls(norms, "masking" in norms, alpha, on, shift, gain, str(get("rir_bank", "none")) != "none",
-                   str(get("clip_lengths", "padded")) == "true", bool(get("device_wer", False)), get("optimizer_type", None))
+                   str(get("clip_lengths", "padded")) == "true", bool(get("device_wer", False)), get("optimizer_type", None),
+                   str(get("bound_search", "off")) != "off")
 
     shift_on = property(lambda m: m.place_shift == "random")
     masking = property(lambda m: m.masking_norm or m.alpha > 0)      # either pairs delta's frames with the clean clip's
 
 
-# eager_adam: torch's own optimizer.step() runs the update, not the device step; L / Lp: clip / perturbation length, where known
-Ctx = namedtuple("Ctx", "world eager_adam L Lp", defaults=(1, False, None, None))
+SIZED_NORMS = ("l2", "linf", "snr", "tv", "fletcher_munson", "max_phon")      # the norms a bound scale tightens (min_max_freqs has no size)
+
+
+class SearchConfig(namedtuple("SearchConfig", "shrink floor_scale wer_milli targeted")):
+    """The per-clip bound search (DESIGN.md §6j): on success a clip's bound scale is multiplied by ``shrink`` down to ``floor_scale``;
+    untargeted success is per-clip WER >= ``wer_milli`` / 1000, targeted success the target transcript exactly."""
+
+    @classmethod
+    def of(cls, args):
+        """The flags of ``args`` as they are (the "search_range" rule judges them); None with the search off."""
+        if str(getattr(args, "bound_search", "off")) == "off":
+            return None
+        wer = getattr(args, "search_success_wer", 0.5)
+        milli = int(round(float(wer) * 1000)) if isinstance(wer, (int, float)) and wer == wer and abs(wer) < 1e6 else 0
+        return cls(getattr(args, "search_shrink", 0.8), getattr(args, "search_floor", 0.01), milli,
+                   getattr(args, "attack_mode", "untargeted") == "targeted")
+
+    def bad(self):
+        """None, or the first value out of range."""
+        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+        if not (num(self.shrink) and 0.0 < self.shrink < 1.0):
+            return f"search_shrink must lie in (0, 1), got {self.shrink}"
+        if not (num(self.floor_scale) and 0.0 < self.floor_scale <= 1.0):
+            return f"search_floor must lie in (0, 1], got {self.floor_scale}"
+        if not (isinstance(self.wer_milli, int) and self.wer_milli >= 1):
+            return "search_success_wer must be at least 0.0005 (it is rounded to thousandths)"
+        return None
+
+
+# eager_adam: torch's own optimizer.step() runs the update, not the device step; L / Lp: clip / perturbation length, where known;
+# search: the SearchConfig of the run; wer_why: why the device WER route is not available (None: it is)
+class Ctx(namedtuple("Ctx", "world eager_adam L Lp search wer_why", defaults=(1, False, None, None, None, None))):
+    __slots__ = ()
+    search_why = property(lambda c: "bound search is on without a SearchConfig" if c.search is None else c.search.bad())
 # mode: the field of Modes that must be on for the rule to apply, or None; when(modes, ctx); msg: formatted with m = modes, c = ctx
 Rule = namedtuple("Rule", "mode when exc msg")
 _PAIRS = ": both pair the perturbation's frames with the clean clip's frames"
 _DEVICE_STEP = " the device step: use the defaults of torch.optim.Adam(lr=...) or --optimizer_type pgd"
 _NO_LEN = "--clip_lengths true does not support "
+_SEARCH = "--bound_search shrink "
 _UNIVERSAL = "the universal perturbation (paa_amd.run_attack); per-clip perturbations have no "
 NIE = NotImplementedError
 RULES = {
@@ -78,12 +113,23 @@ RULES = {
                       _NO_LEN + "placement (--perturbation_seconds, --place_shift, --place_gain_db)"),
     "len_rir": Rule("lengths_on", lambda m, c: m.rir_on, ValueError, _NO_LEN + "--rir_bank"),
     "len_eager": Rule("lengths_on", lambda m, c: c.eager_adam, NIE, "--clip_lengths true needs" + _DEVICE_STEP),
+    # per-clip bound search
+    "search_range": Rule("search_on", lambda m, c: c.search is None or c.search.bad() is not None, ValueError,
+                         "{c.search_why}"),
+    "search_masking": Rule("search_on", lambda m, c: m.masking_norm, NIE, _SEARCH + "is not implemented with --norm_type masking: "
+                           "a per-clip threshold with a moving margin is a change of its own"),
+    "search_no_size": Rule("search_on", lambda m, c: not any(n in SIZED_NORMS for n in m.norms), ValueError,
+                           _SEARCH + "needs a norm with a size to shrink; {m.norms} has none"),
+    "search_route": Rule("search_on", lambda m, c: c.wer_why is not None, NIE,
+                         _SEARCH + "decides success from the on-device WER counters, which are not available: {c.wer_why}"),
 }
 
 PLACE_FLAGS = ("shift_range", "gain_range", "place_masking")
 PLACE = PLACE_FLAGS + ("place_snr_tv", "place_eager")
 ROOMS = ("rir_masking", "rir_eager")
 LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir")
+SEARCH_FLAGS = ("search_range", "search_masking", "search_no_size")       # known from the flags alone
+SEARCH = SEARCH_FLAGS + ("search_route",)                                  # ... and once the vocabulary and the references are known
 
 
 def check(m: Modes, keys, c: Ctx = Ctx()) -> Modes:

@@ -26,9 +26,12 @@
     ``set_lengths``)                           frames, masked compose / attention / CTC
                                                paa_model_frame_counts, paa_argmax_ids_len                 in place of paa_argmax_ids (device WER)
                                                paa_mask_tail_rows (per-clip step only)                    after every paa_project_rows
+    bound search (``search=SearchConfig``;     paa_clip_search                                           after the device WER counters, before
+    per-clip step only; needs device WER)                                                                 the update
+                                               paa_project_rows_scaled                                    in place of paa_project_rows
 
-A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off and lengths off are the
-plain step, bit for bit.
+A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off, lengths off and no bound
+search are the plain step, bit for bit.
 
 Which modes may run together, and which refusal wins when several apply, is decided in one table: training_utils/modes.py.  What
 a mode means is written where it is built: place.py, rir.py (§6g), ``set_lengths`` and PaaModel.set_lengths (§6h).
