@@ -628,7 +628,7 @@ void launch_ring_cfg(int cfg, const GemmArgs& g, hipStream_t st);
 void launch_ring2_cfg(int cfg, const GemmArgs& g, hipStream_t st);      // gemm_ring2.hip: configurations 20..23
 int ring_tile_rows(int cfg);
 int ring_tile_cols(int cfg);
-bool ring_cfg_ok(int cfg, const paa_gemm_desc& d);
+bool ring_cfg_ok(int cfg, const paa_gemm_desc& d, bool forced = false);
 
 // Ring-kernel selection (paa_gemm_config): 0 = automatic, 1 = never (the register-staged kernels of round 1),
 // 2.. = force one ring configuration where its shape constraints hold (kernel A/B runs in tools/gemm_bench.py).
@@ -656,6 +656,38 @@ bool gemm_env_no_bil() {
 bool gemm_env_kgroup() {
     if (!g_env.init) gemm_env_refresh();
     return g_env.kgroup;
+}
+
+// Epilogue kind of a product (gemm_dev.h, EPK_*): a kind only where EVERY epilogue field matches its definition exactly — anything
+// else (alpha != 1, accumulate, an unexpected bias, a bf16 gate, aux and residual together, a row mask outside GELU_FWD, ...) takes
+// the generic epilogue.  The ring kernels of gemm_ring2.hip pick their instantiation by it.
+static int g_last_kind = EPK_GENERIC;          // diagnostic builds: tools/gemm_stamps.py prints it
+static int classify_epilogue(const paa_gemm_desc& d) {
+#ifdef PAA_EXPERIMENTS      // tools/model_ab.py: the generic epilogue everywhere (read per launch)
+    { const char* e = getenv("PAA_NO_EPIK"); if (e && e[0] == '1') return EPK_GENERIC; }
+#endif
+    if (d.alpha != 1.f || d.accumulate || d.aux_bf16 || !d.precision) return EPK_GENERIC;
+    const bool il = d.Cb_il && !d.Cb && !d.Cb_lo, planar = d.Cb && d.Cb_lo && !d.Cb_il, no_planes = !d.Cb && !d.Cb_lo && !d.Cb_il;
+    const bool mask = d.row_period > 0;
+    switch (d.act) {
+        case PAA_ACT_GELU:
+            return (d.bias && d.C_pre && d.aux_gate && il && !d.C && !d.aux && !d.residual && !d.res_ln_stats) ? EPK_GELU_FWD : EPK_GENERIC;
+        case PAA_ACT_GELU_GRAD:
+            if (!(d.aux && d.aux_gate && (il || planar) && !d.bias && !d.C && !d.C_pre && !d.residual && !d.res_ln_stats && !mask)) return EPK_GENERIC;
+#ifdef PAA_EXPERIMENTS      // tools/model_ab.py epik_la2 / epik_la4: the aux stream 2 / 4 row groups ahead
+            { const char* e = getenv("PAA_EPIK_AHEAD"); if (e && e[0] == '2') return EPK_GELU_GRAD_LA2; if (e && e[0] == '4') return EPK_GELU_GRAD_LA4; }
+#endif
+            return EPK_GELU_GRAD;
+        case PAA_ACT_NONE:
+            if (d.C_pre || d.aux || d.aux_gate || mask) return EPK_GENERIC;
+            if (d.C && no_planes && d.residual) {
+                if (d.res_ln_stats) return d.bias ? EPK_RESID_LN : EPK_GENERIC;
+                return d.bias ? EPK_GENERIC : EPK_RESID;
+            }
+            if (!d.C && planar && !d.residual && !d.res_ln_stats) return EPK_PLANES;
+            return EPK_GENERIC;
+        default: return EPK_GENERIC;
+    }
 }
 
 template <int BN, int PREC>
@@ -707,6 +739,7 @@ paa_status gemm(const paa_gemm_desc& d, hipStream_t st) {
         PAA_FAIL(PAA_ERR_ARG, "gemm: res_ln_stats needs a residual, gain and bias (16-byte aligned), batch 1 and no GELU_GRAD");
     GemmArgs g;
     g.d = d;
+    g.kind = EPK_GENERIC;
     const bool narrow = d.N <= 64;
     const int bn = narrow ? 64 : 128;
     // 256 x 128 tile (8 waves, 2 workgroups per CU) for every large-M product; 128 x 128 (4 waves) was 4-8 % faster on
@@ -734,7 +767,10 @@ paa_status gemm(const paa_gemm_desc& d, hipStream_t st) {
     }
     // ring kernel: 0 = off, else the configuration id (see the dispatch below)
     int ring = 0;
-    if (tall && g_ring_mode != 1 && d.N >= 128) {
+    // A FORCED separate-ring configuration (paa_gemm_config(20..23): tests, kernel A/B runs) also takes shapes below the automatic
+    // selection's floor — few rows, K an odd number of slabs (three or more): the kernels clamp the rows past M / N and walk whole K slabs.
+    const bool forced2 = g_ring_mode >= 20 && vec && d.a_kseg <= 0 && ring_cfg_ok(g_ring_mode, d, true);
+    if ((tall || forced2) && g_ring_mode != 1 && d.N >= 128) {
         const int64_t t256 = (int64_t)cdiv(d.M, 256) * cdiv(d.N, 256) * d.batch, t128 = (int64_t)cdiv(d.M, 256) * cdiv(d.N, 128) * d.batch;
         // Measured on the step's shapes (tools/gemm_ring_bench.py, profiles/r2_gemm_ab.txt): the 192 x 128 ring kernels at
         // two workgroups per CU win wherever 256-row tiles leave the persistent grid's last round part-empty (N = 768:
@@ -793,7 +829,7 @@ paa_status gemm(const paa_gemm_desc& d, hipStream_t st) {
         if (ring == 13) { if (!d.precision) ring = 0; }          // 13: register-staged 192 x 128 split tile, swizzled LDS, two workgroups per CU
         else
 #endif
-        if (ring && !ring_cfg_ok(ring, d)) ring = 0;
+        if (ring && !ring_cfg_ok(ring, d, forced2)) ring = 0;
         if (ring && ring < 20 && d.A_il) ring = 0;               // interleaved A: gemm_ring2.hip and the register-staged kernels
     }
     const int ring_bn = ring == 13 ? 128 : ring ? ring_tile_cols(ring) : 0, ring_bm = ring == 13 ? 192 : ring ? ring_tile_rows(ring) : 0;
@@ -855,7 +891,18 @@ paa_status gemm(const paa_gemm_desc& d, hipStream_t st) {
         if (ring == 13) launch_bf<192, 128, 1, 2, true, false, true>(g, st);
         else
 #endif
-        if (ring >= 20) launch_ring2_cfg(ring, g, st);
+        if (ring >= 20) {
+            // Which kinds are TAKEN: GELU_FWD only — the one whose step A/B showed a gain; the others lengthen the K
+            // loop of their instantiations by more than their epilogues save and exist in -DPAA_EXPERIMENTS builds only, where
+            // PAA_EPIK_MASK (a bit set of 1 << EPK_*; tools/model_ab.py, tools/gemm_stamps.py, the tests) switches them on per launch.
+            g.kind = g_last_kind = classify_epilogue(d);
+            int taken = 1 << EPK_GELU_FWD;
+#ifdef PAA_EXPERIMENTS
+            { const char* e = getenv("PAA_EPIK_MASK"); const int mask = e ? atoi(e) : 0; if (mask > 0) taken = mask; }
+#endif
+            if (!((taken >> g.kind) & 1)) g.kind = EPK_GENERIC;
+            launch_ring2_cfg(ring, g, st);
+        }
         else launch_ring_cfg(ring, g, st);
     } else if (d.operand_bf16) {
         const bool seg = d.a_kseg > 0 || (d.K & 63);          // segmented / windowed A or a K tail: general loader
@@ -921,6 +968,10 @@ extern "C" paa_status paa_prof_pause(int paused) {
     paa::g_prof.on = !paused && paa::g_prof.cap > 0;
     return PAA_OK;
 }
+
+#ifdef PAA_EXPERIMENTS
+extern "C" int paa_debug_last_epilogue_kind() { return paa::g_last_kind; }      // kind of the last separate-ring launch (tools/gemm_stamps.py)
+#endif
 
 extern "C" void paa_gemm_config(int ring_mode) { paa::g_ring_mode = ring_mode; paa::gemm_env_refresh(); }
 

@@ -15,6 +15,64 @@ constexpr int G_BM = 128, G_BK = 32, G_LD = 40 /* bf16 per LDS row */, G_NT = 25
 struct GemmArgs {
     paa_gemm_desc d;
     int tiles_m, tiles_n;
+    int kind;                                  // EPK_*: what gemm.hip's classifier made of d's epilogue fields (ring kernels only)
+};
+
+// ---- epilogue kinds -------------------------------------------------------------------------------
+// The vector epilogue is ONE function body whose descriptor tests go through a traits type: each field is EPI_NO / EPI_YES (a
+// compile-time constant: the statements behind it fold away or run unconditionally) or EPI_RT (read from the descriptor, as
+// before).  EpiGeneric reads everything at run time — the epilogue every kernel had; the other kinds fix the field pattern of
+// one class of the model's fp32-parity products (classify_epilogue in gemm.hip maps a descriptor to a kind only on an exact
+// match).  Every kind runs the same arithmetic statements in the same order, so results are bit-identical to EpiGeneric.
+enum { EPK_GENERIC = 0, EPK_GELU_FWD = 1, EPK_GELU_GRAD = 2, EPK_RESID = 3, EPK_RESID_LN = 4, EPK_PLANES = 5,
+       EPK_GELU_GRAD_LA2 = 6, EPK_GELU_GRAD_LA4 = 7, EPK_COUNT = 8 };      // GELU_GRAD with 2 / 4 row groups of aux lookahead (experiment)
+enum { EPI_NO = 0, EPI_YES = 1, EPI_RT = 2 };
+template <int S>
+__device__ __forceinline__ bool epi_on(bool rt) {
+    if constexpr (S == EPI_RT) return rt;
+    else return S == EPI_YES;
+}
+//                       ACT < 0: d.act      bias  f32 C  C_pre  bf16 gate  aux_gate  Cb_il  Cb  Cb_lo  residual  res_ln  row mask  accumulate  alpha = 1
+struct EpiGeneric {      // everything from the descriptor
+    static constexpr int ACT = -1, BIAS = EPI_RT, C = EPI_RT, CPRE = EPI_RT, X16 = EPI_RT, GATE = EPI_RT, CIL = EPI_RT, CB = EPI_RT, CBLO = EPI_RT,
+                         RES = EPI_RT, RLN = EPI_RT, PERIOD = EPI_RT, ACCUM = EPI_RT;
+    static constexpr bool ALPHA1 = false;
+    static constexpr int AHEAD = 1;          // row groups (8 rows) the extra operand stream is requested ahead of its use
+};
+struct EpiGeluFwd {      // bias + GELU, f32 gate kept in C_pre, interleaved planes out (FFN up; a conv forward product when it has a bias); row mask either way
+    static constexpr int ACT = PAA_ACT_GELU, BIAS = EPI_YES, C = EPI_NO, CPRE = EPI_YES, X16 = EPI_NO, GATE = EPI_YES, CIL = EPI_YES, CB = EPI_NO, CBLO = EPI_NO,
+                         RES = EPI_NO, RLN = EPI_NO, PERIOD = EPI_RT, ACCUM = EPI_NO;
+    static constexpr bool ALPHA1 = true;
+    static constexpr int AHEAD = 1;
+};
+struct EpiGeluGrad {     // acc x f32 gate, planes out — interleaved or planar hi + lo (conv dgrads, FFN-down dgrad); no bias registers
+    static constexpr int ACT = PAA_ACT_GELU_GRAD, BIAS = EPI_NO, C = EPI_NO, CPRE = EPI_NO, X16 = EPI_NO, GATE = EPI_YES, CIL = EPI_RT, CB = EPI_YES, CBLO = EPI_YES,
+                         RES = EPI_NO, RLN = EPI_NO, PERIOD = EPI_NO, ACCUM = EPI_NO;
+    static constexpr bool ALPHA1 = true;
+    static constexpr int AHEAD = 1;
+};
+// experiment: the aux stream AH row groups ahead instead of one — 8 registers per group, which the folded kind has to spare
+template <int AH>
+struct EpiGeluGradAhead : EpiGeluGrad {
+    static constexpr int AHEAD = AH;
+};
+struct EpiResid {        // f32 C = acc + f32 residual (FFN-up dgrad, QKV dgrad)
+    static constexpr int ACT = PAA_ACT_NONE, BIAS = EPI_NO, C = EPI_YES, CPRE = EPI_NO, X16 = EPI_NO, GATE = EPI_NO, CIL = EPI_NO, CB = EPI_NO, CBLO = EPI_NO,
+                         RES = EPI_YES, RLN = EPI_NO, PERIOD = EPI_NO, ACCUM = EPI_NO;
+    static constexpr bool ALPHA1 = true;
+    static constexpr int AHEAD = 1;
+};
+struct EpiResidLn {      // f32 C = acc + bias + LN(stored x) through res_ln_stats (out-proj, FFN down)
+    static constexpr int ACT = PAA_ACT_NONE, BIAS = EPI_YES, C = EPI_YES, CPRE = EPI_NO, X16 = EPI_NO, GATE = EPI_NO, CIL = EPI_NO, CB = EPI_NO, CBLO = EPI_NO,
+                         RES = EPI_YES, RLN = EPI_YES, PERIOD = EPI_NO, ACCUM = EPI_NO;
+    static constexpr bool ALPHA1 = true;
+    static constexpr int AHEAD = 1;
+};
+struct EpiPlanes {       // planar hi + lo planes out, bias as a run-time flag (QKV forward, out-proj dgrad)
+    static constexpr int ACT = PAA_ACT_NONE, BIAS = EPI_RT, C = EPI_NO, CPRE = EPI_NO, X16 = EPI_NO, GATE = EPI_NO, CIL = EPI_NO, CB = EPI_YES, CBLO = EPI_YES,
+                         RES = EPI_NO, RLN = EPI_NO, PERIOD = EPI_NO, ACCUM = EPI_NO;
+    static constexpr bool ALPHA1 = true;
+    static constexpr int AHEAD = 1;
 };
 
 // ---- persistent-grid sizing (host) ----------------------------------------------------------------
@@ -151,37 +209,56 @@ __device__ __forceinline__ void quad_transpose(float& x0, float& x1, float& x2, 
     if (o2) { x0 = s; x1 = t; } else { x2 = s; x3 = t; }
 }
 
+// A product that must stay a product: with the epilogue's descriptor tests folded at compile time (the kinds above) the gate multiply and
+// the hi / lo split's subtraction below it become straight-line code, and -ffp-contract would fuse them into one FMA — a differently
+// rounded lo plane than the generic epilogue's, where the two sit in different branches.
+__device__ __forceinline__ float mul_unfused(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 // FAST: GELU / GELU' through the branch-free Abramowitz-Stegun erf (|error| <= 1.5e-7 absolute, paa_common.h) instead of
 // libm's erff.  Since round 2 BOTH precision modes take it in the vector epilogue: the split-bf16 products themselves
 // carry ~2^-16 = 1.5e-5 relative error, a hundred times the erf approximation's, and exact erff made the epilogue of the
 // short-K GELU products (FFN up-projection: 96 outputs per lane x ~50 instructions) as long as their MFMA stream.
 // `ex` is the one extra f32 operand stream of the epilogue: aux (GELU_GRAD) or the residual — the host takes the
 // scalar epilogue when a product asks for both.  All per-lane addresses are 32-bit element offsets from uniform bases.
-template <int MI, bool FAST>
+template <int MI, bool FAST, typename T = EpiGeneric>
 __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&acc)[MI][2], int m0w, int n0w, int z1, int z2, int lane) {
     const int lr = lane & 31, lh = lane >> 5, qa = lr >> 2, qb = lr & 3;
     const bool o1 = qb & 1, o2 = qb & 2;
     const int col = n0w + 8 * qa;                       // this lane's 8 columns
     const int row0 = m0w + 4 * lh + qb;                 // + 32 i + 8 g
     const bool col_ok = col < d.N;
-    const int act = d.act;
+    const int act = T::ACT < 0 ? d.act : T::ACT;
     const bool gg = act == PAA_ACT_GELU_GRAD;
     const int64_t cbase = z1 * d.c_s1 + z2 * d.c_s2;
-    float* __restrict__ C = d.C ? d.C + cbase : nullptr;
-    const bool x16 = d.aux_bf16 != 0;                   // C_pre / aux stored as bf16
-    const bool gate = d.aux_gate != 0;                  // C_pre / aux hold gelu'(v)
-    float* __restrict__ Cp = (d.C_pre && !x16) ? d.C_pre + cbase : nullptr;
-    unsigned short* __restrict__ Cp16 = (d.C_pre && x16) ? reinterpret_cast<unsigned short*>(d.C_pre) + cbase : nullptr;
-    unsigned short* __restrict__ Cb = d.Cb ? reinterpret_cast<unsigned short*>(d.Cb) + cbase : nullptr;
-    unsigned short* __restrict__ Cbl = d.Cb_lo ? reinterpret_cast<unsigned short*>(d.Cb_lo) + cbase : nullptr;
+    // Each stream's pointer is formed as before (null when the stream is off); has_* is what the statements below test: the pointer where
+    // the fields behind it are run-time values (EpiGeneric: the code this epilogue always was), a constant where the kind fixes them.
+    float* __restrict__ C = epi_on<T::C>(d.C != nullptr) ? d.C + cbase : nullptr;
+    const bool has_c = T::C == EPI_RT ? C != nullptr : T::C == EPI_YES;
+    const bool x16 = epi_on<T::X16>(d.aux_bf16 != 0);   // C_pre / aux stored as bf16
+    const bool gate = epi_on<T::GATE>(d.aux_gate != 0); // C_pre / aux hold gelu'(v)
+    float* __restrict__ Cp = (epi_on<T::CPRE>(d.C_pre != nullptr) && !x16) ? d.C_pre + cbase : nullptr;
+    unsigned short* __restrict__ Cp16 = (epi_on<T::CPRE>(d.C_pre != nullptr) && x16) ? reinterpret_cast<unsigned short*>(d.C_pre) + cbase : nullptr;
+    constexpr bool PRE_RT = T::CPRE == EPI_RT || T::X16 == EPI_RT;
+    const bool has_cp = PRE_RT ? Cp != nullptr : (T::CPRE == EPI_YES && T::X16 == EPI_NO);
+    const bool has_cp16 = PRE_RT ? Cp16 != nullptr : (T::CPRE == EPI_YES && T::X16 == EPI_YES);
+    unsigned short* __restrict__ Cb = epi_on<T::CB>(d.Cb != nullptr) ? reinterpret_cast<unsigned short*>(d.Cb) + cbase : nullptr;
+    unsigned short* __restrict__ Cbl = epi_on<T::CBLO>(d.Cb_lo != nullptr) ? reinterpret_cast<unsigned short*>(d.Cb_lo) + cbase : nullptr;
     // interleaved result planes (gemm.h, Cb_il): this lane's 8 columns sit inside one 32-column group, so the hi and the lo vector of
     // a row are two 16-byte stores 64 bytes apart; Cb then points at the array and Cbl at the same array + 32 elements
-    const bool cil = d.Cb_il != nullptr;
+    const bool cil = epi_on<T::CIL>(d.Cb_il != nullptr);
     if (cil) { Cb = reinterpret_cast<unsigned short*>(d.Cb_il) + 2 * cbase; Cbl = Cb + 32; }
+    const bool has_cb = (T::CIL == EPI_YES || T::CB == EPI_YES) ? true : (T::CIL == EPI_NO && T::CB == EPI_NO) ? false : Cb != nullptr;
+    const bool has_cbl = (T::CIL == EPI_YES || T::CBLO == EPI_YES) ? true : (T::CIL == EPI_NO && T::CBLO == EPI_NO) ? false : Cbl != nullptr;
     const bool ex16 = gg && x16;                        // the extra stream is bf16: 8 columns = one 16-byte vector
     const float* __restrict__ ex = gg ? (ex16 ? nullptr : d.aux + z1 * d.aux_s1 + z2 * d.aux_s2)
-                                      : (d.residual ? d.residual + z1 * d.res_s1 + z2 * d.res_s2 : nullptr);
+                                      : (epi_on<T::RES>(d.residual != nullptr) ? d.residual + z1 * d.res_s1 + z2 * d.res_s2 : nullptr);
     const unsigned short* __restrict__ exh = ex16 ? reinterpret_cast<const unsigned short*>(d.aux) + z1 * d.aux_s1 + z2 * d.aux_s2 : nullptr;
+    constexpr bool EX_RT = T::ACT < 0 || T::X16 == EPI_RT || T::RES == EPI_RT;
+    const bool has_ex = EX_RT ? ex != nullptr : (gg ? !ex16 : T::RES == EPI_YES);       // ... is f32: aux or the residual
+    const bool has_exh = EX_RT ? exh != nullptr : ex16;
     const unsigned ldc = (unsigned)d.ldc, ldx = (unsigned)(gg ? d.ld_aux : d.ld_res);
     const unsigned co = (unsigned)row0 * ldc + (unsigned)col;
     const unsigned cob = cil ? (unsigned)row0 * 2u * ldc + (((unsigned)col >> 5) << 6) + ((unsigned)col & 31u) : co;      // bf16 result offset
@@ -190,14 +267,14 @@ __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&ac
     float bv[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) bv[k] = 0.f;
-    if (d.bias && col_ok) {
+    if (epi_on<T::BIAS>(d.bias != nullptr) && col_ok) {
         const float* bp = d.bias + z2 * d.bias_s2;
         const float4 b0 = *reinterpret_cast<const float4*>(bp + (unsigned)col);
         const float4 b1 = *reinterpret_cast<const float4*>(bp + (unsigned)col + 4u);
         bv[0] = b0.x; bv[1] = b0.y; bv[2] = b0.z; bv[3] = b0.w; bv[4] = b1.x; bv[5] = b1.y; bv[6] = b1.z; bv[7] = b1.w;
     }
     // residual = LayerNorm(stored input) (gemm.h, res_ln_stats): gain / bias of this lane's 8 columns
-    const bool rln = d.res_ln_stats != nullptr && !gg && ex != nullptr;
+    const bool rln = epi_on<T::RLN>(d.res_ln_stats != nullptr) && !gg && has_ex;
     // 256-row tiles (MI = 4: 128 accumulator registers per wave at a 256-register budget) cannot afford 16 registers for them across
     // the row groups — held there, the compiler spilled and reloaded other epilogue state around every store burst, each reload behind
     // an s_waitcnt vmcnt(0) that also waits for the stores.  They re-read the 8 columns' gain / bias per row group instead (cache hits;
@@ -212,31 +289,33 @@ __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&ac
         lg[0] = g0.x; lg[1] = g0.y; lg[2] = g0.z; lg[3] = g0.w; lg[4] = g1.x; lg[5] = g1.y; lg[6] = g1.z; lg[7] = g1.w;
         lb[0] = b0.x; lb[1] = b0.y; lb[2] = b0.z; lb[3] = b0.w; lb[4] = b1.x; lb[5] = b1.y; lb[6] = b1.z; lb[7] = b1.w;
     }
-    const int period = d.row_period;
+    const int period = T::PERIOD == EPI_NO ? 0 : d.row_period;
     const int mrem0 = period > 0 ? row0 % period : 0;
-    const float alpha = d.alpha;
-    const bool accum = d.accumulate != 0;
+    const float alpha = T::ALPHA1 ? 1.f : d.alpha;
+    const bool accum = epi_on<T::ACCUM>(d.accumulate != 0);
     constexpr int NG = 4 * MI;                           // row groups of 8 rows: (i, g)
-    uint4 xv[2][2];                                       // raw bits: 2 x float4, or one uint4 of 8 bf16 in [0]
+    constexpr int AH = T::AHEAD < NG ? T::AHEAD : NG - 1, NX = AH + 1;      // groups in flight; a ring of AH + 1 register sets (AH = 1: two)
+    uint4 xv[NX][2];                                      // raw bits: 2 x float4, or one uint4 of 8 bf16 in [0]
 #pragma unroll
-    for (int u = 0; u < 2; ++u) { xv[u][0] = make_uint4(0u, 0u, 0u, 0u); xv[u][1] = xv[u][0]; }
+    for (int u = 0; u < NX; ++u) { xv[u][0] = make_uint4(0u, 0u, 0u, 0u); xv[u][1] = xv[u][0]; }
     auto fetch = [&](int grp, uint4 (&v2)[2]) {
         const int dm = (grp >> 2) * 32 + (grp & 3) * 8;
         if (col_ok && row0 + dm < d.M) {
             const unsigned o = xo + (unsigned)dm * ldx;
-            if (ex) {
+            if (has_ex) {
                 v2[0] = *reinterpret_cast<const uint4*>(ex + o);
                 v2[1] = *reinterpret_cast<const uint4*>(ex + o + 4u);
-            } else if (exh) {
+            } else if (has_exh) {
                 v2[0] = *reinterpret_cast<const uint4*>(exh + o);
             }
         }
     };
-    fetch(0, xv[0]);
+#pragma unroll
+    for (int a = 0; a < AH; ++a) fetch(a, xv[a]);
 #pragma unroll
     for (int grp = 0; grp < NG; ++grp) {
-        const int i = grp >> 2, gq = grp & 3, u = grp & 1;
-        if (grp + 1 < NG) fetch(grp + 1, xv[u ^ 1]);
+        const int i = grp >> 2, gq = grp & 3, u = grp % NX;
+        if (grp + AH < NG) fetch(grp + AH, xv[(grp + AH) % NX]);
         const int dm = i * 32 + gq * 8;
         const bool live = col_ok && row0 + dm < d.M;
         bool dead = false;
@@ -297,19 +376,19 @@ __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&ac
                         x[k] = gelu_f(x[k]);
                     }
                 }
-                if (Cp && live) *reinterpret_cast<float4*>(Cp + ci + 4u * j) = dead ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(kp[0], kp[1], kp[2], kp[3]);
-                if (Cp16) {
+                if (has_cp && live) *reinterpret_cast<float4*>(Cp + ci + 4u * j) = dead ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(kp[0], kp[1], kp[2], kp[3]);
+                if (has_cp16) {
                     pp[2 * j] = dead ? 0u : bf16_pack2(kp[0], kp[1]);
                     pp[2 * j + 1] = dead ? 0u : bf16_pack2(kp[2], kp[3]);
                 }
-                if (ex) {
+                if (has_ex) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) x[k] += e4[k];
                 }
             } else if (gg) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) x[k] *= gate ? e4[k] : (FAST ? gelu_grad_fast(e4[k]) : gelu_grad_f(e4[k]));
-            } else if (ex) {
+                for (int k = 0; k < 4; ++k) x[k] = mul_unfused(x[k], gate ? e4[k] : (FAST ? gelu_grad_fast(e4[k]) : gelu_grad_f(e4[k])));
+            } else if (has_ex) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) x[k] += e4[k];
             }
@@ -317,28 +396,28 @@ __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&ac
 #pragma unroll
                 for (int k = 0; k < 4; ++k) x[k] = 0.f;
             }
-            if (C && live) {
+            if (has_c && live) {
                 if (accum) {
                     const float4 c0 = *reinterpret_cast<const float4*>(C + ci + 4u * j);
                     x[0] += c0.x; x[1] += c0.y; x[2] += c0.z; x[3] += c0.w;
                 }
                 *reinterpret_cast<float4*>(C + ci + 4u * j) = make_float4(x[0], x[1], x[2], x[3]);
             }
-            if (Cb) {                                         // packed conversions: one v_cvt_pk_bf16_f32 per pair and plane
+            if (has_cb) {                                     // packed conversions: one v_cvt_pk_bf16_f32 per pair and plane
                 const unsigned h01 = bf16_pack2(x[0], x[1]), h23 = bf16_pack2(x[2], x[3]);
                 hp[2 * j] = h01; hp[2 * j + 1] = h23;
-                if (Cbl) {
+                if (has_cbl) {
                     lp[2 * j] = bf16_pack2(x[0] - __uint_as_float(h01 << 16), x[1] - __uint_as_float(h01 & 0xFFFF0000u));
                     lp[2 * j + 1] = bf16_pack2(x[2] - __uint_as_float(h23 << 16), x[3] - __uint_as_float(h23 & 0xFFFF0000u));
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (Cp16 && live && act == PAA_ACT_GELU) *reinterpret_cast<uint4*>(Cp16 + ci) = make_uint4(pp[0], pp[1], pp[2], pp[3]);
-        if (Cb && live) {
+        if (has_cp16 && live && act == PAA_ACT_GELU) *reinterpret_cast<uint4*>(Cp16 + ci) = make_uint4(pp[0], pp[1], pp[2], pp[3]);
+        if (has_cb && live) {
             const unsigned cb = cob + (unsigned)dm * ldcb;
             *reinterpret_cast<uint4*>(Cb + cb) = make_uint4(hp[0], hp[1], hp[2], hp[3]);
-            if (Cbl) *reinterpret_cast<uint4*>(Cbl + cb) = make_uint4(lp[0], lp[1], lp[2], lp[3]);
+            if (has_cbl) *reinterpret_cast<uint4*>(Cbl + cb) = make_uint4(lp[0], lp[1], lp[2], lp[3]);
         }
     }
 }

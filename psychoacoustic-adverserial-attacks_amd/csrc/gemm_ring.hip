@@ -367,7 +367,9 @@ namespace paa {
 
 int ring_tile_rows(int cfg) { return ((cfg >= 7 && cfg <= 13) || cfg == 18 || cfg == 19 || cfg == 22 || cfg == 23) ? 192 : 256; }
 int ring_tile_cols(int cfg) { return (cfg == 4 || (cfg >= 6 && cfg <= 13)) ? 128 : 256; }
-bool ring_cfg_ok(int cfg, const paa_gemm_desc& d) {
+// forced (gemm.hip: a configuration asked for through paa_gemm_config): the separate-ring kernels from three K slabs (one per slot of
+// the A ring) upwards; the automatic selection keeps its floor of four
+bool ring_cfg_ok(int cfg, const paa_gemm_desc& d, bool forced) {
     if (cfg < 2 || cfg > 23 || cfg == 13) return false;       // 20..23: gemm_ring2.hip (separate operand rings)
 #ifdef PAA_EXPERIMENTS
     // 9 / 10 are timing probes with WRONG results (MF16): only reachable when the measurement script asks for them
@@ -379,7 +381,7 @@ bool ring_cfg_ok(int cfg, const paa_gemm_desc& d) {
     const bool split = cfg == 4 || cfg == 6 || cfg == 7 || cfg == 9 || cfg == 11 || cfg == 16 || cfg == 17 || cfg == 18 || cfg == 20 || cfg == 22;
     if (split != (d.precision != 0)) return false;
     const int bk = (cfg == 2 || cfg == 8 || cfg == 10 || cfg == 14 || cfg == 19 || cfg == 21 || cfg == 23) ? 64 : cfg == 11 ? 16 : 32;
-    return d.K % bk == 0 && d.K >= 4 * bk;
+    return d.K % bk == 0 && d.K >= ((forced && cfg >= 20) ? 3 : 4) * bk;
 }
 
 }  // namespace paa

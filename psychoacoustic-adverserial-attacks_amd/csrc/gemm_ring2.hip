@@ -14,8 +14,9 @@
 // results are bit-identical to it.  Measured (profiles/r2_gemm_ab_sq.txt): +0..5 % per product in isolation, -3.6 % on the
 // whole fp32-parity step.  Tried on top without effect: starting the workgroups of an XCD in four phases a quarter tile
 // apart, so that their epilogues' store bursts do not coincide (every kernel just got slower by the added delay); epilogues
-// specialised at compile time for the hot descriptor classes (GELU forward, GELU' backward, f32 result + residual): the first two
-// tie the run-time epilogue, the third is 8..16 % SLOWER per product — the epilogue's cost is not its instruction count.
+// specialised at compile time for the hot descriptor classes as hand-written COPIES (GELU forward, GELU' backward, f32 result +
+// residual: the first two tied the run-time epilogue, the third was 8..16 % slower per product).  The epilogue KINDS below (EPI,
+// gemm_dev.h) are the same body behind constant conditions instead; DESIGN.md section 9 holds their resource table and measurements.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -70,7 +71,8 @@ __device__ long long g_r2_stamp[8 * 16 * 6];          // [wave][tile < 16][slabs
 // AIL (split mode only): likewise the A operand from paa_gemm_desc.A_il — the activations' planes interleaved per 32-element K group by
 // their producer (Cb_il of the GEMM epilogues, Bf::il of the element-wise kernels) — so that a K slab of an A row, the operand that
 // streams from HBM, is one 128-byte line too; its slots take the same 128-byte-row layout.
-template <int BM, int BN, int BK, int PREC, int WR, int WC, bool BIL = false, bool AIL = false>
+// EPI: the epilogue kind (gemm_dev.h) — appended LAST: tools/pmc_summary.py::variant_of reads the first four parameters of the kernel name.
+template <int BM, int BN, int BK, int PREC, int WR, int WC, bool BIL = false, bool AIL = false, typename EPI = EpiGeneric>
 __global__ __launch_bounds__(WR * WC * 64, 2) void k_gemm_ring2(GemmArgs g) {
     constexpr int NW = WR * WC;
     constexpr int NPL = PREC ? 2 : 1;
@@ -374,7 +376,7 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void k_gemm_ring2(GemmArgs g) {
 #ifdef PAA_R2_STAMP
         const long long st_t1 = R2_NOW();
 #endif
-        epilogue_vec<MI, true>(d, acc, cur.m0 + wr * (BM / WR), cur.n0 + wc * (BN / WC), cur.z1, cur.z2, lane);
+        epilogue_vec<MI, true, EPI>(d, acc, cur.m0 + wr * (BM / WR), cur.n0 + wc * (BN / WC), cur.z1, cur.z2, lane);
 #ifdef PAA_R2_STAMP
         if (blockIdx.x == 0 && lane == 0 && st_tile < 16) {
             long long* o = g_r2_stamp + (wave * 16 + st_tile) * 6;
@@ -385,24 +387,52 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void k_gemm_ring2(GemmArgs g) {
     }
 }
 
-template <int BM, int BN, int BK, int PREC, int WR, int WC, bool BIL, bool AIL>
+template <int BM, int BN, int BK, int PREC, int WR, int WC, bool BIL, bool AIL, typename EPI = EpiGeneric>
 void launch_ring2_il(const GemmArgs& g, hipStream_t st) {
-    static const int per_cu = blocks_per_cu(k_gemm_ring2<BM, BN, BK, PREC, WR, WC, BIL, AIL>, WR * WC * 64);
+    static const int per_cu = blocks_per_cu(k_gemm_ring2<BM, BN, BK, PREC, WR, WC, BIL, AIL, EPI>, WR * WC * 64);
     const int resident = per_cu * device_cus();
     const int total = g.tiles_m * g.tiles_n * g.d.batch;
     const int blocks = resident > 0 ? std::min(total, resident) : total;
-    hipLaunchKernelGGL((k_gemm_ring2<BM, BN, BK, PREC, WR, WC, BIL, AIL>), dim3(blocks), dim3(WR * WC * 64), 0, st, g);
+    hipLaunchKernelGGL((k_gemm_ring2<BM, BN, BK, PREC, WR, WC, BIL, AIL, EPI>), dim3(blocks), dim3(WR * WC * 64), 0, st, g);
+}
+// Split mode with interleaved weights (what the model's fp32-parity products run): the epilogue kind gemm.hip's classifier found picks
+// the instantiation.  Only what the automatic selection reaches at the model's shapes is held: both GELU kinds on both tiles (FFN up /
+// FFN-down dgrad at N = 3072 and the conv stack take 256 x 256 or 192 x 256 by the round count), the f32-result and plane kinds on the
+// 192-row tile (N = 768 / 2304).  Every other (tile, kind) pair runs the generic epilogue.
+// SHIPPED: GELU_FWD (FFN up: -0.15 .. -0.46 ms on the step, in-process A/Bs on two devices).  The other kinds shorten their epilogues too but
+// their instantiations run a LONGER K loop (stamps: 4550 -> 5480 cycles per slab for GELU_GRAD, 3650 -> 4620 for RESID), the step loses:
+// measured and rejected, held by -DPAA_EXPERIMENTS builds only, like the other rejected kernels.
+template <int BM, int BN, int BK, int WR, int WC, bool AIL>
+void launch_ring2_kind(const GemmArgs& g, hipStream_t st) {
+    if (g.kind == EPK_GELU_FWD) { launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluFwd>(g, st); return; }
+#ifdef PAA_EXPERIMENTS
+    switch (g.kind) {
+        case EPK_GELU_GRAD: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluGrad>(g, st); return;
+        case EPK_GELU_GRAD_LA2: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluGradAhead<2>>(g, st); return;
+        case EPK_GELU_GRAD_LA4: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluGradAhead<4>>(g, st); return;
+        default: break;
+    }
+    if constexpr (BM == 192) {
+        switch (g.kind) {
+            case EPK_RESID: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiResid>(g, st); return;
+            case EPK_RESID_LN: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiResidLn>(g, st); return;
+            case EPK_PLANES: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiPlanes>(g, st); return;
+            default: break;
+        }
+    }
+#endif
+    launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL>(g, st);
 }
 template <int BM, int BN, int BK, int PREC, int WR, int WC>
 void launch_ring2(const GemmArgs& g, hipStream_t st) {
     if constexpr (PREC == 1) {
         const bool bil = g.d.B_il && g.d.b_s1 == 0 && g.d.b_s2 == 0 && !gemm_env_no_bil();
         if (g.d.A_il) {         // interleaved activations (gemm.h, A_il)
-            if (bil) launch_ring2_il<BM, BN, BK, PREC, WR, WC, true, true>(g, st);
+            if (bil) launch_ring2_kind<BM, BN, BK, WR, WC, true>(g, st);
             else launch_ring2_il<BM, BN, BK, PREC, WR, WC, false, true>(g, st);
             return;
         }
-        if (bil) { launch_ring2_il<BM, BN, BK, PREC, WR, WC, true, false>(g, st); return; }
+        if (bil) { launch_ring2_kind<BM, BN, BK, WR, WC, false>(g, st); return; }
     }
     launch_ring2_il<BM, BN, BK, PREC, WR, WC, false, false>(g, st);
 }

@@ -30,7 +30,9 @@ SHAPES = [("conv1 fwd gelu", 512000, 512, 1536, 1024, "gelu"), ("conv1 fwd gelu 
           ("dqkv (wqkv_t) resid", 16000, 768, 2304, None, "res"), ("outproj resid", 16000, 768, 768, None, "res")]
 
 
-def build(M, N, K, lda, ep, prec, kg=0):
+def build(M, N, K, lda, ep, prec, kg=0, model=False):
+    """model: the epilogue fields as csrc/model.hip sets them in fp32-parity mode (alpha 1, interleaved weight / activation planes, bias
+    and f32 gate on the GELU products, interleaved planes out of them) — the descriptors gemm.hip classifies into epilogue kinds"""
     alias = lda == 0              # every A / B row aliases row 0: operands always hit in cache (memory-system probe)
     lda = K if (lda is None or alias) else lda
     def rnd16(n, scale=1.0):          # random bf16 bit patterns of N(0, scale^2) values (full-range mantissas and signs)
@@ -50,6 +52,40 @@ def build(M, N, K, lda, ep, prec, kg=0):
     d.k_group = kg
     keep = [A, B, Al, Bl, aux, aux16]
     outs = {}
+    if model:
+        assert prec == 1 and not alias
+        d.alpha = 1.0
+        Bil = torch.stack([B.view(N, K // 32, 32), Bl.view(N, K // 32, 32)], dim=2).reshape(-1).contiguous()
+        Ail = torch.stack([A.view(-1, 32), Al.view(-1, 32)], dim=1).reshape(-1).contiguous()
+        bias = torch.randn(N, device="cuda")
+        keep += [Bil, Ail, bias]
+        d.B_il, d.A_il = Bil.data_ptr(), Ail.data_ptr()
+        if ep in ("gelu", "gg"):
+            d.act = 1 if ep == "gelu" else 2
+            d.aux_gate = 1
+            il = torch.zeros(2 * M * N, dtype=torch.int16, device="cuda")
+            outs["cb_il"] = il
+            d.Cb_il = il.data_ptr()
+            if ep == "gelu":
+                d.bias = bias.data_ptr()
+                pre = torch.zeros(M * N, device="cuda")
+                outs["pre"] = pre
+                d.C_pre = pre.data_ptr()
+            else:
+                d.aux, d.ld_aux = aux.data_ptr(), N
+            return d, outs, keep
+        if ep == "bf":
+            d.bias = bias.data_ptr()
+        if ep == "rln":         # out-proj / FFN down of the post-LN encoder: bias + LN(stored x) as the residual (gemm.h res_ln_stats)
+            stats = torch.stack([torch.randn(M, device="cuda") * 0.1, torch.rand(M, device="cuda") + 0.5], dim=1).reshape(-1).contiguous()
+            g, b = torch.randn(N, device="cuda"), torch.randn(N, device="cuda")
+            keep += [stats, g, b]
+            d.bias = bias.data_ptr()
+            d.residual, d.ld_res = aux.data_ptr(), N
+            d.res_ln_stats, d.res_ln_g, d.res_ln_b = stats.data_ptr(), g.data_ptr(), b.data_ptr()
+            outs["c"] = torch.zeros(M * N, device="cuda")
+            d.C = outs["c"].data_ptr()
+            return d, outs, keep
 
     def out(name, dtype):
         t = torch.zeros(M * N, dtype=dtype, device="cuda")

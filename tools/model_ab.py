@@ -6,7 +6,11 @@ device: one model per variant at the headline shape, timed in alternating rounds
 
 Variants: default = the shipped behaviour; no_ail = planar activation planes instead of the interleaved ones (gemm.h A_il / Cb_il;
 read at model creation); no_c0dma = the register-staged conv0 GroupNorm backward instead of the LDS-DMA one (read per launch);
-no_rln = f32 LayerNorm outputs written and read back as residuals instead of LN(x) evaluated in the epilogue (gemm.h res_ln_stats).
+no_rln = f32 LayerNorm outputs written and read back as residuals instead of LN(x) evaluated in the epilogue (gemm.h res_ln_stats);
+no_epik = the generic epilogue in every ring GEMM instead of the compile-time epilogue kinds (gemm_dev.h EPK_*; read per launch);
+default takes the GELU_FWD kind only, as the shipped library does; epik_all = every kind (PAA_EPIK_MASK, a bit set of 1 << EPK_*);
+epik_fwd_rln = GELU_FWD + RESID_LN; epik_la2 / epik_la4 = every kind, the GELU' one with its aux stream 2 / 4 row groups ahead.
+Variants that only change how a result is computed, not the result (no_epik), must leave p bit-identical to the first variant: asserted.
 """
 import json
 import os
@@ -24,8 +28,12 @@ from paa_amd.training_utils import parser
 from paa_amd.training_utils.pgd import PgdStepper
 
 
-VARIANTS = {"default": {}, "no_ail": {"PAA_NO_AIL": "1"}, "no_c0dma": {"PAA_NO_C0DMA": "1"}, "no_rln": {"PAA_NO_RLN": "1"}}
-SWITCHES = ("PAA_NO_AIL", "PAA_NO_C0DMA", "PAA_NO_RLN")
+VARIANTS = {"default": {}, "no_ail": {"PAA_NO_AIL": "1"}, "no_c0dma": {"PAA_NO_C0DMA": "1"}, "no_rln": {"PAA_NO_RLN": "1"},
+            "no_epik": {"PAA_NO_EPIK": "1"}, "epik_all": {"PAA_EPIK_MASK": "255"},
+            "epik_fwd_rln": {"PAA_EPIK_MASK": str((1 << 1) | (1 << 4))},
+            "epik_la2": {"PAA_EPIK_MASK": "255", "PAA_EPIK_AHEAD": "2"}, "epik_la4": {"PAA_EPIK_MASK": "255", "PAA_EPIK_AHEAD": "4"}}
+SWITCHES = ("PAA_NO_AIL", "PAA_NO_C0DMA", "PAA_NO_RLN", "PAA_NO_EPIK", "PAA_EPIK_AHEAD", "PAA_EPIK_MASK")
+BIT_IDENTICAL = ("default", "no_epik", "epik_all", "epik_la2", "epik_la4", "epik_fwd_rln")      # arms that must compute the same bits
 
 
 def set_env(name):
@@ -34,7 +42,7 @@ def set_env(name):
 
 
 def main(names, steps=24, rounds=3):
-    assert _lib.lib().paa_version() == 301, "build the diagnostic library first (see the module docstring)"
+    assert _lib.lib().paa_version() == 351, "build the diagnostic library first (see the module docstring)"
     a, B, L = A.BASE, 32, 160000
     clean = torch.from_numpy(synth.clean_audio(B, L, seed=5)).cuda()
     texts = [("the quick brown fox jumps over a lazy dog and runs " * 4)[:150] for _ in range(B)]
@@ -63,6 +71,9 @@ def main(names, steps=24, rounds=3):
     ref = ps[names[0]]
     print(json.dumps({"ms_per_step": ms, "p_equal_to_first_variant": {n: bool(torch.equal(ps[n], ref)) for n in names},
                       "max_abs_diff_to_first_variant": {n: float((ps[n] - ref).abs().max()) for n in names}}), flush=True)
+    if names[0] in BIT_IDENTICAL:
+        for n in names:
+            assert n not in BIT_IDENTICAL or torch.equal(ps[n], ref), f"{n}: p differs from {names[0]} (max |diff| {float((ps[n] - ref).abs().max()):.3e})"
 
 
 if __name__ == "__main__":
