@@ -47,7 +47,8 @@ typedef struct {
 
 const char* paa_last_error(void);
 /* 350 = this header (340 + the placement entries paa_place_draw, paa_place_rows and paa_place_reduce; the room-response entries
- * paa_rir_draw and paa_rir_apply are later additions that changed nothing else and took no new number); 351 = the same ABI built
+ * paa_rir_draw and paa_rir_apply, and the playback-channel entries paa_chan_draw, paa_drift_apply and paa_noise_add, are later
+ * additions that changed nothing else and took no new number); 351 = the same ABI built
  * with -DPAA_EXPERIMENTS (diagnostic kernels and environment switches compiled in,
  * tools/ only).  Bindings refuse other values. */
 int paa_version(void);
@@ -269,6 +270,42 @@ paa_status paa_rir_draw(uint64_t seed, int32_t* d_counter, int stream_id, int cl
  * |out - exact| <= (K + 64) 2^-24 sum_k |h_k in| + 2^-149. */
 paa_status paa_rir_apply(const float* d_bank, int N, int K, const int32_t* d_index, const float* d_in, float* d_out, int B, int L,
                          int adjoint, void* stream);
+
+/* ---- the playback channel on the placement layer: clock drift and ambient noise (extension) --------------------
+ * Drift: clip b is resampled by r_b = rq_b / 2^32 (unsigned Q32; values outside [2^31, 2^33] are clamped on the device) with a
+ * 16-tap Hann-windowed sinc, T = 8.  The output keeps the length L; samples outside [0, L) are zeros:
+ *   pos_q = i * rq_b (64-bit, exact),  n = pos_q >> 32,  f = (pos_q & 0xffffffff) * 2^-32
+ *   out[b][i] = sum_{t=-T+1..T} w(t - f) * in[b][n + t]                               (adjoint = 0)
+ *   out[b][j] = sum_{i : n_i in [j-T, j+T-1]} w(j - n_i - f_i) * in[b][i]             (adjoint = 1: the exact transpose)
+ *   w(u) = sinc(u) * (1 + cos(pi u / T)) / 2 for |u| < T, else 0 (sinc(0) = 1), in float32 with f rounded to float32
+ * rq = 2^32 is the identity bit for bit.  No band-limiting is done for r > 1: meant for |r - 1| <= 0.1.
+ * Noise: rows[b][i] += sigma_b * z_{b,i},  sigma_b = sqrt(mean_i clean[b][i]^2) * 10^(-snr_b / 20),  z standard normal.
+ * All three entries are asynchronous on the stream, allocate nothing, are capturable and use no atomics: two calls on the same
+ * inputs (and, for the noise, the same counter value) give the same bits.  They are additions to ABI 350.
+ *
+ * paa_chan_draw: Philox4x32-10 as paa_place_draw, the same key, counter (step, clip_base + b, stream_id, 2) — word 3 = 2 keeps
+ * the draw disjoint from placement's (0) and the rooms' (1).  With outputs r0, r1:
+ *   d_rq[b]     = 2^32 + ((((int64) r0 - 2^31) * drift_q32) >> 31)     (integers only, arithmetic shift; within 2^32 +- drift_q32)
+ *   d_snr_db[b] = fmaf((r1 >> 8) * 2^-24, snr_hi_db - snr_lo_db, snr_lo_db)
+ * step = *d_counter; *d_counter = step + 1 on the device, by one thread, after every clip has read it.  One block.  drift_q32 =
+ * round(drift_ppm * 1e-6 * 2^32), computed by the caller.  Null pointers, B < 1, drift_q32 > 2^31, snr_lo_db > snr_hi_db or
+ * either beyond +-1000: PAA_ERR_ARG. */
+paa_status paa_chan_draw(uint64_t seed, int32_t* d_counter, int stream_id, int clip_base, int B, uint32_t drift_q32,
+                         float snr_lo_db, float snr_hi_db, uint64_t* d_rq /* (B) */, float* d_snr_db /* (B) */, void* stream);
+/* d_in (B, L) -> d_out (B, L), WRITTEN; they must not overlap.  Null pointers, B < 1, L < 1 or overlapping buffers: PAA_ERR_ARG
+ * before any launch.  64-bit element offsets; rows need no alignment.  adjoint = 0: one f32 fmaf chain per output, t ascending,
+ *   |out - exact| <= 2^-24 (16 sum_t |w_t in_t| + 8 sum_t |in_t|) + 2^-149
+ * (the chain, and the rounding of the float32 weights).  adjoint = 1: the same float32 weights, exact products summed in f64 in
+ * ascending i and rounded once; every output is owned by one thread. */
+paa_status paa_drift_apply(const uint64_t* d_rq, const float* d_in, float* d_out, int B, int L, int adjoint, void* stream);
+/* In place on d_rows (B, L).  Two launches: d_sigma[b] (a workspace of B floats, and an output) from d_clean (B, L) and
+ * d_snr_db (B), then the add.  The samples: Philox4x32-10 with key (seed & 0xffffffff, (seed >> 32) ^ 0x6E6F6973) — another key
+ * than every draw's — and counter (step, clip_base + b, i >> 2, stream_id); the word pair (r[2p], r[2p+1]), p = (i & 3) >> 1, gives
+ *   u1 = ((r[2p] >> 8) + 1) * 2^-24,  u2 = (r[2p+1] >> 8) * 2^-24,  z = sqrt(-2 ln u1) * (cos(2 pi u2) for even i, sin for odd i).
+ * step = *d_counter, a counter of the noise's own: the first launch advances it (one block, after reading it) and the second
+ * reads it back as *d_counter - 1.  A clip with sigma = 0 keeps its rows' bits.  Null pointers, B < 1 or L < 1: PAA_ERR_ARG. */
+paa_status paa_noise_add(uint64_t seed, int32_t* d_counter, int stream_id, int clip_base, const float* d_clean,
+                         const float* d_snr_db, float* d_sigma /* (B) */, float* d_rows, int B, int L, void* stream);
 
 /* ------------------------------------------------------------------ model context ---------- */
 /* Wav2Vec2ForCTC forward + CTC loss + backward to the waveform (core/loss_helpers.py:12-23 ->

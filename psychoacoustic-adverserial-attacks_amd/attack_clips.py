@@ -235,7 +235,7 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
 
 def main(args) -> int:
     # what per-clip perturbations do not run with, and the refusals of --clip_lengths true: before any launch or collective
-    lengths_mode = modes.check(modes.Modes.of(args), ("place_clips", "rir_clips") + modes.LENGTHS).lengths_on
+    lengths_mode = modes.check(modes.Modes.of(args), ("place_clips", "rir_clips", "chan_range", "chan_clips") + modes.LENGTHS).lengths_on
     modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS, modes.Ctx(search=modes.SearchConfig.of(args)))
     if not torch.cuda.is_available():
         raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")

@@ -12,7 +12,7 @@ import sys
 import torch
 
 from .core import iso
-from .training_utils import build, evaluation, modes, parser, place, rir, save, scoring_helpers, train
+from .training_utils import build, channel, evaluation, modes, parser, place, rir, save, scoring_helpers, train
 
 
 def main(args) -> int:
@@ -27,6 +27,7 @@ def main(args) -> int:
     m = modes.check(modes.Modes.of(args), ("route",), modes.Ctx(world))
     place.check_flags(args)
     rir.check_flags(args)
+    channel.check_flags(args)
     mask_alpha = modes.check(m, modes.LENGTHS).alpha
     build.start_process_group(args, world)
     if world > 1 and rank != 0:
@@ -53,6 +54,7 @@ def main(args) -> int:
     extra = {}          # results.json keys of the masking-threshold loss term: present only when masking_loss_alpha > 0
     place_extra = place.results_extra(args, p.shape[-1])          # and those of placement, present only when it is on
     place_extra.update(rir.results_extra(args))                   # and those of room responses, likewise
+    place_extra.update(channel.results_extra(args))               # and those of the playback channel
     extra.update(place_extra)
     goal = scoring_helpers.Objective(args.attack_mode)      # targeted: perturbed WER down; untargeted: perturbed CTC up
     best_epoch, no_improve, best_eval = -1, 0, goal.worst

@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch
 
 from ..core import loss_helpers
-from . import modes, place, rir
+from . import channel, modes, place, rir
 from .build import batch_lengths
 from .scoring_helpers import Scores
 
@@ -14,22 +14,26 @@ class _PlacedEval:
     """evaluate(perturbed=True) with placement on: every batch sees the perturbation at a drawn placement (Philox stream 1, the
     step counter restarting at 0 in every evaluate call, so every evaluation sees the same placements and epochs compare).  With
     room responses on (training_utils/rir.py) the rows then pass through rooms drawn the same way: every evaluation hears the same
-    rooms; with placement itself off the rows are the perturbation at shift 0 and gain 1."""
+    rooms; with placement itself off the rows are the perturbation at shift 0 and gain 1.  With the playback channel on
+    (training_utils/channel.py) the rows are drifted and noise is added the same way: the draw's and the noise's counters restart
+    at 0 with this object, so every evaluation hears the same channels and the same noise."""
 
     def __init__(self, args, model, pp):
         rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
         place.check(args, int(model.length), pp.numel())
         place.shift_on(args), place.gain_db(args)          # rooms alone still place: these two flags are read before the rooms'
         rir.check(args)
+        channel.check(args)
         self.pp, self.placed = pp, rir.PlacedRows(args, model, pp.numel(), place.STREAM_EVAL, False, rank)
 
-    def rows(self, B):
-        return self.placed.rows(self.pp, B)
+    def rows(self, B, clean=None):
+        return self.placed.rows(self.pp, B, clean)
 
 
-def _pert(pp, B):
-    """The perturbation operand of model.forward for a batch of B clips: the (1, L) row, placed rows, or None."""
-    return pp.rows(B) if isinstance(pp, _PlacedEval) else pp
+def _pert(pp, B, clean=None):
+    """The perturbation operand of model.forward for a batch of B clips: the (1, L) row, placed rows, or None.  ``clean``: the
+    batch itself, whose level scales the channel's noise."""
+    return pp.rows(B, clean) if isinstance(pp, _PlacedEval) else pp
 
 
 def _set_lengths(model, lengths, B):
@@ -62,7 +66,7 @@ def _evaluate_device(args, eval_data_loader, pp, model, processor, canon, length
             data = data.to(args.device, torch.float32).contiguous()
             labels = loss_helpers.make_labels(target_texts, processor, args, len(data))
             frames = _set_lengths(model, lengths, len(data))
-            r = model.forward(data, _pert(pp, len(data)), labels, clamp=False)
+            r = model.forward(data, _pert(pp, len(data), data), labels, clamp=False)
             st[ST_LOSS].copy_(r["loss"])
             refs = loss_helpers.encode_refs(target_texts)
             if refs is None:
@@ -97,7 +101,7 @@ def evaluate(args, eval_data_loader, p, model, processor, wer_metric, perturbed=
     pp = None
     if perturbed and isinstance(p, torch.Tensor):
         pp = p.detach().to(model.device, torch.float32).reshape(1, -1).contiguous()
-        if m.place_on or m.rir_on:
+        if m.place_on or m.rir_on or m.chan_on:
             pp = _PlacedEval(args, model, pp)
     if not lengths_mode and model.lengths_on:
         model.set_lengths(None)                      # padded means padded, whatever an earlier caller left behind
@@ -115,7 +119,7 @@ def evaluate(args, eval_data_loader, p, model, processor, wer_metric, perturbed=
         data = data.to(args.device, torch.float32).contiguous()
         labels = loss_helpers.make_labels(target_texts, processor, args, len(data))
         frames = _set_lengths(model, lengths, len(data))
-        r = model.forward(data, _pert(pp, len(data)), labels, clamp=False)
+        r = model.forward(data, _pert(pp, len(data), data), labels, clamp=False)
         ctc_scores.append(float(r["loss"].item()))
         pred_texts, ref_texts = loss_helpers.wer_texts(r["logits"], target_texts, processor, frames, blank)
         e, w = loss_helpers.wer_counts(pred_texts, ref_texts)

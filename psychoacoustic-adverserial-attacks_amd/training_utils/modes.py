@@ -8,6 +8,29 @@ from collections import namedtuple
 from dataclasses import dataclass, replace  # noqa: F401  (replace: how a caller forces a mode on)
 
 GAIN_DB_MAX = 20.0
+DRIFT_PPM_MAX = 100000.0
+NOISE_SNR_MIN, NOISE_SNR_MAX = -20.0, 100.0
+
+
+def _pair(v):
+    """--noise_snr_db as a tuple (of floats where they are numbers); None stays None; anything else is kept for "chan_range"."""
+    if v is None:
+        return None
+    try:
+        return tuple(float(x) if isinstance(x, (int, float, str)) else x for x in v)
+    except (TypeError, ValueError):
+        return (v,)
+
+
+def _chan_bad(m):
+    """None, or the first channel flag out of range."""
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
+    if not (num(m.drift_ppm) and 0.0 <= m.drift_ppm <= DRIFT_PPM_MAX):
+        return f"drift_ppm must be in [0, {DRIFT_PPM_MAX:g}], got {m.drift_ppm}"
+    s = m.noise_snr
+    if s is not None and not (len(s) == 2 and num(s[0]) and num(s[1]) and NOISE_SNR_MIN <= s[0] <= s[1] <= NOISE_SNR_MAX):
+        return f"noise_snr_db must be LO HI with {NOISE_SNR_MIN:g} <= LO <= HI <= {NOISE_SNR_MAX:g} dB, got {list(s)}"
+    return None
 
 
 @dataclass(frozen=True)
@@ -22,6 +45,8 @@ class Modes:
     lengths_on: bool               # --clip_lengths true
     device_wer: bool
     optimizer_type: str
+    drift_ppm: float = 0.0         # --drift_ppm
+    noise_snr: tuple = None        # --noise_snr_db (LO, HI), or None
     search_on: bool = False        # --bound_search other than "off" (attack_clips only)
 
     @classmethod
@@ -34,10 +59,15 @@ class Modes:
         on = get("perturbation_seconds", None) is not None or shift == "random" or (isinstance(gain, float) and gain > 0)
         return cls(norms, "masking" in norms, alpha, on, shift, gain, str(get("rir_bank", "none")) != "none",
                    str(get("clip_lengths", "padded")) == "true", bool(get("device_wer", False)), get("optimizer_type", None),
-                   str(get("bound_search", "off")) != "off")
+                   drift_ppm=_num(get("drift_ppm", 0.0) or 0.0), noise_snr=_pair(get("noise_snr_db", None)),
+                   search_on=str(get("bound_search", "off")) != "off")
 
+    drift_on = property(lambda m: isinstance(m.drift_ppm, float) and m.drift_ppm > 0)
+    noise_on = property(lambda m: m.noise_snr is not None)
+    chan_on = property(lambda m: m.drift_on or m.noise_on)        # the playback channel: clock drift and / or ambient noise
     shift_on = property(lambda m: m.place_shift == "random")
     masking = property(lambda m: m.masking_norm or m.alpha > 0)      # either pairs delta's frames with the clean clip's
+    chan_why = property(lambda m: _chan_bad(m))
 
 
 SIZED_NORMS = ("l2", "linf", "snr", "tv", "fletcher_munson", "max_phon")      # the norms a bound scale tightens (min_max_freqs has no size)
@@ -106,12 +136,20 @@ RULES = {
                         "room responses (rir_bank) are not implemented with the masking norm or masking_loss_alpha > 0" + _PAIRS),
     "rir_eager": Rule("rir_on", lambda m, c: c.eager_adam, NIE, "room responses (rir_bank) need" + _DEVICE_STEP),
     "rir_clips": Rule("rir_on", lambda m, c: True, NIE, "--rir_bank applies to " + _UNIVERSAL + "room responses yet"),
+    # the playback channel: clock drift and ambient noise
+    "chan_range": Rule(None, lambda m, c: _chan_bad(m) is not None, ValueError, "{m.chan_why}"),
+    "chan_masking": Rule("chan_on", lambda m, c: m.masking, NIE, "the playback channel (drift_ppm / noise_snr_db) is not "
+                         "implemented with the masking norm or masking_loss_alpha > 0" + _PAIRS),
+    "chan_eager": Rule("chan_on", lambda m, c: c.eager_adam, NIE, "the playback channel (drift_ppm / noise_snr_db) needs" + _DEVICE_STEP),
+    "chan_clips": Rule("chan_on", lambda m, c: True, NIE,
+                       "--drift_ppm / --noise_snr_db apply to " + _UNIVERSAL + "playback channel yet"),
     # true clip lengths: each of these needs a design of its own before it may meet them
     "len_masking": Rule("lengths_on", lambda m, c: m.masking_norm, ValueError, _NO_LEN + "--norm_type masking"),
     "len_alpha": Rule("lengths_on", lambda m, c: m.alpha > 0, ValueError, _NO_LEN + "--masking_loss_alpha > 0"),
     "len_place": Rule("lengths_on", lambda m, c: m.place_on, ValueError,
                       _NO_LEN + "placement (--perturbation_seconds, --place_shift, --place_gain_db)"),
     "len_rir": Rule("lengths_on", lambda m, c: m.rir_on, ValueError, _NO_LEN + "--rir_bank"),
+    "len_chan": Rule("lengths_on", lambda m, c: m.chan_on, ValueError, _NO_LEN + "--drift_ppm / --noise_snr_db"),
     "len_eager": Rule("lengths_on", lambda m, c: c.eager_adam, NIE, "--clip_lengths true needs" + _DEVICE_STEP),
     # per-clip bound search
     "search_range": Rule("search_on", lambda m, c: c.search is None or c.search.bad() is not None, ValueError,
@@ -127,7 +165,9 @@ RULES = {
 PLACE_FLAGS = ("shift_range", "gain_range", "place_masking")
 PLACE = PLACE_FLAGS + ("place_snr_tv", "place_eager")
 ROOMS = ("rir_masking", "rir_eager")
-LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir")
+CHANNEL_FLAGS = ("chan_range", "chan_masking")
+CHANNEL = CHANNEL_FLAGS + ("chan_eager",)
+LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir", "len_chan")
 SEARCH_FLAGS = ("search_range", "search_masking", "search_no_size")       # known from the flags alone
 SEARCH = SEARCH_FLAGS + ("search_route",)                                  # ... and once the vocabulary and the references are known
 

@@ -112,4 +112,12 @@ def create_arg_parser():
     parser.add_argument('--rir_drr_db', type=_ranged("rir_drr_db", -40.0, 60.0, float), default=6.0,
                         help='direct-to-reverberant energy ratio of a synthetic bank in dB')
     parser.add_argument('--rir_seed', type=int, default=None, help='seed of the synthetic bank (default: --seed)')
+    # the playback channel on the placement layer (extension); the defaults leave the step as it is.  Both draw
+    # under --place_seed / --seed, as the rooms do
+    parser.add_argument('--drift_ppm', type=_ranged("drift_ppm", 0.0, 100000.0, float), default=0.0,
+                        help='P in [0, 100000]: every clip of every step hears the perturbation resampled by a clock ratio uniform '
+                             'in 1 +- P * 1e-6 (16-tap windowed sinc; no band-limiting, meant for P <= 100000); 0 = off')
+    parser.add_argument('--noise_snr_db', type=_ranged("noise_snr_db", -20.0, 100.0, float), nargs=2, default=None,
+                        metavar=("LO", "HI"), help='ambient noise: white Gaussian noise is added to every clip of every step at an '
+                        'SNR uniform in [LO, HI] dB below the clean clip; absent = off')
     return parser

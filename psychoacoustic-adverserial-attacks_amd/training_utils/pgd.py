@@ -21,6 +21,10 @@
     room responses (``rir_bank``; universal    paa_rir_draw (not after ``set_rooms``), paa_rir_apply      between paa_place_rows and the forward
     only; runs the placement launches too,     paa_rir_apply (adjoint)                                    between the backward pass and
     at shift 0 / gain 1 when placement is off)                                                            paa_place_reduce
+    playback channel (``drift_ppm`` /          paa_chan_draw (not after ``set_channel``),                 between paa_place_rows and the rooms
+    ``noise_snr_db``; universal only; runs     paa_drift_apply (drift only)
+    the placement launches too, likewise)      paa_noise_add (noise only: two launches)                   last before the forward pass
+                                               paa_drift_apply (adjoint; drift only)                      right before paa_place_reduce
 
     true clip lengths (``lengths=`` /          inside paa_model_fwd_bwd{,_rows}: frame counts, zeroed      DESIGN.md §6h
     ``set_lengths``)                           frames, masked compose / attention / CTC
@@ -30,11 +34,11 @@
     per-clip step only; needs device WER)                                                                 the update
                                                paa_project_rows_scaled                                    in place of paa_project_rows
 
-A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off, lengths off and no bound
-search are the plain step, bit for bit.
+A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off, the channel off, lengths off
+and no bound search are the plain step, bit for bit.
 
 Which modes may run together, and which refusal wins when several apply, is decided in one table: training_utils/modes.py.  What
-a mode means is written where it is built: place.py, rir.py (§6g), ``set_lengths`` and PaaModel.set_lengths (§6h).
+a mode means is written where it is built: place.py, rir.py (§6g), channel.py (§6k), ``set_lengths`` and PaaModel.set_lengths (§6h).
 
 The packed vector is ``[ grad (Lp) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, masking loss, 0 ]`` in
 float32; the 8 stat slots are defined HERE (ST_*) and documented in include/paa_hip.h (paa_model_fwd_bwd, d_stats).  Every rank
@@ -57,7 +61,7 @@ import contextlib
 import torch
 
 from .. import _lib, runtime
-from . import modes, place, rir
+from . import channel, modes, place, rir
 from .build import batch_lengths, unpack_batch  # noqa: F401  (re-exported)
 from .modes import Ctx, Modes, replace
 
@@ -428,8 +432,9 @@ class PgdStepper(_StepperCore):
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.world = torch.distributed.get_world_size(group)
         rir.check(args)                                                          # refusals: before any launch or collective
+        channel.check(args)
         m = Modes.of(args)
-        self.place_on, self.rir_on, self.Lp = m.place_on, m.rir_on, L
+        self.place_on, self.rir_on, self.chan_on, self.Lp = m.place_on, m.rir_on, m.chan_on, L
         if m.place_on:
             self.Lp = int(p_length) if p_length is not None else place.perturbation_length(args, L)
         elif p_length is not None and int(p_length) != L:
@@ -444,7 +449,7 @@ class PgdStepper(_StepperCore):
         self.packed = torch.zeros(self.Lp + N_STATS, dtype=torch.float32, device=self.dev)
         self.grad = self.packed[: self.Lp].view(1, self.Lp)
         self.stats = self.packed[self.Lp:]
-        if self.place_on or self.rir_on:
+        if self.place_on or self.rir_on or self.chan_on:
             rank = torch.distributed.get_rank(self.group) if self.world > 1 else 0
             self.placed = rir.PlacedRows(args, model, self.Lp, place.STREAM_TRAIN, True, rank, L)
             pl = self.placer = self.placed.placer
@@ -452,6 +457,8 @@ class PgdStepper(_StepperCore):
         if self.rir_on:
             rv = self.reverb = self.placed.reverb
             self.room, self.rir_counter, self.wet_rows = rv.index, rv.counter, rv.rows
+        if self.chan_on:
+            self.chan = self.placed.chan
 
     def _check_adam_shape(self):
         if self.adam_p.numel() != self.Lp:
@@ -472,6 +479,21 @@ class PgdStepper(_StepperCore):
         """Device step counter of the next room draw (resume, tests)."""
         self._reverb().set_step(n)
 
+    def _chan(self):
+        if not self.chan_on:
+            raise RuntimeError("the stepper was built with the playback channel off (drift_ppm / noise_snr_db)")
+        return self.chan
+
+    def set_channel(self, ratio, snr_db=None):
+        """Explicit per-clip clock ratios (and noise SNRs in dB) instead of the draw, from the next step on (stream-ordered copy
+        into the fixed buffers); ``set_channel(None)`` returns to drawing.  The noise samples keep their own counter and stay
+        fresh.  A captured graph keeps the form it was captured with."""
+        self._chan().set_channel(ratio, snr_db)
+
+    def set_chan_step(self, n: int):
+        """Device step counters of the next channel draw and the next noise (resume, tests)."""
+        self._chan().set_step(n)
+
     def _placer(self):
         if not self.place_on:
             raise RuntimeError("the stepper was built with placement off (perturbation_seconds / place_shift / place_gain_db)")
@@ -490,16 +512,19 @@ class PgdStepper(_StepperCore):
     def clip_base(self):
         """Global id of this rank's first clip in the draws' counters (default rank * model.max_batch); assignable per step.  A
         captured graph holds the value it was captured with."""
-        return (self.placer if self.rir_on else self._placer()).clip_base
+        return (self.placer if self.rir_on or self.chan_on else self._placer()).clip_base
 
     @clip_base.setter
     def clip_base(self, v):
-        (self.placer if self.rir_on else self._placer()).clip_base = int(v)
+        (self.placer if self.rir_on or self.chan_on else self._placer()).clip_base = int(v)
         if self.rir_on:
             self.reverb.clip_base = int(v)
+        if self.chan_on:
+            self.chan.clip_base = int(v)
 
     def _replay_state(self):
-        return super()._replay_state() + ([self.counter] if self.place_on else []) + ([self.rir_counter] if self.rir_on else [])
+        return super()._replay_state() + ([self.counter] if self.place_on else []) + ([self.rir_counter] if self.rir_on else []) \
+            + ([self.chan.counter, self.chan.noise_counter] if self.chan_on else [])
 
     # ---- bookkeeping carried by the packed vector -------------------------------------------------------------
     def set_wer_counts(self, errors: float, ref_words: float):
@@ -513,10 +538,10 @@ class PgdStepper(_StepperCore):
         out = {"grad": self.grad, "stats": self.stats}
         if logits_out is not None:
             out["logits"] = logits_out
-        placed = self.place_on or self.rir_on          # rir.PlacedRows: one gradient row per clip, then their adjoint into self.grad
+        placed = self.place_on or self.rir_on or self.chan_on      # rir.PlacedRows: one gradient row per clip, then their adjoint into self.grad
         if placed:
             out["grad"] = self.grad_rows[:B]
-        r = self.model.fwd_bwd(clean, self.placed.rows(p, B) if placed else p, labels, self.direction, want_grad=True,
+        r = self.model.fwd_bwd(clean, self.placed.rows(p, B, clean) if placed else p, labels, self.direction, want_grad=True,
                                want_logits=want_logits, out=out)
         if placed:
             self.placed.reduce(B, self.grad)

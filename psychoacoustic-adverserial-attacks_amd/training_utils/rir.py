@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _lib, synth
-from . import modes, place
+from . import channel, modes, place
 from .modes import Ctx, Modes
 
 MAX_TAPS = 16384                      # PAA_RIR_MAX_TAPS of include/paa_hip.h
@@ -221,9 +221,11 @@ class Reverb:
 
 
 class PlacedRows:
-    """The rows the model sees at one site (the training step, or one evaluation) with placement and / or room responses on: a
-    ``place.Placer`` and, with room responses on, a ``Reverb``, both keyed by ``draw_seed`` and the global clip id ``rank *
-    max_batch + b``.  With placement off the rows are placed at explicit zero shifts and unit gains, and nothing is drawn."""
+    """The rows the model sees at one site (the training step, or one evaluation) with placement, room responses and / or the
+    playback channel (channel.py) on: a ``place.Placer``, with room responses on a ``Reverb``, with the channel on a
+    ``channel.Channel``, all keyed by ``draw_seed`` and the global clip id ``rank * max_batch + b``.  The chain is place -> drift ->
+    rooms -> + noise: drift belongs to the emitter, the room to the path, noise to the microphone.  With placement off the rows are
+    placed at explicit zero shifts and unit gains, and nothing is drawn for them."""
 
     def __init__(self, args, model, Lp: int, stream_id: int, with_grad: bool = True, rank: int = 0, L=None):
         m, nb, L, seed = Modes.of(args), int(model.max_batch), int(model.length if L is None else L), draw_seed(args)
@@ -233,23 +235,40 @@ class PlacedRows:
             self.placer.set_placement([0] * nb)
         self.reverb = Reverb(model.device, bank_of(args), nb, L, seed, stream_id, clip_base=rank * nb,
                              with_grad=with_grad) if m.rir_on else None
+        self.chan = channel.of_args(args, model, seed, stream_id, with_grad, rank, L)
 
-    def rows(self, p, B: int):
-        """draw -> rows [-> room draw -> rows through the rooms]; an explicit placement / explicit rooms skip their draw."""
-        pl, rv = self.placer, self.reverb
+    def rows(self, p, B: int, clean=None):
+        """draw -> rows [-> channel draw -> drift] [-> room draw -> rows through the rooms] [-> + noise]; an explicit placement /
+        explicit channels / explicit rooms skip their draw.  ``clean`` (B, L): the clean batch, whose level scales the noise."""
+        pl, rv, ch = self.placer, self.reverb, self.chan
         if not pl.explicit:
             pl.draw(B)
-        rows = pl.place(p, B)
+        rows, buf = pl.place(p, B), pl.rows          # buf: the whole buffer the last launch wrote, rows its first B
+        if ch is not None:
+            if not ch.explicit:
+                ch.draw(B)
+            if ch.drift_on:
+                rows, buf = ch.apply(buf, B), ch.rows
         if rv is not None:
             if not rv.explicit:
                 rv.draw(B)
-            rows = rv.apply(pl.rows, B)
+            rows, buf = rv.apply(buf, B), rv.rows
+        if ch is not None and ch.noise_on:
+            if clean is None:
+                raise ValueError("ambient noise (noise_snr_db) needs the clean batch: rows(p, B, clean)")
+            ch.add_noise(buf, clean, B)
         return rows
 
     def reduce(self, B: int, grad):
-        """The model's gradient rows (``placer.grad_rows``) [-> the rooms' adjoint] -> adjoint gather-sum into ``grad``."""
-        pl, rv = self.placer, self.reverb
-        pl.reduce(B, grad, rv.adjoint(pl.grad_rows, B) if rv is not None else None)
+        """The model's gradient rows (``placer.grad_rows``) [-> the rooms' adjoint] [-> the drift's transpose] -> adjoint gather-sum
+        into ``grad``.  Noise does not depend on the perturbation: the backward pass does not see it."""
+        pl, rv, ch = self.placer, self.reverb, self.chan
+        g = pl.grad_rows
+        if rv is not None:
+            g = rv.adjoint(g, B)
+        if ch is not None and ch.drift_on:
+            g = ch.adjoint(g, B)
+        pl.reduce(B, grad, None if g is pl.grad_rows else g)
 
 
 def reverberate(rows, bank, index):

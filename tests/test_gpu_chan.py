@@ -1,0 +1,552 @@
+"""-m gpu: the playback channel on the placement layer — paa_drift_apply in both directions, paa_chan_draw and
+paa_noise_add against tests/chan_ref.py, the step with the mode on against the oracle, the draws inside captured graphs, the mode
+off, Adam, two ranks and evaluation.
+
+Bounds.  The drift forward is one f32 fmaf chain of 16 terms with float32 weights: per output
+|dev - ref64| <= 2^-24 (16 sum_t |w_t x_t| + 8 sum_t |x_t|) + 2^-149 (chan_ref.bound: the chain, and 8 units for the weights'
+own rounding — 1.64 measured on the host with correctly rounded sinpi / cospi, the rest is margin for the device's).  The adjoint
+holds the same bound with the roles swapped.  sigma: 2^-22 relative.  The noise samples: 4 x the error of the same formula in torch
+float32 on the CPU, floor 1 float32 ulp (2^-23) of sigma * radius.  The step bounds are those of
+test_gpu_rir.test_reverberant_step_vs_oracle; the gradient reference is the oracle's autograd gradient with respect to the rows,
+taken back through chan_ref.adjoint64 (the transpose of apply64: tests/test_chan_host.py), rir_ref.adjoint64 and place_ref.reduce64.
+Every kernel output lives between two guard blocks that must survive."""
+import json
+import math
+import os
+import socket
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import chan_ref as CR
+import place_ref as PR
+import rir_ref as RR
+from gpu_util import record_launches, rel_err
+from oracle import pgd as opgd, projections as OP, wav2vec2 as OW
+from oracle.gen_cases import PGD_TEXTS, cli_to_args
+from paa_amd import _lib, arch as A, runtime, synth
+from paa_amd.model import PaaModel
+from paa_amd.training_utils import build, channel, rir
+from paa_amd.training_utils.pgd import PgdStepper
+from test_gpu_place import Guarded
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ONE = 1 << 32
+# 0.9, 1 - 2^-32, 1, 1 + 1e-4, 1.1
+RATIOS = [CR.rq_of(0.9), ONE - 1, ONE, CR.rq_of(1.0 + 1e-4), CR.rq_of(1.1)]
+# (B, L): one output, one window, two blocks and a bit (a block covers 1024 outputs), whole blocks, many blocks at an odd length,
+# a ten-second clip
+DRIFT_SHAPES = [(1, 5), (1, 16), (3, 2085), (2, 4096), (2, 20011), (1, 160000)]
+SEED = 5
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _fresh_projection_contexts():
+    """max_phon contours are loaded into the process-wide projection contexts: drop them for the modules that follow."""
+    yield
+    torch.cuda.synchronize()
+    runtime._PROJ.clear()
+
+
+def _i64(x):
+    return torch.tensor([int(v) for v in x], dtype=torch.int64, device="cuda")
+
+
+def _signal(B, L, tag):
+    return np.stack([synth.normal(synth.key_of(f"{tag}{b}_{L}", 5), L) for b in range(B)]).astype(np.float32)
+
+
+def _drift(rq, x, adjoint):
+    """One paa_drift_apply launch between guard blocks -> the (B, L) output tensor."""
+    B, L = x.shape
+    out = Guarded((B, L))
+    _lib.check(_lib.lib().paa_drift_apply(_lib.ptr(rq), _lib.ptr(x), out.ptr, B, L, adjoint, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    out.check()
+    return out.t
+
+
+def _ratio_sets(B, L):
+    """Every ratio on some row: the list rotated, B rows per launch (the ten-second clip takes the two extremes)."""
+    if L >= 100000:
+        return [[RATIOS[0]], [RATIOS[4]]]
+    return [[RATIOS[(k + b) % 5] for b in range(B)] for k in range(0, 5, B)]
+
+
+# ---- 1. paa_drift_apply, both directions ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("B,L", DRIFT_SHAPES)
+def test_drift_vs_float64(B, L):
+    x_np, g_np = _signal(B, L, "x"), _signal(B, L, "g")
+    for rq in _ratio_sets(B, L):
+        rq_dev = _i64(rq)
+        outs = {}
+        for adjoint, src in ((0, x_np), (1, g_np)):
+            d = torch.from_numpy(src).cuda()
+            a = _drift(rq_dev, d, adjoint)
+            b = _drift(rq_dev, d, adjoint)
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32))                 # two calls: the same bits
+            dev = a.cpu().numpy().astype(np.float64)
+            ref = (CR.adjoint64 if adjoint else CR.apply64)(rq, src)
+            bound = CR.bound(rq, src, bool(adjoint))
+            err = np.abs(dev - ref)
+            print(f"B={B} L={L} rq={rq} adjoint={adjoint}: max err / bound {float((err / bound).max()):.4f}, "
+                  f"max |ref| {np.abs(ref).max():.3g}")
+            assert np.isfinite(dev).all() and np.all(err <= bound), float((err / bound).max())
+            outs[adjoint] = (dev, bound)
+        # <A x, g> = <x, A' g>, in float64 on the device's own outputs, within the sum of the two bounds
+        x64, g64 = x_np.astype(np.float64), g_np.astype(np.float64)
+        lhs, rhs = math.fsum((outs[0][0] * g64).ravel()), math.fsum((x64 * outs[1][0]).ravel())
+        tol = math.fsum((outs[0][1] * np.abs(g64)).ravel()) + math.fsum((np.abs(x64) * outs[1][1]).ravel())
+        print(f"B={B} L={L} rq={rq}: adjointness |lhs - rhs| / tol {abs(lhs - rhs) / tol:.4f}")
+        assert abs(lhs - rhs) <= tol, (lhs, rhs, tol)
+
+
+@pytest.mark.parametrize("L", [5, 2085, 20011])
+def test_unit_ratio_is_the_identity_bit_for_bit(L):
+    B = 2
+    x = torch.from_numpy(_signal(B, L, "id")).cuda()
+    rq = _i64([ONE, ONE])
+    for adjoint in (0, 1):
+        assert torch.equal(_drift(rq, x, adjoint).view(torch.int32), x.view(torch.int32))
+    assert torch.equal(channel.drift(x, [1.0, 1.0]), x) and torch.equal(channel.drift(x, [ONE, ONE], adjoint=True), x)
+
+
+def test_ratios_out_of_range_are_clamped():
+    B, L = 3, 600
+    x_np = _signal(B, L, "cl")
+    rq = [1, 1 << 40, (1 << 33) + 1]
+    got = _drift(_i64(rq), torch.from_numpy(x_np).cuda(), 0).cpu().numpy().astype(np.float64)
+    ref = CR.apply64([1 << 31, 1 << 33, 1 << 33], x_np)
+    assert np.all(np.abs(got - ref) <= CR.bound(rq, x_np))
+    assert np.array_equal(CR.apply64(rq, x_np), ref)
+
+
+def test_chan_refusals_leave_outputs_alone():
+    L_ = _lib.lib()
+    B, L = 2, 600
+    x, rq = torch.zeros(B, L, device="cuda"), _i64([ONE, ONE])
+    out, rqo, snr, sig, counter = Guarded((B, L)), Guarded((2 * B,), torch.int32), Guarded((B,)), Guarded((B,)), Guarded((1,), torch.int32)
+    st, ARG = _lib.stream_ptr(), _lib.PAA_ERR_ARG
+    for adjoint in (0, 1):
+        for B_, L__ in ((0, L), (B, 0)):
+            assert L_.paa_drift_apply(_lib.ptr(rq), _lib.ptr(x), out.ptr, B_, L__, adjoint, st) == ARG
+        for k in range(3):
+            a = [_lib.ptr(rq), _lib.ptr(x), out.ptr]
+            a[k] = None
+            assert L_.paa_drift_apply(a[0], a[1], a[2], B, L, adjoint, st) == ARG
+        assert L_.paa_drift_apply(_lib.ptr(rq), out.ptr, out.ptr, B, L, adjoint, st) == ARG          # in place
+        assert b"overlap" in L_.paa_last_error()
+    half = Guarded((2 * B, L))
+    assert L_.paa_drift_apply(_lib.ptr(rq), half.ptr, _lib.ptr(half.t[1:]), B, L, 1, st) == ARG
+    with pytest.raises(_lib.PaaError, match="overlap"):
+        _lib.check(L_.paa_drift_apply(_lib.ptr(rq), _lib.ptr(half.t[1:]), half.ptr, B, L, 0, st))
+    draw = lambda c, B_, D, lo, hi, r, s: L_.paa_chan_draw(SEED, c, 0, 0, B_, D, lo, hi, r, s, st)
+    assert draw(None, B, 10, 0.0, 1.0, rqo.ptr, snr.ptr) == ARG
+    assert draw(counter.ptr, B, 10, 0.0, 1.0, None, snr.ptr) == ARG
+    assert draw(counter.ptr, B, 10, 0.0, 1.0, rqo.ptr, None) == ARG
+    assert draw(counter.ptr, 0, 10, 0.0, 1.0, rqo.ptr, snr.ptr) == ARG
+    assert draw(counter.ptr, B, (1 << 31) + 1, 0.0, 1.0, rqo.ptr, snr.ptr) == ARG
+    assert draw(counter.ptr, B, 10, 2.0, 1.0, rqo.ptr, snr.ptr) == ARG
+    assert draw(counter.ptr, B, 10, float("nan"), 1.0, rqo.ptr, snr.ptr) == ARG
+    noise = lambda c, cl, s, sg, r, B_, L__: L_.paa_noise_add(SEED, c, 0, 0, cl, s, sg, r, B_, L__, st)
+    ok = [counter.ptr, _lib.ptr(x), snr.ptr, sig.ptr, out.ptr]
+    for k in range(5):
+        a = list(ok)
+        a[k] = None
+        assert noise(*a, B, L) == ARG
+    assert noise(*ok, 0, L) == ARG and noise(*ok, B, 0) == ARG
+    torch.cuda.synchronize()
+    for g in (out, half, rqo, snr, sig, counter):
+        g.check()
+        assert g.untouched()
+
+
+# ---- 2. paa_chan_draw ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B", [1, 3, 300])
+def test_chan_draw(B):
+    base, D, lo, hi = 7, CR.drift_q32(20000.0), 12.5, 30.0
+    counter = Guarded((1,), torch.int32)
+    counter.t.fill_(3)
+    for step in (3, 4):
+        rq, snr = Guarded((2 * B,), torch.int32), Guarded((B,))
+        _lib.check(_lib.lib().paa_chan_draw(SEED, counter.ptr, 0, base, B, D, lo, hi, rq.ptr, snr.ptr, _lib.stream_ptr()))
+        torch.cuda.synchronize()
+        rq.check(), snr.check(), counter.check()
+        want_rq, want_snr = CR.draw(SEED, step, base, B, 0, D, lo, hi)
+        got = rq.t.view(torch.int64).cpu().tolist()
+        assert got == want_rq, step                                          # integers: bit-exact
+        assert all(ONE - D <= q <= ONE + D for q in got) and (B == 1 or len(set(got)) > 1)
+        s = snr.t.cpu().numpy()
+        ulp = np.spacing(np.abs(want_snr).astype(np.float32))
+        assert np.all(np.abs(s.astype(np.float64) - want_snr.astype(np.float64)) <= ulp) and np.all((s >= lo) & (s <= hi))
+        assert int(counter.t.item()) == step + 1                             # one per launch, not one per clip
+    rq0, rq1 = Guarded((2 * B,), torch.int32), Guarded((2 * B,), torch.int32)          # drift off: exactly one; another stream: other draws
+    snr = Guarded((B,))
+    counter.t.zero_()
+    _lib.check(_lib.lib().paa_chan_draw(SEED, counter.ptr, 0, base, B, 0, lo, lo, rq0.ptr, snr.ptr, _lib.stream_ptr()))
+    _lib.check(_lib.lib().paa_chan_draw(SEED, counter.ptr, 1, base, B, D, lo, hi, rq1.ptr, snr.ptr, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    assert rq0.t.view(torch.int64).cpu().tolist() == [ONE] * B
+    assert rq1.t.view(torch.int64).cpu().tolist() == CR.draw(SEED, 1, base, B, 1, D, lo, hi)[0]
+
+
+# ---- 3. paa_noise_add ----------------------------------------------------------------------------------------------------
+def _noise(counter, clean, snr, rows, base=0, stream=0):
+    B, L = rows.shape
+    sigma = Guarded((B,))
+    _lib.check(_lib.lib().paa_noise_add(SEED, counter.ptr, stream, base, _lib.ptr(clean), _lib.ptr(snr), sigma.ptr, _lib.ptr(rows),
+                                        B, L, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    sigma.check(), counter.check()
+    return sigma.t.cpu().numpy()
+
+
+@pytest.mark.parametrize("L", [5, 2085, 20011])
+def test_noise_add_vs_float64(L):
+    B, base, s0 = 3, 11, 6
+    clean_np = _signal(B, L, "cn") * np.float32(0.1)
+    clean_np[1] = 0.0                                                        # a silent clip
+    snr_np = np.array([20.0, 10.0, -3.5], dtype=np.float32)
+    clean, snr = torch.from_numpy(clean_np).cuda(), torch.from_numpy(snr_np).cuda()
+    counter = Guarded((1,), torch.int32)
+    counter.t.fill_(s0)
+    sig64 = CR.sigma64(clean_np, snr_np)
+    outs = []
+    for k, start in enumerate((np.zeros((B, L), dtype=np.float32), _signal(B, L, "r0"))):
+        rows = Guarded((B, L))
+        rows.t.copy_(torch.from_numpy(start))
+        sig = _noise(counter, clean, snr, rows.t, base)
+        rows.check()
+        assert int(counter.t.item()) == s0 + k + 1
+        assert sig[1] == 0.0 and np.all(np.abs(sig - sig64) <= 2.0 ** -22 * sig64)
+        got = rows.t.cpu().numpy()
+        assert np.array_equal(got[1].view(np.int32), start[1].view(np.int32))          # sigma = 0: the rows keep their bits
+        for b in (0, 2):
+            u1, u2 = CR.noise_uniforms(SEED, s0 + k, base + b, 0, L)
+            z64 = CR.noise64(SEED, s0 + k, base + b, 0, L)
+            want = start[b].astype(np.float64) + float(sig[b]) * z64         # the device's own float32 sigma: its error is judged above
+            # the same formula in torch float32 on the CPU
+            t1, t2 = torch.from_numpy(u1.astype(np.float32)), torch.from_numpy(u2.astype(np.float32))
+            rad = torch.sqrt(-2.0 * torch.log(t1))
+            ang = np.float32(2.0 * np.pi) * t2
+            even = torch.from_numpy((np.arange(L) & 1) == 0)
+            t32 = torch.from_numpy(start[b]) + torch.tensor(sig[b]) * (rad * torch.where(even, torch.cos(ang), torch.sin(ang)))
+            e_t = float(np.abs(t32.numpy().astype(np.float64) - want).max())
+            bound = np.maximum(4.0 * e_t, 2.0 ** -23 * float(sig[b]) * rad.numpy().astype(np.float64))
+            err = np.abs(got[b].astype(np.float64) - want)
+            print(f"L={L} call {k} clip {b}: noise max err / bound {float((err / bound).max()):.3f} (torch float32 error {e_t:.2e})")
+            assert np.all(err <= bound), float((err / bound).max())
+        outs.append(got - start)
+    assert not np.array_equal(outs[0][0], outs[1][0])                        # two calls: steps s and s + 1
+
+
+def test_allocating_pair_matches_the_launches():
+    B, L = 2, 2085
+    x = torch.from_numpy(_signal(B, L, "ap")).cuda()
+    y = channel.drift(x, [0.9, 1.1])
+    assert np.all(np.abs(y.cpu().numpy() - CR.apply64([CR.rq_of(0.9), CR.rq_of(1.1)], x.cpu().numpy()))
+                  <= CR.bound([CR.rq_of(0.9), CR.rq_of(1.1)], x.cpu().numpy()))
+    n = channel.add_noise(torch.zeros_like(x), x, [20.0, 30.0], seed=SEED, step=2, stream_id=1, clip_base=4)
+    sig = CR.sigma64(x.cpu().numpy(), [20.0, 30.0])
+    for b in range(B):
+        assert np.allclose(n[b].cpu().numpy(), sig[b] * CR.noise64(SEED, 2, 4 + b, 1, L), rtol=1e-5, atol=1e-6 * sig[b])
+
+
+# ---- 4. the step with the mode on against the oracle ---------------------------------------------------------------------
+#            norm, extra, drift ratios, snr_db, Lp (None: placement off), shifts, gains, rooms
+STEP_CASES = {"drift": ("linf", [], (0.95, 1.0 + 3e-3), None, None, (0, 0), None, None),
+              "noise": ("snr", ["--snr_db", "40"], None, (30.0, 24.0), None, (0, 0), None, None),
+              "all": ("linf", [], (1.08, 0.97), (35.0, 28.0), 8000, (12, 7999), (0.7, 1.3), (0, 2))}
+STEP_N, STEP_K = 3, 600
+
+
+@pytest.mark.parametrize("variant", ["group", "layer"])
+@pytest.mark.parametrize("case", list(STEP_CASES))
+def test_channel_step_vs_oracle(case, variant):
+    norm, extra, ratios, snrs, Lp, shifts, gains, rooms = STEP_CASES[case]
+    a = A.tiny("group", False) if variant == "group" else A.tiny("layer", True)
+    B, L, s0 = 2, 16000, 3
+    args = cli_to_args(norm, extra)
+    args.device, args.sr, args.seed = "cuda", 16000, 5
+    if ratios is not None:
+        args.drift_ppm = 90000.0
+    if snrs is not None:
+        args.noise_snr_db = [20.0, 40.0]
+    if rooms is not None:
+        args.rir_bank, args.rir_count, args.rir_taps = "synthetic", STEP_N, STEP_K
+    if Lp is not None:
+        args.perturbation_seconds = Lp / 16000
+    Lp = L if Lp is None else Lp
+    sdn = A.rule_weights(a)
+    sd = OW.to_torch(sdn)
+    clean = torch.from_numpy(synth.clean_audio(B, L))
+    p0 = torch.from_numpy(synth.perturbation(Lp) * np.float32(1e-3)).view(1, Lp)
+    labels = opgd.make_labels(PGD_TEXTS[:B], args, B)
+    spl = OP.spl_thresh_tensor(args)
+    m = PaaModel(a, sdn, B, L, "fp32")
+    st = PgdStepper(m, args, L, None, build.init_phon_threshold_tensor(args))
+    assert st.chan_on and st.chan.drift_on == (ratios is not None) and st.chan.noise_on == (snrs is not None)
+    assert st.place_on == (case == "all") and st.rir_on == (rooms is not None) and st.Lp == Lp
+    rq = [CR.rq_of(r) for r in ratios] if ratios is not None else [ONE] * B
+    st.set_channel(rq, snrs)
+    st.set_chan_step(s0)
+    if st.place_on:
+        st.set_placement(shifts, gains)
+    if rooms is not None:
+        st.set_rooms(rooms)
+    p = p0.cuda()
+    with record_launches() as names:
+        r = st.step(p, clean.cuda(), labels)
+    torch.cuda.synchronize()
+    assert "paa_chan_draw" not in names and int(st.chan.counter.item()) == s0          # pinned: nothing drawn
+    assert names.count("paa_drift_apply") == (2 if ratios is not None else 0) and names.count("paa_noise_add") == (snrs is not None)
+    g = st.grad.cpu().numpy()[0]
+    g32 = None if gains is None else np.asarray(gains, dtype=np.float32)
+    # the chain place -> drift -> rooms -> + noise in numpy float64
+    rows0 = PR.place(p0.numpy()[0], L, shifts, g32)
+    if case != "noise":          # noise alone is added in place on the placed rows
+        assert torch.equal(st.rows.cpu(), torch.from_numpy(rows0))
+    wet = rows0.astype(np.float64)
+    if ratios is not None:
+        wet = CR.apply64(rq, wet)
+    if rooms is not None:
+        wet = RR.apply64(rir.bank_of(args), rooms, wet)
+    if snrs is not None:
+        assert int(st.chan.noise_counter.item()) == s0 + 1
+        sig = CR.sigma64(clean.numpy(), np.asarray(snrs, dtype=np.float32))
+        wet = wet + np.stack([sig[b] * CR.noise64(5, s0, b, 0, L) for b in range(B)])
+    last = st.wet_rows if rooms is not None else (st.chan.rows if ratios is not None else st.rows)
+    seen = last[:B].cpu().numpy().astype(np.float64)
+    assert np.abs(seen - wet).max() <= 1e-5 * np.abs(wet).max()
+    ref = opgd.pgd_step(sd, a, args, clean, labels, torch.from_numpy(wet.astype(np.float32)), spl)
+    # the oracle's autograd gradient with respect to the rows, back through the transposes (noise: none)
+    grows = ref["grad"].numpy().astype(np.float64)
+    if rooms is not None:
+        grows = RR.adjoint64(rir.bank_of(args), rooms, grows)
+    if ratios is not None:
+        grows = CR.adjoint64(rq, grows)
+    gref = PR.reduce64(grows, shifts, g32, Lp)[0]
+    e_g = rel_err(g, gref)
+    flips = float((np.sign(g) != np.sign(gref)).mean())
+    e_loss = abs(float(r["loss"]) - float(ref["loss"])) / abs(float(ref["loss"]))
+    with torch.no_grad():
+        pexp = OP.perturbation_constraint(p0 + args.lr * torch.from_numpy(g[None]).sign(), clean if norm == "snr" else None, args, spl)
+    e_p = rel_err(p.cpu().numpy()[0], pexp.numpy()[0])
+    print(f"case {case} {variant}: grad rel {e_g:.2e} flips {flips:.2e} loss rel {e_loss:.2e} p' rel {e_p:.2e}")
+    assert e_g < 5e-3 and flips < 5e-3 and e_loss < 2e-4 and e_p < 5e-5, (e_g, flips, e_loss, e_p)
+
+
+# ---- 5. drawing inside captured graphs; pinned channels ------------------------------------------------------------------
+def _case(B=2, L=8000, **kw):
+    args = cli_to_args("linf", ["--linf_size", "0.01"])
+    args.device, args.sr, args.seed = "cuda", 16000, 5
+    args.drift_ppm, args.noise_snr_db = 20000.0, [20.0, 30.0]
+    for k, v in kw.items():
+        setattr(args, k, v)
+    a = A.tiny()
+    m = PaaModel(a, A.rule_weights(a), B, L, "fp32")
+    clean = torch.from_numpy(synth.clean_audio(B, L)).cuda()
+    labels = opgd.make_labels(PGD_TEXTS[:B], args, B)
+    return args, m, clean, labels
+
+
+def test_draws_in_graph_follow_the_device_counters():
+    B, L, c0 = 2, 8000, 4
+    args, m, clean, labels = _case(B, L)
+    D = CR.drift_q32(20000.0)
+    p0 = torch.from_numpy(synth.perturbation(L) * np.float32(1e-3)).cuda().view(1, L)
+    st_g, st_e = PgdStepper(m, args, L), PgdStepper(m, args, L)
+    p_g, p_e = p0.clone(), p0.clone()
+    for st in (st_g, st_e):
+        st.set_chan_step(c0)
+    with record_launches() as cap:
+        g, _ = st_g.capture(p_g, clean, labels)
+    torch.cuda.synchronize()
+    seq = ["paa_place_rows", "paa_chan_draw", "paa_drift_apply", "paa_noise_add", "paa_model_fwd_bwd_rows", "paa_drift_apply",
+           "paa_place_reduce", "paa_sign_step", "paa_project"]
+    assert cap == seq + seq                                      # the warm-up step, then the captured one
+    assert int(st_g.chan.counter.item()) == c0 and int(st_g.chan.noise_counter.item()) == c0      # capture() hands both back
+    p_g.copy_(p0)
+    seen = []
+    for k in range(2):
+        g.replay()
+        torch.cuda.synchronize()
+        want_rq, want_snr = CR.draw(5, c0 + k, 0, B, 0, D, 20.0, 30.0)
+        assert st_g.chan.rq.cpu().tolist() == want_rq, k
+        assert np.allclose(st_g.chan.snr_db.cpu().numpy(), want_snr, rtol=0, atol=4e-6)
+        assert int(st_g.chan.counter.item()) == c0 + k + 1 and int(st_g.chan.noise_counter.item()) == c0 + k + 1
+        st_e.step(p_e, clean, labels)
+        torch.cuda.synchronize()
+        assert torch.equal(st_e.chan.rq, st_g.chan.rq) and torch.equal(st_e.chan.rows, st_g.chan.rows)
+        seen.append(st_g.chan.rows.clone())
+    assert not torch.equal(seen[0], seen[1])                     # drawn anew: other ratios, other noise
+    assert torch.equal(p_g, p_e) and not torch.equal(p_g, p0)    # two replays = two eager steps
+
+
+def test_set_channel_pins_ratios_but_not_the_noise():
+    B, L = 2, 8000
+    args, m, clean, labels = _case(B, L)
+    p0 = torch.from_numpy(synth.perturbation(L) * np.float32(1e-3)).cuda().view(1, L)
+    st = PgdStepper(m, args, L)
+    st.set_channel([0.98, 1.01], [25.0, 25.0])
+    p, seen = p0.clone(), []
+    for _ in range(2):
+        with record_launches() as names:
+            st.step(p, clean, labels)
+        assert "paa_chan_draw" not in names and names.count("paa_drift_apply") == 2 and names.count("paa_noise_add") == 1
+        seen.append(st.chan.rows.clone())
+    torch.cuda.synchronize()
+    assert st.chan.rq.cpu().tolist() == [CR.rq_of(0.98), CR.rq_of(1.01)] and int(st.chan.counter.item()) == 0
+    assert int(st.chan.noise_counter.item()) == 2 and not torch.equal(seen[0], seen[1])          # fresh noise under pinned channels
+    st.set_channel(None)
+    with record_launches() as names:
+        st.step(p, clean, labels)
+    torch.cuda.synchronize()
+    assert "paa_chan_draw" in names and st.chan.rq.cpu().tolist() == CR.draw(5, 0, 0, B, 0, CR.drift_q32(20000.0))[0]
+    with pytest.raises(ValueError):
+        st.set_channel([1.0, 1.0, 1.0])
+    with pytest.raises(ValueError):
+        st.set_channel([3.0, 1.0])
+
+
+# ---- 6. unchanged when off ------------------------------------------------------------------------------------------------
+def test_off_is_the_plain_step():
+    B, L = 2, 8000
+    a = A.tiny()
+    m = PaaModel(a, A.rule_weights(a), B, L, "fp32")
+    clean = torch.from_numpy(synth.clean_audio(B, L)).cuda()
+    outs = []
+    for explicit in (False, True):
+        args = cli_to_args("snr", ["--snr_db", "40"])
+        args.device = "cuda"
+        assert not hasattr(args, "drift_ppm") and not hasattr(args, "noise_snr_db")
+        if explicit:
+            args.drift_ppm, args.noise_snr_db = 0.0, None
+        st = PgdStepper(m, args, L)
+        assert not st.chan_on and not st.rir_on and not st.place_on and st.Lp == L and st.packed.numel() == L + 8
+        for name in ("placer", "placed", "chan", "rows", "grad_rows"):
+            assert name not in vars(st), name
+        with pytest.raises(RuntimeError):
+            st.set_channel([1.0, 1.0])
+        with pytest.raises(RuntimeError):
+            st.set_chan_step(3)
+        p = torch.from_numpy(synth.perturbation(L) * np.float32(1e-2)).cuda().view(1, L)
+        labels = opgd.make_labels(PGD_TEXTS[:B], args, B)
+        seqs = []
+        for _ in range(3):
+            with record_launches() as names:
+                r = st.step(p, clean, labels)
+            seqs.append(names)
+        torch.cuda.synchronize()
+        assert seqs[0] == seqs[1] == seqs[2] == ["paa_model_fwd_bwd", "paa_sign_step", "paa_project"]
+        outs.append((p.clone(), r["loss"].clone()))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
+# ---- 7. Adam --------------------------------------------------------------------------------------------------------------
+def test_adam_with_the_channel_matches_torch():
+    B, L, lr = 2, 8000, 2e-4
+    args, m, clean, labels = _case(B, L, optimizer_type="adam", lr=lr)
+    p0 = torch.from_numpy(synth.perturbation(L) * np.float32(1e-3)).cuda().view(1, L)
+    p = torch.nn.Parameter(p0.clone())
+    opt = torch.optim.Adam([p], lr=lr)
+    st = PgdStepper(m, args, L, optimizer=opt)
+    assert st.chan_on and st.Lp == L
+    q = torch.nn.Parameter(p0.clone())
+    ref = torch.optim.Adam([q], lr=lr)
+    for k in range(3):
+        st.step(p.data, clean, labels)
+        torch.cuda.synchronize()
+        assert p.grad.shape == (1, L) and torch.equal(p.grad, -st.grad) and float(st.grad.abs().max()) > 0
+        q.grad = p.grad.clone()
+        ref.step()
+        with torch.no_grad():
+            q.clamp_(-float(args.linf_size), float(args.linf_size))
+        assert torch.equal(p.detach(), q.detach()), k
+    assert torch.equal(opt.state[p]["exp_avg"], ref.state[q]["exp_avg"])
+    assert torch.equal(opt.state[p]["exp_avg_sq"], ref.state[q]["exp_avg_sq"])
+    assert int(st.chan.counter.item()) == 3 and int(st.chan.noise_counter.item()) == 3
+
+
+# ---- 8. two ranks ---------------------------------------------------------------------------------------------------------
+def test_two_ranks_equal_one_with_the_channel(tmp_path):
+    import chan_dist_child as child
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    procs = [subprocess.Popen(["timeout", "-k", "10", "300", sys.executable, os.path.join(ROOT, "tests", "chan_dist_child.py"),
+                               str(r), "2", str(port), str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                              text=True) for r in range(2)]
+    outs = []
+    try:
+        for pr in procs:
+            outs.append(pr.communicate(timeout=330))
+    finally:
+        for pr in procs:
+            if pr.poll() is None:
+                pr.kill()
+    res = []
+    for pr, (so, se) in zip(procs, outs):
+        assert pr.returncode == 0, (so[-2000:], se[-4000:])
+        res.append(json.loads([l for l in so.splitlines() if l.startswith("CHAN_CHILD ")][-1][len("CHAN_CHILD "):]))
+    D = CR.drift_q32(child.DRIFT_PPM)
+    for d in res:
+        assert d["replicas_identical"] and d["graph_equals_eager"] and d["split_graph"] == "_SplitGraph", d
+        assert d["counters"] == [child.STEPS, child.STEPS]
+        # rank r drew clip id r: disjoint from the other rank's, and what the reference draws for that id
+        assert d["rq"] == [CR.draw(5, k, d["rank"], 1, 0, D, *child.NOISE)[0][0] for k in range(child.STEPS)]
+    assert res[0]["rq"] != res[1]["rq"]
+    p_dp = np.load(tmp_path / "rank0.npz")["p_eager"]
+    # one rank holding both clips draws the same ids 0 and 1
+    L, B = child.L, 2
+    args = child.case_args()
+    a = A.tiny()
+    clean = torch.from_numpy(synth.clean_audio(B, L)).cuda()
+    p = torch.from_numpy(synth.perturbation(L) * np.float32(1e-2)).cuda().view(1, L)
+    m = PaaModel(a, A.rule_weights(a), B, L, "fp32")
+    st = PgdStepper(m, args, L)
+    for _ in range(child.STEPS):
+        r = st.step(p, clean, opgd.make_labels(child.TEXTS, args, B))
+    torch.cuda.synchronize()
+    assert st.chan.rq.cpu().tolist() == [res[0]["rq"][-1], res[1]["rq"][-1]]
+    assert res[0]["loss"] == pytest.approx(float(r["loss"]), rel=1e-5)
+    diff = np.abs(p_dp - p.cpu().numpy())
+    scale = np.abs(p.cpu().numpy()).max()
+    print(f"channel DP vs single max diff {diff.max() / scale:.2e}; fraction differing {(diff > 1e-6 * scale).mean():.2e}")
+    assert (diff > 1e-5 * scale).mean() < 5e-3          # only where a gradient sign is numerically undecided
+
+
+# ---- 9. evaluation --------------------------------------------------------------------------------------------------------
+def test_evaluate_repeats_its_channels():
+    from paa_amd.core import loss_helpers
+    from paa_amd.training_utils import evaluation, parser
+    B, L = 2, 8000
+    args = parser.create_arg_parser().parse_args(["--arch", "tiny", "--dtype", "fp32", "--norm_type", "linf", "--drift_ppm", "20000",
+                                                  "--noise_snr_db", "20", "30"])
+    a = A.tiny()
+    m = PaaModel(a, A.rule_weights(a), B, L, "fp32")
+    x = torch.from_numpy(synth.clean_audio(3 * B, L))
+    texts = ["ab cd", "hello", "a b c", "xyz w", "the fox", "dog"]
+    loader = [(x[i:i + B], texts[i:i + B]) for i in range(0, 3 * B, B)]
+    p = torch.from_numpy(synth.perturbation(L) * np.float32(1e-2)).cuda().view(1, L)
+    s1 = evaluation.evaluate(args, loader, p, m, None, None, perturbed=True)
+    s2 = evaluation.evaluate(args, loader, p, m, None, None, perturbed=True)
+    assert (s1.ctc, s1.wer) == (s2.ctc, s2.wer)                  # the counters restart: every evaluation hears the same channels
+    D = CR.drift_q32(20000.0)
+    ctc = []
+    for k, (data, tt) in enumerate(loader):
+        rq, snr = CR.draw(int(args.seed), k, 0, B, 1, D, 20.0, 30.0)
+        rows = channel.drift(p.expand(B, L).contiguous(), rq)
+        rows = channel.add_noise(rows, data.cuda(), snr, seed=int(args.seed), step=k, stream_id=1)
+        r = m.forward(data.cuda(), rows, loss_helpers.make_labels(tt, None, args, B), clamp=False)
+        ctc.append(float(r["loss"]))
+    assert s1.ctc == pytest.approx(sum(ctc) / 3, rel=1e-6)
+    args.drift_ppm, args.noise_snr_db = 0.0, None
+    dry = evaluation.evaluate(args, loader, p, m, None, None, perturbed=True)
+    assert dry.ctc != s1.ctc
