@@ -199,7 +199,7 @@ struct paa_model {
     // workspace
     float* arena = nullptr;
     int64_t arena_floats = 0;
-    float *gn_stats, *gn_bsums, *c0_part, *G = nullptr, *G1 = nullptr, *c0_Mx = nullptr, *c0_kc = nullptr;
+    float *gn_stats, *gn_center, *gn_bsums, *c0_part, *G = nullptr, *G1 = nullptr, *c0_Mx = nullptr, *c0_kc = nullptr;
     Bf c0_w1H{nullptr, nullptr};
     float* gF[2];                    // f32 conv-stack gradients (conv0's input; every layer under the layer-norm variant)
     Bf gH[2];                        // bf16 conv-stack gradients (dgrad GEMM operands), with zero guard rows in front
@@ -371,6 +371,7 @@ extern "C" paa_status paa_model_create(paa_model** out, const paa_arch* arch, co
         }
         const ConvL& c0 = m->conv[0];
         m->gn_stats = take((int64_t)B * c0.cout * 2); m->gn_bsums = take((int64_t)B * c0.cout * 2);
+        m->gn_center = take((int64_t)B * (c0.cout + 1));
         m->c0_part = take(conv0_part_floats(B, c0.T, c0.cout));
         if (a.feat_norm_layer) m->G = take((int64_t)B * c0.P * c0.k);
         else {
@@ -488,7 +489,7 @@ static paa_status forward(paa_model* m, const float* clean, const float* p, int 
         ca.lens = m->lens;
         ca.clean = clean; ca.p = p; ca.p_ld = p_ld; ca.grad_rows = p_ld != 0; ca.clamp = clamp; ca.B = B; ca.L = m->L; ca.T = c.T; ca.P = c.P; ca.C = c.cout;
         ca.k = c.k; ca.stride = c.s; ca.w = c.w0; ca.bias = c.b; ca.gamma = c.g; ca.beta = c.beta; ca.eps = 1e-5f;
-        ca.pre = c.pre; ca.pre16 = c.pre16; ca.gate = c.gate; ca.actb = c.actb; ca.gn_stats = m->gn_stats; ca.row_stats = c.row_stats;
+        ca.pre = c.pre; ca.pre16 = c.pre16; ca.gate = c.gate; ca.actb = c.actb; ca.gn_stats = m->gn_stats; ca.gn_center = m->gn_center; ca.row_stats = c.row_stats;
         if (a.feat_norm_layer) PAA_TRY(conv0_ln_forward(ca, st)); else PAA_TRY(conv0_gn_forward(ca, m->c0_part, st));
     }
     for (int i = 1; i < nc; ++i) {
@@ -735,7 +736,7 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
         ca.lens = m->lens;
         ca.clean = clean; ca.p = p; ca.p_ld = p_ld; ca.grad_rows = p_ld != 0; ca.clamp = clamp; ca.B = B; ca.L = m->L; ca.T = c.T; ca.P = c.P; ca.C = c.cout;
         ca.k = c.k; ca.stride = c.s; ca.w = c.w0; ca.bias = c.b; ca.gamma = c.g; ca.beta = c.beta; ca.eps = 1e-5f;
-        ca.gn_stats = m->gn_stats; ca.gn_bsums = m->gn_bsums; ca.row_stats = c.row_stats; ca.dpre = m->gF[0]; ca.G = m->G;
+        ca.gn_stats = m->gn_stats; ca.gn_center = m->gn_center; ca.gn_bsums = m->gn_bsums; ca.row_stats = c.row_stats; ca.dpre = m->gF[0]; ca.G = m->G;
         ca.dpreb = m->g0H; ca.G1 = m->G1; ca.w1b = m->c0_w1H; ca.Mx = m->c0_Mx; ca.kc = m->c0_kc;
         PAA_TRY(conv0_backward(ca, a.feat_norm_layer, m->prec, m->c0_part, grad, st));
     }

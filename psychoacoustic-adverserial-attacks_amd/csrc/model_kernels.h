@@ -39,6 +39,7 @@ struct Conv0Args {
     int gate;                // group-norm forward: pre keeps gelu'(.) (f32 unless pre16)
     Bf actb;                 // (B, P, C) GELU(pre) as bf16 planes (the next conv's GEMM operand)
     float* gn_stats;         // group: (B, C, 2) mean, rstd over time
+    float* gn_center;        // group forward: (B, 1 + C) the clip's sample mean m, then mean_c - m * sum_j w_cj per channel
     float* gn_bsums;         // group backward: (B, C, 2) mean_t(dy), mean_t(dy * xhat)
     float* row_stats;        // layer: (B, P, 2) mean, rstd over channels
     const float* dpre;       // backward, layer-norm variant: (B, P, C) f32 gradient wrt `pre`

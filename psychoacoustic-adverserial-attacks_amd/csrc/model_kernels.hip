@@ -220,7 +220,12 @@ __global__ __launch_bounds__(256) void k_conv0_gn(Conv0Args a) {
     const int nt = min(C0_TCH, a.T - t0);
     const int span = (nt - 1) * a.stride + a.k;
     const int span_alloc = (C0_TCH - 1) * a.stride + 10 + 8;
-    for (int i = threadIdx.x; i < span_alloc; i += 256) xs[i] = (i < span) ? in_sample(a, b, t0 * a.stride + i) : 0.f;
+    // forward: the samples are centred on the clip's mean m and the channel mean is that of the centred conv output,
+    // mean_c - m * sum_j w_cj (k_conv0_gn_stats) — the same v - mean, but its f32 rounding scales with |x - m| instead of |x|:
+    // on a DC offset the residue of v - mean (times rstd up to 1 / sqrt(eps) = 316) vanishes with the signal's variation
+    const float xm = MODE == 1 ? a.gn_center[(size_t)b * (a.C + 1)] : 0.f;
+    const float* cmean = MODE == 1 ? a.gn_center + (size_t)b * (a.C + 1) + 1 : nullptr;
+    for (int i = threadIdx.x; i < span_alloc; i += 256) xs[i] = (i < span) ? in_sample(a, b, t0 * a.stride + i) - xm : 0.f;
     __syncthreads();
     // wav2vec2's conv0 (k = 10, stride 5, even C): a thread owns a channel PAIR (4-byte bf16x2 accesses instead of
     // 2-byte ones) and walks the frames 4 at a time — the 4 windows come from 7 broadcast ds_read_b128 and, in the
@@ -232,7 +237,8 @@ __global__ __launch_bounds__(256) void k_conv0_gn(Conv0Args a) {
             f32x2 s1 = {0.f, 0.f}, s2 = {0.f, 0.f};
 #pragma unroll
             for (int j = 0; j < 10; ++j) w2[j] = f32x2{a.w[c * 10 + j], a.w[(c + 1) * 10 + j]};
-            mean2 = f32x2{a.gn_stats[((size_t)b * a.C + c) * 2], a.gn_stats[((size_t)b * a.C + c + 1) * 2]};
+            mean2 = MODE == 1 ? f32x2{cmean[c], cmean[c + 1]}
+                              : f32x2{a.gn_stats[((size_t)b * a.C + c) * 2], a.gn_stats[((size_t)b * a.C + c + 1) * 2]};
             rstd2 = f32x2{a.gn_stats[((size_t)b * a.C + c) * 2 + 1], a.gn_stats[((size_t)b * a.C + c + 1) * 2 + 1]};
             gam2 = f32x2{a.gamma[c], a.gamma[c + 1]};
             bet2 = f32x2{a.beta[c], a.beta[c + 1]};
@@ -302,7 +308,7 @@ __global__ __launch_bounds__(256) void k_conv0_gn(Conv0Args a) {
             float w[10];
 #pragma unroll
             for (int j = 0; j < 10; ++j) w[j] = (j < a.k) ? a.w[c * a.k + j] : 0.f;
-            const float mean = a.gn_stats[((size_t)b * a.C + c) * 2], rstd = a.gn_stats[((size_t)b * a.C + c) * 2 + 1];
+            const float mean = MODE == 1 ? cmean[c] : a.gn_stats[((size_t)b * a.C + c) * 2], rstd = a.gn_stats[((size_t)b * a.C + c) * 2 + 1];
             const float gam = a.gamma[c], bet = a.beta[c];
             float s1 = 0.f, s2 = 0.f;
             for (int t = 0; t < nt; ++t) {
@@ -351,9 +357,9 @@ __global__ __launch_bounds__(256) void k_conv0_gn(Conv0Args a) {
 // GroupNorm statistics of conv0 WITHOUT a pass over the (T, C) output.  With one input channel the output of channel
 // c at frame t is w_c . x_t (x_t = the k input samples of the frame), so over a clip
 //   sum_t v = w_c . Sx,   sum_t v^2 = w_c^T Gx w_c,   Sx = sum_t x_t,  Gx = sum_t x_t x_t^T   (k x k, per clip)
-// k_conv0_gram accumulates the 55 + 10 distinct entries per chunk of frames (f32 products of <= 8 frames per thread,
-// summed in f64, fixed order => reproducible); k_conv0_gn_stats reduces the chunks and evaluates the two quadratic
-// forms per channel in f64.
+// k_conv0_gram accumulates the 55 + 10 distinct entries per chunk of frames (exact f64 products, summed in f64 in a
+// fixed order => reproducible); k_conv0_gn_stats reduces the chunks and evaluates the two quadratic forms per channel
+// in f64.
 constexpr int C0_GCH = 2048;       // frames per workgroup of the Gram kernel
 constexpr int C0_GQ = 66;          // 55 lower-triangle products + 10 sums (+1 pad)
 __global__ __launch_bounds__(256) void k_conv0_gram(Conv0Args a, double* __restrict__ part) {
@@ -365,13 +371,16 @@ __global__ __launch_bounds__(256) void k_conv0_gram(Conv0Args a, double* __restr
     const int span = (nt - 1) * a.stride + a.k;
     for (int i = threadIdx.x; i < span; i += 256) xs[i] = in_sample(a, b, t0 * a.stride + i);
     __syncthreads();
-    float acc[65];
+    // products and sums in f64: the product of two floats is exact there.  A channel whose taps nearly cancel on a smooth signal
+    // (a difference filter on a tone or a DC offset) makes w^T Gx w 1e3 .. 1e6 times smaller than its terms, and f32 products
+    // left their rounding in rstd at 1e-3 ("conv0 statistics on tonal input")
+    double acc[65];
 #pragma unroll
-    for (int q = 0; q < 65; ++q) acc[q] = 0.f;
+    for (int q = 0; q < 65; ++q) acc[q] = 0.0;
     for (int t = threadIdx.x; t < nt; t += 256) {
-        float xw[10];
+        double xw[10];
 #pragma unroll
-        for (int j = 0; j < 10; ++j) xw[j] = j < a.k ? xs[t * a.stride + j] : 0.f;
+        for (int j = 0; j < 10; ++j) xw[j] = j < a.k ? (double)xs[t * a.stride + j] : 0.0;
         int idx = 0;
 #pragma unroll
         for (int j = 0; j < 10; ++j)
@@ -386,7 +395,7 @@ __global__ __launch_bounds__(256) void k_conv0_gram(Conv0Args a, double* __restr
     const int wv = threadIdx.x >> 6;
 #pragma unroll
     for (int q = 0; q < 65; ++q) {
-        const double t = wave_sum((double)acc[q]);
+        const double t = wave_sum(acc[q]);
         if ((threadIdx.x & 63) == 0) red[wv][q] = t;
     }
     __syncthreads();
@@ -407,19 +416,27 @@ __global__ __launch_bounds__(256) void k_conv0_gn_stats(Conv0Args a, const doubl
         G[threadIdx.x] = t;
     }
     __syncthreads();
+    // the clip's sample mean m (over the frames' taps), as the f32 the forward kernel subtracts from every sample
+    double sx = 0.0;
+#pragma unroll
+    for (int j = 0; j < 10; ++j) sx += G[55 + j];
+    const float m = (float)(sx / ((double)a.k * a.T));
+    if (threadIdx.x == 0) a.gn_center[(size_t)b * (a.C + 1)] = m;
     for (int c = threadIdx.x; c < a.C; c += 256) {
         double w[10];
 #pragma unroll
         for (int j = 0; j < 10; ++j) w[j] = j < a.k ? (double)a.w[c * a.k + j] : 0.0;
-        double s1 = 0.0, s2 = 0.0;
+        double s1 = 0.0, s2 = 0.0, sw = 0.0;
         int idx = 0;
 #pragma unroll
         for (int j = 0; j < 10; ++j) {
 #pragma unroll
             for (int q = 0; q <= j; ++q) { s2 += (q == j ? 1.0 : 2.0) * w[j] * w[q] * G[idx]; ++idx; }
             s1 += w[j] * G[55 + j];
+            sw += w[j];
         }
         const double mean = s1 / a.T;
+        a.gn_center[(size_t)b * (a.C + 1) + 1 + c] = (float)(mean - (double)m * sw);      // mean of w_c . (x_t - m)
         double var = s2 / a.T - mean * mean;
         if (var < 0.0) var = 0.0;
         a.gn_stats[((size_t)b * a.C + c) * 2] = (float)mean;
