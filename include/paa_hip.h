@@ -526,6 +526,36 @@ paa_status paa_ctc_padded(const float* logits, const int32_t* labels, int B, int
 paa_status paa_mul_gelu_grad_planes(const float* dy, const float* pre, float* out, void* out_hi, void* out_lo, int out_il,
                                     int64_t n, void* stream);
 
+/* ------------------------------------------------------ alignment-margin loss ----- */
+/* Forced alignment of every clip's label row to its frames, and the Carlini-Wagner hinge on that alignment.  For clip b with
+ * T_b = d_frames[b] frames (clamped to [1, T]; d_frames NULL: T), valid labels l_1..l_S (the non-negative entries of its row, in
+ * order) and extended states e_0..e_2S = blank, l_1, blank, ..., blank:
+ *   v_0(0) = z[0][blank], v_0(1) = z[0][l_1];   v_t(s) = z[t][e_s] + max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2))
+ * on the RAW logits z in float64 (s-2 only where e_s != blank and e_s != e_{s-2}); among equal maxima the predecessor with the
+ * largest state index wins (stay, then s-1, then s-2), and at the end state 2S wins over 2S-1.  pi_t = e_s of the path's state.
+ *   m_t = (double)kappa + z[t][c*_t] - z[t][pi_t],   c*_t = the first maximum of z[t][c] over c != pi_t
+ *   loss[b] = sum_{t < T_b} max(m_t, 0)                                (float64 sum in a fixed order, rounded once to f32)
+ *   dlogits[t][c*_t] = +grad_scale, dlogits[t][pi_t] = -grad_scale on the frames with m_t > 0, every other entry 0
+ * logits / dlogits are (B, Tpad, V) with Tpad >= T: frames [T, Tpad) of the logits are not read; rows t >= T_b and the pad rows of
+ * dlogits and of its planar bf16 planes dlb_hi / dlb_lo (nullable; they need dlogits and a hi plane) are zeros.  A label row
+ * that no path of T_b frames spells gives loss[b] = +inf, NaN in the clip's dlogits rows and the all-blank alignment; the other
+ * clips are not affected.  align (B, T) int16 (nullable) receives pi, `blank` for t >= T_b.  dlogits NULL: forced aligner and
+ * loss only.  labels (B, S_max) int32, values < V, negatives = padding anywhere in the row; 2 S_max + 1 <= 1024, 2 <= V <= 256,
+ * T <= 8192.  work: paa_align_margin_work_floats(B, T, V, S_max) floats, 16-byte aligned.  Two calls give the same bits.
+ * PAA_ERR_ARG: a null logits / labels / loss / work, planes without dlogits, kappa negative or not finite, a misaligned work
+ * buffer; PAA_ERR_SIZE: a shape outside the ranges above.  Additions to ABI 350. */
+int64_t paa_align_margin_work_floats(int B, int T, int V, int S_max);
+paa_status paa_align_margin(const float* logits, const int32_t* labels, const int32_t* d_frames /* nullable */, int B, int T,
+                            int Tpad, int V, int S_max, int blank, float kappa, float grad_scale, float* loss /* B */,
+                            int16_t* align /* (B, T), nullable */, float* dlogits /* nullable */, void* dlb_hi, void* dlb_lo,
+                            float* work, void* stream);
+/* The loss of every later paa_model_fwd_bwd{,_rows} call, with or without a gradient: kind 0 = CTC (the default), 1 = the alignment
+ * margin above with `kappa` (direction as grad_scale, the model's true clip lengths as d_frames).  The per-clip values land where
+ * the CTC values do, so d_stats[0] = sum_b loss_b.  paa_model_forward{,_rows} keep reporting CTC.  Kind 0 restores bits identical
+ * to a model that never had a loss set.  Kind 1 needs 2 S_max + 1 <= 1024 at the call (PAA_ERR_SIZE there).  Not itself
+ * capturable (it changes what later calls launch).  PAA_ERR_ARG: a null model, another kind, kappa negative or not finite. */
+paa_status paa_model_set_loss(paa_model* m, int kind, float kappa);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,10 @@ _SIGS = {
     "paa_attn_bwd_split_len": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 6 + [C.c_void_p]),
     "paa_ctc_len": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float] + [C.c_void_p] * 4),
     "paa_zero_frames": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    # alignment-margin loss
+    "paa_align_margin_work_floats": (C.c_int64, [C.c_int] * 4),
+    "paa_align_margin": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float] * 2 + [C.c_void_p] * 7),
+    "paa_model_set_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
 }
 
 _lib = None

@@ -12,6 +12,10 @@ collective, and one gather after the last batch brings the records to rank 0, wh
 ``--bound_search shrink`` answers "how small a perturbation makes this clip fall?": the moment a clip's attack
 succeeds its delta is remembered and its bound is multiplied by ``--search_shrink``; the record then describes the smallest
 successful delta (``found``, ``found_step``, ``bound_scale``, ``last_scale``), or the last iterate of a clip that never fell.
+
+``--loss_type margin`` (targeted attacks): the steps optimise the alignment-margin loss, which is zero exactly when
+the greedy decode is the target — the search's success test.  The step's ``loss`` then holds the margin loss; the records'
+``clean_ctc`` / ``final_ctc`` stay CTC.
 """
 from __future__ import annotations
 
@@ -236,7 +240,7 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
 def main(args) -> int:
     # what per-clip perturbations do not run with, and the refusals of --clip_lengths true: before any launch or collective
     lengths_mode = modes.check(modes.Modes.of(args), ("place_clips", "rir_clips", "chan_range", "chan_clips") + modes.LENGTHS).lengths_on
-    modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS, modes.Ctx(search=modes.SearchConfig.of(args)))
+    modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS + modes.MARGIN, modes.Ctx(search=modes.SearchConfig.of(args)))
     if not torch.cuda.is_available():
         raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")
     if not str(args.device).startswith("cuda"):

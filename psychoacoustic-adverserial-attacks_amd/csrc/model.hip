@@ -217,6 +217,9 @@ struct paa_model {
     const int32_t* lens = nullptr;
     int32_t* frames = nullptr;
     const int32_t* fr() const { return lens ? frames : nullptr; }
+    // the loss of paa_model_fwd_bwd{,_rows} (paa_model_set_loss): 0 = CTC, 1 = alignment margin with `kappa`
+    int loss_kind = 0;
+    float kappa = 0.f;
 };
 
 static const float* find(paa_model* m, const std::string& n, int64_t numel, paa_status* st) {
@@ -406,7 +409,8 @@ extern "C" paa_status paa_model_create(paa_model** out, const paa_arch* arch, co
         m->logits = take((int64_t)m->M * V); m->dlogits = take((int64_t)m->M * V); m->dlogitsH = take_bf((int64_t)m->M * V);
         m->nll = take(B);
         m->S_cap = std::min(2047, std::max(64, m->T));    // labels longer than T_e are infeasible (infinite CTC loss) but legal
-        m->ctc_work = take((int64_t)B * ctc_work_floats_per_clip(m->T, V, m->S_cap));
+        m->ctc_work = take((int64_t)B * std::max(ctc_work_floats_per_clip(m->T, V, m->S_cap),      // the larger of the two losses' layouts
+                                                 align_margin_work_floats_per_clip(m->T)));
         m->dxa = take(MH); m->dxaH = take_bf(MH, m->ail); m->dxb = take(MH); m->dxbH = take_bf(MH, m->ail);
         m->dqkvH = take_bf(3 * MH);
         if (m->fused) { m->dctxH = take_bf(MH); m->delta = take(LS); }
@@ -763,8 +767,12 @@ static paa_status fwd_bwd_impl(paa_model* m, const float* d_clean, const float* 
         PAA_LAUNCH_CHECK();
     }
     if (d_labels) {
-        PAA_TRY(ctc(m->logits, d_labels, B, m->T, m->P, V, S_max, m->a.blank, (float)direction, m->nll,
-                    d_grad ? m->dlogits : nullptr, d_grad ? m->dlogitsH : NOBF, m->ctc_work, st, m->fr()));
+        if (m->loss_kind == 1)
+            PAA_TRY(align_margin(m->logits, d_labels, m->fr(), B, m->T, m->P, V, S_max, m->a.blank, m->kappa, (float)direction, m->nll,
+                                 nullptr, d_grad ? m->dlogits : nullptr, d_grad ? m->dlogitsH : NOBF, m->ctc_work, st));
+        else
+            PAA_TRY(ctc(m->logits, d_labels, B, m->T, m->P, V, S_max, m->a.blank, (float)direction, m->nll,
+                        d_grad ? m->dlogits : nullptr, d_grad ? m->dlogitsH : NOBF, m->ctc_work, st, m->fr()));
         if (d_stats) PAA_TRY(sum_small(m->nll, B, d_stats, st));
     }
     if (d_grad) PAA_TRY(backward(m, d_clean, d_p, p_ld, clamp, B, d_grad, st));
@@ -834,6 +842,16 @@ extern "C" paa_status paa_model_set_lengths(paa_model* m, const int32_t* d_lengt
         PAA_FAIL(PAA_ERR_ARG, "paa_model_set_lengths: per-clip lengths need the fused attention path (head dim 64, got %d)",
                  m->a.hidden / m->a.heads);
     m->lens = d_lengths;
+    return PAA_OK;
+}
+// ---- loss of the training calls ----
+extern "C" paa_status paa_model_set_loss(paa_model* m, int kind, float kappa) {
+    if (!m) PAA_FAIL(PAA_ERR_ARG, "paa_model_set_loss: null model");
+    if (kind != 0 && kind != 1) PAA_FAIL(PAA_ERR_ARG, "paa_model_set_loss: kind=%d must be 0 (CTC) or 1 (alignment margin)", kind);
+    if (kind == 1 && !(kappa >= 0.f && kappa < INFINITY))
+        PAA_FAIL(PAA_ERR_ARG, "paa_model_set_loss: kappa=%g must be finite and >= 0", (double)kappa);
+    m->loss_kind = kind;
+    m->kappa = kind == 1 ? kappa : 0.f;
     return PAA_OK;
 }
 extern "C" paa_status paa_model_frame_counts(paa_model* m, int B, int32_t* d_out, void* stream) {

@@ -85,6 +85,11 @@ int64_t conv0_part_floats(int B, int T, int C);
 paa_status ctc(const float* logits, const int32_t* labels, int B, int T, int Tpad, int V, int S_max, int blank,
                float grad_scale, float* nll, float* dlogits, Bf dlb, float* work, hipStream_t st,
                const int32_t* frames = nullptr);   // per-clip frame counts in [1, T] (device), or null
+// forced alignment + alignment-margin loss (paa_align_margin with the planes as a Bf)
+int64_t align_margin_work_floats_per_clip(int T);
+paa_status align_margin(const float* logits, const int32_t* labels, const int32_t* frames, int B, int T, int Tpad, int V, int S_max,
+                        int blank, float kappa, float grad_scale, float* loss, int16_t* align, float* dlogits, Bf dlb, float* work,
+                        hipStream_t st);
 paa_status sum_small(const float* x, int n, float* out, hipStream_t st);
 
 // Fused attention (attention.hip): bf16 hi planes only (bf16 mode), head_dim 64.

@@ -1598,6 +1598,251 @@ paa_status ctc(const float* logits, const int32_t* labels, int B, int T, int Tpa
     return PAA_OK;
 }
 
+// ---- alignment-margin loss: forced alignment by Viterbi, then a per-frame hinge ------------------------------
+// The max-plus twin of k_ctc_rec on RAW logits (every path has one emission per frame, so the per-frame log-partition cancels in
+// the argmax): v_t(s) = z[t][e_s] + max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2)), float64, one add per frame, no transcendentals
+// and no beta pass.  One wave per clip, lane i owning the NS consecutive states i * NS .. i * NS + NS - 1 in registers, the
+// neighbour lane's two boundary states arriving by wave_shr1.  Ties go to the predecessor with the LARGEST state index (stay
+// over s-1 over s-2), at the end state 2S wins over 2S-1.  The back-pointer of a state is 2 bits (0 stay, 1, 2), a lane's NS of
+// them one 32-bit word per frame: row t of the table is 64 words, stored coalesced.  The backtrace is a chain of T dependent
+// steps; it walks the table out of LDS, staged in blocks of AL_BLK frames (the whole table at T <= AL_BLK).
+//
+// Per-clip work layout (floats): hv [T] f64 (hinge value of every frame) | best f64 (value of the path; <= -1e29: infeasible) |
+// bp [T][64] u32 | pi [T] i16
+constexpr int AL_BLK = 512;          // frames of back-pointers staged in LDS at a time (128 KiB)
+constexpr int AL_PF = 4;             // frames of emissions in flight ahead of the recursion
+constexpr int AL_TMAX = 8192;
+struct AlignWork {
+    double* hv; double* best; unsigned* bp; int16_t* pi;
+};
+static int64_t align_work_floats_per_clip(int T) {
+    return 2 * (((int64_t)T + 2) & ~(int64_t)1) + 64 * (int64_t)T + ((int64_t)T + 7) / 8 * 4;      // bp stays 16-byte aligned
+}
+__device__ __forceinline__ AlignWork align_work(float* wk, int T) {
+    AlignWork w;
+    w.hv = reinterpret_cast<double*>(wk);
+    w.best = w.hv + T;
+    w.bp = reinterpret_cast<unsigned*>(w.hv + ((T + 2) & ~1));
+    w.pi = reinterpret_cast<int16_t*>(w.bp + (size_t)64 * T);
+    return w;
+}
+
+template <int NS>
+__global__ __launch_bounds__(64) void k_align_rec(const float* __restrict__ logits, const int32_t* __restrict__ labels, int Tall,
+                                                  int Tpad, int V, int S_max, int blank, int16_t* __restrict__ align,
+                                                  float* __restrict__ work, int64_t wpc, const int32_t* __restrict__ frames) {
+    extern __shared__ __attribute__((aligned(16))) unsigned sma[];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int T = ctc_frames(frames, b, Tall);
+    const int SPmax = 2 * S_max + 1;
+    const int nblk = max(T < AL_BLK ? T : AL_BLK, 2 * NS);         // as the launcher sizes it: fin needs 2 NS rows
+    unsigned* tab = sma;                                           // [nblk][64] back-pointer words of the staged block
+    int* lab = reinterpret_cast<int*>(sma + (size_t)64 * nblk);    // [SPmax] extended labels
+    int* raw = lab + SPmax;                                        // [S_max]
+    double* fin = reinterpret_cast<double*>(tab);                  // [64 NS] final values (before the table is staged)
+    __shared__ int s_len;
+    const AlignWork w = align_work(work + (size_t)b * wpc, Tall);
+    const float* lg = logits + (size_t)b * Tpad * V;
+    for (int s = lane; s < S_max; s += 64) raw[s] = labels[(size_t)b * S_max + s];
+    __syncthreads();
+    if (lane == 0) {           // valid labels are the non-negative entries, in order (as k_ctc_rec compacts them)
+        int k = 0;
+        lab[0] = blank;
+        for (int s = 0; s < S_max; ++s) {
+            const int v = raw[s];
+            if (v >= 0) { lab[2 * k + 1] = v; lab[2 * k + 2] = blank; ++k; }
+        }
+        s_len = k;
+    }
+    __syncthreads();
+    const int S = s_len, SP = 2 * S + 1;
+    int l[NS];
+    unsigned skf = 0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int s = lane * NS + j;
+        l[j] = s < SP ? lab[s] : blank;
+        if (s < SP && s >= 2 && l[j] != blank && l[j] != lab[s - 2]) skf |= 1u << j;
+    }
+    // ---- recursion: emissions are fetched AL_PF frames ahead (a step is a handful of fmax, far shorter than an L2 round trip)
+    float e[AL_PF][NS], en[AL_PF][NS];
+    auto fetch = [&](int t0, float (&o)[AL_PF][NS]) {
+#pragma unroll
+        for (int u = 0; u < AL_PF; ++u) {
+            const int t = t0 + u < T ? t0 + u : T - 1;             // past the clip's end: a frame that exists, never used
+#pragma unroll
+            for (int j = 0; j < NS; ++j) o[u][j] = lg[(size_t)t * V + l[j]];
+        }
+    };
+    double a[NS];
+    fetch(0, e);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int s = lane * NS + j;
+        a[j] = ((s == 0 || s == 1) && s < SP) ? (double)e[0][j] : CTC_NEG;
+    }
+    for (int t0 = 0; t0 < T; t0 += AL_PF) {
+        if (t0 + AL_PF < T) fetch(t0 + AL_PF, en);
+#pragma unroll
+        for (int u = 0; u < AL_PF; ++u) {
+            const int t = t0 + u;
+            if (t == 0 || t >= T) continue;
+            const double n1 = wave_shr1(a[NS - 1]);
+            const double n2 = NS >= 2 ? wave_shr1(a[NS >= 2 ? NS - 2 : 0]) : wave_shr1(n1);
+            double nw[NS];
+            unsigned word = 0;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                const double x1 = j >= 1 ? a[j >= 1 ? j - 1 : 0] : n1;
+                const double x2r = j >= 2 ? a[j >= 2 ? j - 2 : 0] : (j == 1 ? n1 : n2);
+                const double x2 = (skf & (1u << j)) ? x2r : CTC_NEG;
+                const unsigned d = (a[j] >= x1 && a[j] >= x2) ? 0u : (x1 >= x2 ? 1u : 2u);
+                nw[j] = (double)e[u][j] + fmax(a[j], fmax(x1, x2));
+                word |= d << (2 * j);
+            }
+#pragma unroll
+            for (int j = 0; j < NS; ++j) a[j] = nw[j];
+            w.bp[(size_t)t * 64 + lane] = word;
+        }
+#pragma unroll
+        for (int u = 0; u < AL_PF; ++u)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) e[u][j] = en[u][j];
+    }
+    // ---- the end state: 2S over 2S-1 when equal
+#pragma unroll
+    for (int j = 0; j < NS; ++j) fin[lane * NS + j] = a[j];
+    __threadfence();           // the back-pointer rows are read back below by other lanes
+    __syncthreads();
+    int s_cur = SP - 1;
+    double best = fin[SP - 1];
+    if (SP >= 2 && !(best >= fin[SP - 2])) { best = fin[SP - 2]; s_cur = SP - 2; }
+    if (lane == 0) *w.best = best;
+    const bool feasible = best > -1e29;
+    __syncthreads();           // fin aliases the staged table
+    // ---- backtrace: blocks of the table, last first, through LDS; every lane walks the same path (uniform LDS reads)
+    if (feasible) {
+        for (int hi = T; hi > 1; ) {                       // rows [lo, hi) of the table, lo >= 1 (row 0 holds nothing)
+            const int lo = hi - 1 > AL_BLK ? hi - AL_BLK : 1;
+            const uint4* src = reinterpret_cast<const uint4*>(w.bp + (size_t)lo * 64);
+            uint4* dst = reinterpret_cast<uint4*>(tab);
+            const int n4 = (hi - lo) * 16;
+            for (int i = lane; i < n4; i += 64) dst[i] = src[i];
+            __syncthreads();
+            for (int t = hi - 1; t >= lo; --t) {
+                if (lane == 0) w.pi[t] = (int16_t)lab[s_cur];
+                const unsigned word = tab[(size_t)(t - lo) * 64 + s_cur / NS];
+                s_cur = max(s_cur - (int)((word >> (2 * (s_cur % NS))) & 3u), 0);      // (a NaN logit can break d <= s)
+            }
+            __syncthreads();
+            hi = lo;
+        }
+        if (lane == 0) w.pi[0] = (int16_t)lab[s_cur];
+    } else {
+        for (int t = lane; t < T; t += 64) w.pi[t] = (int16_t)blank;
+    }
+    __threadfence();
+    __syncthreads();
+    if (align) for (int t = lane; t < Tall; t += 64) align[(size_t)b * Tall + t] = t < T ? w.pi[t] : (int16_t)blank;
+}
+
+// The hinge of every frame, one wave per frame (grid: frames / 4 x clips, as k_ctc_grad): c* = the first maximum over c != pi_t,
+// m = kappa + z[c*] - z[pi_t] in float64; an active frame (m > 0) gets +g at c*, -g at pi_t, every other entry 0.  Rows past the
+// clip's end and pad rows are zeros; the rows of an infeasible clip NaN.  hv[t] = max(m, 0) for k_align_loss.
+__global__ __launch_bounds__(256) void k_align_hinge(const float* __restrict__ logits, int Tall, int Tpad, int V, float kappa,
+                                                     float gscale, float* __restrict__ dlogits, Bf dlb, float* __restrict__ work,
+                                                     int64_t wpc, const int32_t* __restrict__ frames) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = blockIdx.x * 4 + wave;
+    const int T = ctc_frames(frames, b, Tall);
+    const AlignWork w = align_work(work + (size_t)b * wpc, Tall);
+    const size_t row = ((size_t)b * Tpad + t) * V;
+    if (t >= T) {
+        if (t < Tpad && dlogits) for (int c = lane; c < V; c += 64) { dlogits[row + c] = 0.f; store_bf16(dlb, row + c, 0.f); }
+        return;
+    }
+    if (!(*w.best > -1e29)) {
+        if (dlogits) for (int c = lane; c < V; c += 64) { dlogits[row + c] = NAN; store_bf16(dlb, row + c, NAN); }
+        return;
+    }
+    const int pi = w.pi[t];
+    const float* z = logits + row;
+    float mx = -INFINITY;
+    int mi = 0x7fffffff;
+    for (int c = lane; c < V; c += 64) {           // ascending c: a strict compare keeps the lowest index
+        const float v = z[c];
+        if (c != pi && (v > mx || mi == 0x7fffffff)) { mx = v; mi = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(mx, o, 64);
+        const int oi = __shfl_xor(mi, o, 64);
+        if (oi != 0x7fffffff && (mi == 0x7fffffff || ov > mx || (ov == mx && oi < mi))) { mx = ov; mi = oi; }
+    }
+    const double m = ((double)kappa + (double)mx) - (double)z[pi];
+    const bool act = m > 0.0;
+    if (lane == 0) w.hv[t] = act ? m : 0.0;
+    if (!dlogits) return;
+    for (int c = lane; c < V; c += 64) {
+        const float gv = !act ? 0.f : (c == mi ? gscale : (c == pi ? -gscale : 0.f));
+        dlogits[row + c] = gv;
+        store_bf16(dlb, row + c, gv);
+    }
+}
+
+// loss_b = sum_t hv[t] in float64: thread i sums frames i, i + 256, ... in order, then the fixed tree of block_sum
+__global__ __launch_bounds__(256) void k_align_loss(int Tall, float* __restrict__ loss, const float* __restrict__ work, int64_t wpc,
+                                                    const int32_t* __restrict__ frames) {
+    __shared__ double red[256 / 64];
+    const int b = blockIdx.x;
+    const int T = ctc_frames(frames, b, Tall);
+    const AlignWork w = align_work(const_cast<float*>(work) + (size_t)b * wpc, Tall);
+    const bool feasible = *w.best > -1e29;
+    double s = 0.0;
+    if (feasible) for (int t = threadIdx.x; t < T; t += 256) s += w.hv[t];
+    s = block_sum<double, 256>(s, red);
+    if (threadIdx.x == 0) loss[b] = feasible ? (float)s : INFINITY;
+}
+
+int64_t align_margin_work_floats_per_clip(int T) { return align_work_floats_per_clip(T); }
+
+paa_status align_margin(const float* logits, const int32_t* labels, const int32_t* frames, int B, int T, int Tpad, int V, int S_max,
+                        int blank, float kappa, float grad_scale, float* loss, int16_t* align, float* dlogits, Bf dlb, float* work,
+                        hipStream_t st) {
+    if (!logits || !labels || !loss || !work) PAA_FAIL(PAA_ERR_ARG, "align_margin: null argument");
+    if (dlb.hi && !dlogits) PAA_FAIL(PAA_ERR_ARG, "align_margin: planes need dlogits");
+    if (!(kappa >= 0.f && kappa < INFINITY)) PAA_FAIL(PAA_ERR_ARG, "align_margin: kappa=%g must be finite and >= 0", (double)kappa);
+    if ((uintptr_t)work & 15) PAA_FAIL(PAA_ERR_ARG, "align_margin: work buffer must be 16-byte aligned");
+    if (B < 1 || T < 1 || T > AL_TMAX || Tpad < T || V < 2 || V > 256 || blank < 0 || blank >= V)
+        PAA_FAIL(PAA_ERR_SIZE, "align_margin: B=%d T=%d (max %d) Tpad=%d V=%d (2..256) blank=%d", B, T, AL_TMAX, Tpad, V, blank);
+    const int SPmax = 2 * S_max + 1;
+    const int ns = S_max >= 1 ? ctc_ws_ns(SPmax) : 0;
+    if (!ns) PAA_FAIL(PAA_ERR_SIZE, "align_margin: S_max=%d out of range (2 S_max + 1 <= 1024)", S_max);
+    const int64_t wpc = align_work_floats_per_clip(T);
+    const size_t lds = sizeof(unsigned) * 64 * (size_t)std::max(std::min(T, AL_BLK), 2 * ns) + sizeof(int) * ((size_t)SPmax + S_max);
+#define PAA_ALIGN_REC(N)                                                                                                              \
+    case N: {                                                                                                                         \
+        static bool attr = false;                                                                                                     \
+        if (!attr) {                                                                                                                  \
+            PAA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_align_rec<N>), hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                        152 * 1024));                                                                                 \
+            attr = true;                                                                                                              \
+        }                                                                                                                             \
+        hipLaunchKernelGGL((k_align_rec<N>), dim3(B), dim3(64), lds, st, logits, labels, T, Tpad, V, S_max, blank, align, work, wpc,  \
+                           frames);                                                                                                   \
+        break;                                                                                                                        \
+    }
+    switch (ns) { PAA_ALIGN_REC(1) PAA_ALIGN_REC(2) PAA_ALIGN_REC(4) PAA_ALIGN_REC(6) PAA_ALIGN_REC(8) PAA_ALIGN_REC(16) }
+#undef PAA_ALIGN_REC
+    PAA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_align_hinge, dim3(cdiv(dlogits ? Tpad : T, 4), B), dim3(256), 0, st, logits, T, Tpad, V, kappa, grad_scale,
+                       dlogits, dlb, work, wpc, frames);
+    PAA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_align_loss, dim3(B), dim3(256), 0, st, T, loss, (const float*)work, wpc, frames);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
 __global__ void k_sum_small(const float* __restrict__ x, int n, float* __restrict__ out) {
     __shared__ double red[256 / 64];
     double s = 0.0;
@@ -1700,4 +1945,16 @@ extern "C" paa_status paa_ctc_padded(const float* logits, const int32_t* labels,
     if (Tpad < T) PAA_FAIL(PAA_ERR_SIZE, "paa_ctc_padded: Tpad=%d < T=%d", Tpad, T);
     if ((dlb_hi || dlb_lo) && (!dlogits || !dlb_hi)) PAA_FAIL(PAA_ERR_ARG, "paa_ctc_padded: planes need dlogits and a hi plane");
     return ctc(logits, labels, B, T, Tpad, V, S_max, blank, grad_scale, nll, dlogits, planes(dlb_hi, dlb_lo, 0), work, (hipStream_t)stream);
+}
+// Forced alignment + alignment-margin loss (include/paa_hip.h)
+extern "C" int64_t paa_align_margin_work_floats(int B, int T, int V, int S_max) {
+    (void)V; (void)S_max;
+    return B < 1 || T < 1 ? 0 : (int64_t)B * align_margin_work_floats_per_clip(T);
+}
+extern "C" paa_status paa_align_margin(const float* logits, const int32_t* labels, const int32_t* d_frames, int B, int T, int Tpad, int V,
+                                       int S_max, int blank, float kappa, float grad_scale, float* loss, int16_t* align, float* dlogits,
+                                       void* dlb_hi, void* dlb_lo, float* work, void* stream) {
+    if ((dlb_hi || dlb_lo) && (!dlogits || !dlb_hi)) PAA_FAIL(PAA_ERR_ARG, "paa_align_margin: planes need dlogits and a hi plane");
+    return align_margin(logits, labels, d_frames, B, T, Tpad, V, S_max, blank, kappa, grad_scale, loss, align, dlogits,
+                        planes(dlb_hi, dlb_lo, 0), work, (hipStream_t)stream);
 }

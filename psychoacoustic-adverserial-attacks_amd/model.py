@@ -198,6 +198,7 @@ class PaaModel:
         self._lengths = None          # persistent int32 (max_batch) buffer of set_lengths; allocated on first use
         self._len_slots, self._len_events, self._len_i = None, None, 0      # pinned host slots behind its asynchronous copies
         self.lengths_on = False
+        self.loss_kind, self.loss_kappa = 0, 0.0      # set_loss
 
     @classmethod
     def from_hf(cls, hf_model, max_batch, length, dtype="bf16", device="cuda"):
@@ -252,6 +253,18 @@ class PaaModel:
         self._len_events[k] = ev
         return self._lengths
 
+    LOSS_KINDS = {"ctc": 0, "margin": 1}
+
+    def set_loss(self, kind, kappa=0.0):
+        """The loss of every later ``fwd_bwd`` call: kind 0 / "ctc" = CTC (the default), 1 / "margin" = the
+        alignment-margin loss with margin ``kappa`` in logits.  ``forward`` keeps reporting CTC.  Like ``set_lengths`` it changes
+        what later calls launch, so a captured graph keeps the loss it was captured with."""
+        k = self.LOSS_KINDS.get(kind, kind)
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise ValueError(f"loss kind must be one of {list(self.LOSS_KINDS)} or 0 / 1, got {kind!r}")
+        _lib.check(_lib.lib().paa_model_set_loss(self.h, k, float(kappa)))
+        self.loss_kind, self.loss_kappa = k, float(kappa) if k else 0.0
+
     def frame_counts(self, B):
         """T_b of the current length buffer for the first B clips, as an int32 device tensor."""
         out = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -288,7 +301,8 @@ class PaaModel:
     def fwd_bwd(self, clean, p, labels, direction=+1, want_grad=True, want_logits=True, out=None):
         """clean (B, L) f32 cuda; p (1, L), (L,), (B, L) (one row per clip) or None; labels (B, S) integer tensor,
         negatives = padding.  Returns dict(loss=0-d tensor, logits=(B, T_e, V) | None, grad=(1, L) | (B, L) | None,
-        stats=(8,)); with a per-clip p the gradient has one row per clip (no sum over the clips)."""
+        stats=(8,)); with a per-clip p the gradient has one row per clip (no sum over the clips).  ``loss`` is the CTC loss, or the
+        alignment-margin loss after ``set_loss("margin", kappa)``."""
         clean, p, p_rows = self._checked(clean, p)
         B, L = clean.shape
         dev = self.device

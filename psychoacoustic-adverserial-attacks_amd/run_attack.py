@@ -3,6 +3,10 @@ evaluation, best tracking :151-167, StepLR :170-178, early stopping :181-183, fi
 report :265-279) with its eight defects fixed, on the HIP path.
 
     python -m paa_amd.run_attack --optimizer_type pgd --norm_type snr --snr_db 40 [--model_path DIR] [--data_dir DIR]
+
+With ``--loss_type margin`` (targeted attacks) the training step optimises the alignment-margin loss: the ``ctc`` field
+of the training scores (``train_ctc``, ``train_score`` / ``best_train_score`` in results.json) then holds the margin loss.  The
+evaluation scores stay CTC, so runs of either loss type compare.
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ def main(args) -> int:
     place.check_flags(args)
     rir.check_flags(args)
     channel.check_flags(args)
+    modes.check(m, modes.MARGIN)
     mask_alpha = modes.check(m, modes.LENGTHS).alpha
     build.start_process_group(args, world)
     if world > 1 and rank != 0:

@@ -47,6 +47,9 @@ class Modes:
     optimizer_type: str
     drift_ppm: float = 0.0         # --drift_ppm
     noise_snr: tuple = None        # --noise_snr_db (LO, HI), or None
+    loss_type: str = "ctc"         # --loss_type: "ctc" or "margin" (the alignment-margin loss)
+    kappa: float = 1.0             # --margin_kappa, in logits
+    targeted: bool = False         # --attack_mode targeted
     search_on: bool = False        # --bound_search other than "off" (attack_clips only)
 
     @classmethod
@@ -60,7 +63,8 @@ class Modes:
         return cls(norms, "masking" in norms, alpha, on, shift, gain, str(get("rir_bank", "none")) != "none",
                    str(get("clip_lengths", "padded")) == "true", bool(get("device_wer", False)), get("optimizer_type", None),
                    drift_ppm=_num(get("drift_ppm", 0.0) or 0.0), noise_snr=_pair(get("noise_snr_db", None)),
-                   search_on=str(get("bound_search", "off")) != "off")
+                   search_on=str(get("bound_search", "off")) != "off", loss_type=str(get("loss_type", "ctc")),
+                   kappa=_num(get("margin_kappa", 1.0)), targeted=str(get("attack_mode", "untargeted")) == "targeted")
 
     drift_on = property(lambda m: isinstance(m.drift_ppm, float) and m.drift_ppm > 0)
     noise_on = property(lambda m: m.noise_snr is not None)
@@ -68,6 +72,7 @@ class Modes:
     shift_on = property(lambda m: m.place_shift == "random")
     masking = property(lambda m: m.masking_norm or m.alpha > 0)      # either pairs delta's frames with the clean clip's
     chan_why = property(lambda m: _chan_bad(m))
+    margin_on = property(lambda m: m.loss_type == "margin")
 
 
 SIZED_NORMS = ("l2", "linf", "snr", "tv", "fletcher_munson", "max_phon")      # the norms a bound scale tightens (min_max_freqs has no size)
@@ -160,6 +165,13 @@ RULES = {
                            _SEARCH + "needs a norm with a size to shrink; {m.norms} has none"),
     "search_route": Rule("search_on", lambda m, c: c.wer_why is not None, NIE,
                          _SEARCH + "decides success from the on-device WER counters, which are not available: {c.wer_why}"),
+    # the alignment-margin loss
+    "margin_untargeted": Rule("margin_on", lambda m, c: not m.targeted, ValueError,
+                              "--loss_type margin needs --attack_mode targeted: the hinge is flat wherever the aligned class already "
+                              "wins, so it is no untargeted objective"),
+    "margin_kappa": Rule("margin_on", lambda m, c: not (isinstance(m.kappa, (int, float)) and not isinstance(m.kappa, bool)
+                                                        and 0.0 <= m.kappa < float("inf")), ValueError,
+                         "margin_kappa must be finite and >= 0, got {m.kappa}"),
 }
 
 PLACE_FLAGS = ("shift_range", "gain_range", "place_masking")
@@ -169,6 +181,7 @@ CHANNEL_FLAGS = ("chan_range", "chan_masking")
 CHANNEL = CHANNEL_FLAGS + ("chan_eager",)
 LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir", "len_chan")
 SEARCH_FLAGS = ("search_range", "search_masking", "search_no_size")       # known from the flags alone
+MARGIN = ("margin_untargeted", "margin_kappa")                            # known from the flags alone
 SEARCH = SEARCH_FLAGS + ("search_route",)                                  # ... and once the vocabulary and the references are known
 
 

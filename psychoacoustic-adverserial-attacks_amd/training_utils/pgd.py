@@ -26,6 +26,9 @@
     the placement launches too, likewise)      paa_noise_add (noise only: two launches)                   last before the forward pass
                                                paa_drift_apply (adjoint; drift only)                      right before paa_place_reduce
 
+    margin loss (``loss_type`` = "margin",     inside paa_model_fwd_bwd{,_rows}: the alignment-margin      DESIGN.md §6l
+    targeted only)                             sequence (paa_align_margin) in place of CTC; slot 0 of the
+                                               stats then holds the margin loss
     true clip lengths (``lengths=`` /          inside paa_model_fwd_bwd{,_rows}: frame counts, zeroed      DESIGN.md §6h
     ``set_lengths``)                           frames, masked compose / attention / CTC
                                                paa_model_frame_counts, paa_argmax_ids_len                 in place of paa_argmax_ids (device WER)
@@ -177,7 +180,7 @@ class _StepperCore:
     def __init__(self, model, args, length, interp, spl_thresh, optimizer, device_wer, canon, r_cap, log_cap, proj_rows, proj_len):
         self.model, self.args, self.L = model, args, int(length)
         self.dev = model.device
-        self.modes = Modes.of(args)
+        self.modes = modes.check(Modes.of(args), modes.MARGIN)
         self.norms = list(self.modes.norms)
         for n in self.norms:
             if n not in _lib.NORM_IDS:
@@ -200,7 +203,18 @@ class _StepperCore:
         self._ring = _HostRing(4, self.dev) if (self.collective or optimizer is not None) else None
         self._init_masking_loss()
         self._init_device_wer(device_wer, canon, r_cap, log_cap)
+        self._apply_loss()
         self._lengths_captured = None        # capture() records whether the captured launch sequence runs in the length mode
+
+    # ---- the loss of the step -------------------------------------------------------------------------
+    def _apply_loss(self):
+        """``--loss_type`` / ``--margin_kappa`` of ``args`` go to the model (``PaaModel.set_loss``; a host-side switch read by every
+        later ``fwd_bwd``).  Steppers of different loss types may share a model: every eager step sets its own; a captured graph
+        keeps the launches it was captured with.  A model that never saw the margin loss is not touched."""
+        kind = 1 if self.modes.margin_on else 0
+        kappa = float(self.modes.kappa) if kind else 0.0
+        if (getattr(self.model, "loss_kind", 0), getattr(self.model, "loss_kappa", 0.0)) != (kind, kappa):
+            self.model.set_loss(kind, kappa)
 
     # ---- true clip lengths ------------------------------------------------------------------------------------------
     @property
@@ -335,6 +349,7 @@ class _StepperCore:
         """Host side of one step, before its launches (eager step, single-graph replay and _SplitGraph.replay alike): this
         rank's WER counters of the previous step go behind the gradient, and for Adam the step count is advanced and the
         step's scalars go to ``adam_scal``.  ``consts``: the (w1, beta2, omb2, eps) a graph captured by value."""
+        self._apply_loss()
         if self._ring is None:
             return
         with self._ring.slot() as h:
