@@ -230,11 +230,20 @@ paa_status paa_compose_clamp_rows(const float* d_clean, const float* d_p, int p_
  * G (B, L) is what paa_model_fwd_bwd_rows writes for d_p = rows.  No entry uses atomics: two calls give the same bits.  Null
  * pointers (except where stated), B < 1, L < 1 or Lp < 1: PAA_ERR_ARG, before any launch.
  *
- * paa_place_draw: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) with key
- * (seed & 0xffffffff, seed >> 32) and counter (step, clip_base + b, stream_id, 0), step = *d_counter read on the device.  With
- * outputs r0..r3: d_shift[b] = (r0 * Lp) >> 32 (64-bit product; 0 when shift_on = 0); u = (r1 >> 8) * 2^-24,
- * d_gain[b] = exp2f(fmaf(u, 2 gain_db, -gain_db) * (log2(10) / 20)), exactly 1.0f for gain_db = 0.  Then *d_counter = step + 1 ON
- * THE DEVICE (one thread, after every draw has read step), so a captured graph draws anew on every replay.  One launch.
+ * THE STREAM TABLE of the playback chain (placement, room responses §6g, the channel §6k; csrc/philox.h).  Every
+ * random number is a word of Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) under
+ * (k0, k1) = (seed & 0xffffffff, seed >> 32), with clip = clip_base + b:
+ *     stream                            key                        counter (word 0, 1, 2, 3)
+ *     placement draw  (paa_place_draw)  (k0, k1)                   (step, clip, stream_id, 0)
+ *     room draw       (paa_rir_draw)    (k0, k1)                   (step, clip, stream_id, 1)
+ *     channel draw    (paa_chan_draw)   (k0, k1)                   (step, clip, stream_id, 2)
+ *     noise samples   (paa_noise_add)   (k0, k1 ^ 0x6E6F6973)      (step, clip, i >> 2,    stream_id)
+ * The draws differ in word 3, the noise from all of them in the key: no (counter, key) pair of one stream is another's.  A draw is
+ * ONE block: step = *d_counter read on the device, then *d_counter = step + 1 ON THE DEVICE (one thread, after every clip has
+ * read step), so a captured graph draws anew on every replay.
+ *
+ * paa_place_draw: the placement stream.  With outputs r0..r3: d_shift[b] = (r0 * Lp) >> 32 (64-bit product; 0 when shift_on = 0);
+ * u = (r1 >> 8) * 2^-24, d_gain[b] = exp2f(fmaf(u, 2 gain_db, -gain_db) * (log2(10) / 20)), exactly 1.0f for gain_db = 0.
  * gain_db outside [0, 20]: PAA_ERR_ARG.  stream_id: 0 = training, 1 = evaluation (by convention of the callers). */
 paa_status paa_place_draw(uint64_t seed, int32_t* d_counter, int stream_id, int clip_base, int B, int Lp, int shift_on,
                           float gain_db, int32_t* d_shift, float* d_gain, void* stream);
@@ -256,10 +265,9 @@ paa_status paa_place_reduce(const float* d_grad_rows, const int32_t* d_shift, co
  * Both entries are asynchronous on the stream, allocate nothing, are capturable and use no atomics: two calls give the same bits.
  * They are additions to ABI 350: a binding that does not know them loses nothing.
  *
- * paa_rir_draw: Philox4x32-10 as paa_place_draw, the same key, counter (step, clip_base + b, stream_id, 1) — word 3 = 1 keeps the
- * draw disjoint from placement's, which uses 0.  d_index[b] = (r0 * N) >> 32.  step = *d_counter, a counter of the room draw's
- * own (placement's is not advanced under explicit placements); *d_counter = step + 1 on the device, by one thread, after every
- * clip has read it.  One block.  Null pointers, B < 1 or N < 1: PAA_ERR_ARG. */
+ * paa_rir_draw: the room stream of the stream table (above, at paa_place_draw).  d_index[b] = (r0 * N) >> 32.  d_counter is a
+ * counter of the room draw's own (placement's is not advanced under explicit placements).  Null pointers, B < 1 or N < 1:
+ * PAA_ERR_ARG. */
 #define PAA_RIR_MAX_TAPS 16384
 paa_status paa_rir_draw(uint64_t seed, int32_t* d_counter, int stream_id, int clip_base, int B, int N, int32_t* d_index,
                         void* stream);
@@ -283,13 +291,11 @@ paa_status paa_rir_apply(const float* d_bank, int N, int K, const int32_t* d_ind
  * All three entries are asynchronous on the stream, allocate nothing, are capturable and use no atomics: two calls on the same
  * inputs (and, for the noise, the same counter value) give the same bits.  They are additions to ABI 350.
  *
- * paa_chan_draw: Philox4x32-10 as paa_place_draw, the same key, counter (step, clip_base + b, stream_id, 2) — word 3 = 2 keeps
- * the draw disjoint from placement's (0) and the rooms' (1).  With outputs r0, r1:
+ * paa_chan_draw: the channel stream of the stream table (at paa_place_draw).  With outputs r0, r1:
  *   d_rq[b]     = 2^32 + ((((int64) r0 - 2^31) * drift_q32) >> 31)     (integers only, arithmetic shift; within 2^32 +- drift_q32)
  *   d_snr_db[b] = fmaf((r1 >> 8) * 2^-24, snr_hi_db - snr_lo_db, snr_lo_db)
- * step = *d_counter; *d_counter = step + 1 on the device, by one thread, after every clip has read it.  One block.  drift_q32 =
- * round(drift_ppm * 1e-6 * 2^32), computed by the caller.  Null pointers, B < 1, drift_q32 > 2^31, snr_lo_db > snr_hi_db or
- * either beyond +-1000: PAA_ERR_ARG. */
+ * d_counter is a counter of the channel draw's own.  drift_q32 = round(drift_ppm * 1e-6 * 2^32), computed by the caller.  Null
+ * pointers, B < 1, drift_q32 > 2^31, snr_lo_db > snr_hi_db or either beyond +-1000: PAA_ERR_ARG. */
 paa_status paa_chan_draw(uint64_t seed, int32_t* d_counter, int stream_id, int clip_base, int B, uint32_t drift_q32,
                          float snr_lo_db, float snr_hi_db, uint64_t* d_rq /* (B) */, float* d_snr_db /* (B) */, void* stream);
 /* d_in (B, L) -> d_out (B, L), WRITTEN; they must not overlap.  Null pointers, B < 1, L < 1 or overlapping buffers: PAA_ERR_ARG
@@ -299,8 +305,8 @@ paa_status paa_chan_draw(uint64_t seed, int32_t* d_counter, int stream_id, int c
  * ascending i and rounded once; every output is owned by one thread. */
 paa_status paa_drift_apply(const uint64_t* d_rq, const float* d_in, float* d_out, int B, int L, int adjoint, void* stream);
 /* In place on d_rows (B, L).  Two launches: d_sigma[b] (a workspace of B floats, and an output) from d_clean (B, L) and
- * d_snr_db (B), then the add.  The samples: Philox4x32-10 with key (seed & 0xffffffff, (seed >> 32) ^ 0x6E6F6973) — another key
- * than every draw's — and counter (step, clip_base + b, i >> 2, stream_id); the word pair (r[2p], r[2p+1]), p = (i & 3) >> 1, gives
+ * d_snr_db (B), then the add.  The samples: the noise stream of the stream table (at paa_place_draw); the word pair
+ * (r[2p], r[2p+1]), p = (i & 3) >> 1, of the block of group i >> 2 gives
  *   u1 = ((r[2p] >> 8) + 1) * 2^-24,  u2 = (r[2p+1] >> 8) * 2^-24,  z = sqrt(-2 ln u1) * (cos(2 pi u2) for even i, sin for odd i).
  * step = *d_counter, a counter of the noise's own: the first launch advances it (one block, after reading it) and the second
  * reads it back as *d_counter - 1.  A clip with sigma = 0 keeps its rows' bits.  Null pointers, B < 1 or L < 1: PAA_ERR_ARG. */

@@ -16,45 +16,24 @@
 // completely, are served by the cache.
 //
 // Noise (paa_noise_add).  rows[b][i] += sigma_b * z_{b,i}, sigma_b = sqrt(mean_i clean[b][i]^2) * 10^(-snr_b / 20) (f64 sum in a
-// fixed order), z a standard normal by Box-Muller on Philox4x32-10: counter (step, clip_base + b, i >> 2, stream_id), key
-// (seed & 0xffffffff, (seed >> 32) ^ NOISE_KEY).  The other draws (placement, rooms, paa_chan_draw) use the plain key, so no
-// (counter, key) pair of the noise can meet one of theirs.  Word pair (c[2p], c[2p+1]), p = (i & 3) >> 1, gives
+// fixed order), z a standard normal by Box-Muller on the noise stream of philox.h (its stream table; normal_pair).  Word pair
+// (c[2p], c[2p+1]), p = (i & 3) >> 1, of the block of group i >> 2 gives
 //     u1 = ((c[2p] >> 8) + 1) * 2^-24 in (0, 1],  u2 = (c[2p+1] >> 8) * 2^-24 in [0, 1),  rad = sqrt(-2 ln u1)
 //     z = rad * cos(2 pi u2) for even i, rad * sin(2 pi u2) for odd i.
 //
-// Draw (paa_chan_draw).  Counter (step, clip_base + b, stream_id, 2) under the plain key (placement draws with word 3 = 0, rooms
-// with 1):  rq_b = 2^32 + ((((int64) c0 - 2^31) * D) >> 31)  (pure integers),  snr_b = fmaf((c1 >> 8) * 2^-24, hi - lo, lo).
+// Draw (paa_chan_draw).  The channel stream of philox.h:  rq_b = 2^32 + ((((int64) c0 - 2^31) * D) >> 31)  (pure integers, draw_rq),
+// snr_b = fmaf((c1 >> 8) * 2^-24, hi - lo, lo)  (draw_snr).
 #include "paa_common.h"
+#include "philox.h"
 
 using namespace paa;
 
 namespace {
 
-constexpr int CHAN_NT = 256;            // threads per block, every kernel here
+constexpr int CHAN_NT = 256;            // threads per block of the drift and the noise kernels
 constexpr int DRIFT_PER_THREAD = 4;     // outputs per thread of both drift directions: a block covers 1024 consecutive samples
 constexpr int DRIFT_T = 8;              // half width of the window: taps t = -T+1 .. T
-constexpr uint32_t NOISE_KEY = 0x6E6F6973u;      // "nois": XORed into the key's second word for the noise samples
 constexpr uint64_t RQ_MIN = 1ull << 31, RQ_MAX = 1ull << 33;
-
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-// Philox4x32-10, as place_kernels.hip
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
 
 __device__ __forceinline__ uint64_t clamp_rq(uint64_t rq) { return rq < RQ_MIN ? RQ_MIN : (rq > RQ_MAX ? RQ_MAX : rq); }
 
@@ -142,20 +121,13 @@ __global__ void __launch_bounds__(CHAN_NT) k_drift_adjoint(const uint64_t* __res
     }
 }
 
-__global__ void __launch_bounds__(CHAN_NT) k_chan_draw(uint32_t k0, uint32_t k1, int32_t* __restrict__ counter, int stream_id,
+__global__ void __launch_bounds__(DRAW_NT) k_chan_draw(uint32_t k0, uint32_t k1, int32_t* __restrict__ counter, int stream_id,
                                                        int clip_base, int B, uint32_t drift_q32, float snr_lo, float snr_hi,
                                                        uint64_t* __restrict__ rq, float* __restrict__ snr) {
-    const uint32_t step = (uint32_t)*counter;
-    for (int b = threadIdx.x; b < B; b += CHAN_NT) {
-        uint32_t c[4] = {step, (uint32_t)(clip_base + b), (uint32_t)stream_id, 2u};      // word 3: placement 0, rooms 1
-        philox4x32_10(c, k0, k1);
-        const int64_t d = (((int64_t)c[0] - ((int64_t)1 << 31)) * (int64_t)drift_q32) >> 31;      // arithmetic shift: floor
-        rq[b] = (uint64_t)(((int64_t)1 << 32) + d);
-        const float u = (float)(c[1] >> 8) * 0x1p-24f;                   // 24 bits: exact in f32, u in [0, 1)
-        snr[b] = fmaf(u, snr_hi - snr_lo, snr_lo);
-    }
-    __syncthreads();                          // every thread has read the counter
-    if (threadIdx.x == 0) *counter = (int32_t)(step + 1u);
+    draw_clips(k0, k1, counter, stream_id, clip_base, B, TAG_CHAN, [=](int b, const uint32_t (&c)[4]) {
+        rq[b] = draw_rq(c[0], drift_q32);
+        snr[b] = draw_snr(c[1], snr_lo, snr_hi);
+    });
 }
 
 // one block per clip: sigma_b.  The per-thread partial sums (i = tid, tid + 256, ...) and their reduction have a fixed order.
@@ -191,17 +163,17 @@ __global__ void __launch_bounds__(CHAN_NT) k_noise_add(uint32_t k0, uint32_t k1,
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
         const float sg = sigma[b];
         if (sg == 0.0f) continue;                                        // a silent clip: its rows keep their bits
-        uint32_t c[4] = {step, (uint32_t)(clip_base + b), (uint32_t)grp, (uint32_t)stream_id};
-        philox4x32_10(c, k0, k1 ^ NOISE_KEY);
+        uint32_t c[4];
+        noise_counter(c, step, (uint32_t)(clip_base + b), (uint32_t)grp, (uint32_t)stream_id);
+        philox4x32_10(c, k0, noise_k1(k1));
         float* __restrict__ y = rows + (int64_t)b * L + i0;
         const int m = (int)min((int64_t)4, (int64_t)L - i0);
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            const float u1 = (float)((c[2 * p] >> 8) + 1u) * 0x1p-24f;   // (0, 1]
-            const float u2 = (float)(c[2 * p + 1] >> 8) * 0x1p-24f;      // [0, 1)
-            const float rad = sqrtf(-2.0f * logf(u1));
-            if (2 * p < m) y[2 * p] = fmaf(sg, rad * cospif(2.0f * u2), y[2 * p]);
-            if (2 * p + 1 < m) y[2 * p + 1] = fmaf(sg, rad * sinpif(2.0f * u2), y[2 * p + 1]);
+            float z_even, z_odd;
+            normal_pair(c[2 * p], c[2 * p + 1], z_even, z_odd);
+            if (2 * p < m) y[2 * p] = fmaf(sg, z_even, y[2 * p]);
+            if (2 * p + 1 < m) y[2 * p + 1] = fmaf(sg, z_odd, y[2 * p + 1]);
         }
     }
 }
@@ -215,8 +187,9 @@ extern "C" paa_status paa_chan_draw(uint64_t seed, int32_t* d_counter, int strea
     if (drift_q32 > (1u << 31)) PAA_FAIL(PAA_ERR_ARG, "paa_chan_draw: drift_q32=%u above 2^31", drift_q32);
     if (!(snr_lo_db <= snr_hi_db) || !(fabsf(snr_lo_db) <= 1000.0f) || !(fabsf(snr_hi_db) <= 1000.0f))
         PAA_FAIL(PAA_ERR_ARG, "paa_chan_draw: snr range [%g, %g] dB", (double)snr_lo_db, (double)snr_hi_db);
-    hipLaunchKernelGGL(k_chan_draw, dim3(1), dim3(CHAN_NT), 0, (hipStream_t)stream, (uint32_t)(seed & 0xffffffffu),
-                       (uint32_t)(seed >> 32), d_counter, stream_id, clip_base, B, drift_q32, snr_lo_db, snr_hi_db, d_rq, d_snr_db);
+    const PhiloxKey k = key_of(seed);
+    hipLaunchKernelGGL(k_chan_draw, dim3(1), dim3(DRAW_NT), 0, (hipStream_t)stream, k.k0, k.k1, d_counter, stream_id, clip_base, B,
+                       drift_q32, snr_lo_db, snr_hi_db, d_rq, d_snr_db);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }
@@ -227,7 +200,7 @@ extern "C" paa_status paa_drift_apply(const uint64_t* d_rq, const float* d_in, f
     if (B < 1 || L < 1) PAA_FAIL(PAA_ERR_ARG, "paa_drift_apply: B=%d L=%d (>= 1 each)", B, L);
     const uintptr_t i0 = (uintptr_t)d_in, o0 = (uintptr_t)d_out, bytes = (uintptr_t)B * (uintptr_t)L * sizeof(float);
     if (i0 < o0 + bytes && o0 < i0 + bytes) PAA_FAIL(PAA_ERR_ARG, "paa_drift_apply: d_in and d_out overlap");
-    const dim3 grid(cdiv(L, CHAN_NT * DRIFT_PER_THREAD), B < 65535 ? B : 65535);
+    const dim3 grid = clips_grid(cdiv(L, CHAN_NT * DRIFT_PER_THREAD), B);
     if (adjoint)
         hipLaunchKernelGGL(k_drift_adjoint, grid, dim3(CHAN_NT), 0, (hipStream_t)stream, d_rq, d_in, d_out, B, L);
     else
@@ -242,9 +215,9 @@ extern "C" paa_status paa_noise_add(uint64_t seed, int32_t* d_counter, int strea
     if (B < 1 || L < 1) PAA_FAIL(PAA_ERR_ARG, "paa_noise_add: B=%d L=%d (>= 1 each)", B, L);
     hipLaunchKernelGGL(k_noise_sigma, dim3(B), dim3(CHAN_NT), 0, (hipStream_t)stream, d_counter, d_clean, d_snr_db, d_sigma, B, L);
     PAA_LAUNCH_CHECK();
-    const dim3 grid(cdiv(cdiv(L, 4), CHAN_NT), B < 65535 ? B : 65535);
-    hipLaunchKernelGGL(k_noise_add, grid, dim3(CHAN_NT), 0, (hipStream_t)stream, (uint32_t)(seed & 0xffffffffu),
-                       (uint32_t)(seed >> 32), d_counter, stream_id, clip_base, d_sigma, d_rows, B, L);
+    const PhiloxKey k = key_of(seed);
+    hipLaunchKernelGGL(k_noise_add, clips_grid(cdiv(cdiv(L, 4), CHAN_NT), B), dim3(CHAN_NT), 0, (hipStream_t)stream, k.k0, k.k1,
+                       d_counter, stream_id, clip_base, d_sigma, d_rows, B, L);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }

@@ -40,6 +40,9 @@ void set_error(const std::string& msg);
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// grid (tiles along a row, clips): gridDim.y stops at 65535, and a kernel launched on it strides b over the clips by gridDim.y
+static inline dim3 clips_grid(int tiles, int B) { return dim3(tiles, B < 65535 ? B : 65535); }
+
 // Compute units of the CURRENT device, cached per device id (a process may drive several devices, and a partitioned part
 // reports fewer CUs than the 256 of a whole MI355X).
 inline int device_cus() {

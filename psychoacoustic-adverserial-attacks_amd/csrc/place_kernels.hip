@@ -2,18 +2,19 @@
 // and a gain a_b,
 //     rows[b][i] = a_b * delta[(i + s_b) mod Lp]                                   (paa_place_rows, gather only)
 //     grad[j]    = sum_b a_b * sum_{i < L, (i + s_b) mod Lp = j} G[b][i]           (paa_place_reduce, its adjoint)
-// and the draw of (s_b, a_b) from Philox4x32-10 with the step counter in device memory (paa_place_draw), so that a captured
-// graph draws anew on every replay.  All three are memory-bound: the gather reads delta (Lp floats, cache-resident) and writes
+// and the draw of (s_b, a_b) from the placement stream of philox.h with the step counter in device memory (paa_place_draw), so that
+// a captured graph draws anew on every replay.  All three are memory-bound: the gather reads delta (Lp floats, cache-resident) and writes
 // B * L floats once; the reduce reads B * L floats once, every output owned by one thread (no atomics, f64 sums in a fixed
 // order: two calls give the same bits).  No integer division per element: a thread resolves its start once and wraps by
 // compare-and-subtract.
 #include "paa_common.h"
+#include "philox.h"
 
 using namespace paa;
 
 namespace {
 
-constexpr int PLACE_NT = 256;          // threads per block, all three kernels
+constexpr int PLACE_NT = 256;          // threads per block of the gather and the reduce
 constexpr int ROWS_PER_THREAD = 8;     // outputs per thread of the gather: a block covers 2048 consecutive samples of one row
 constexpr int REDUCE_CLIPS = 256;      // clips whose (shift, gain) a block of the reduce stages in LDS at a time
 
@@ -23,40 +24,13 @@ __device__ __forceinline__ int wrap_shift(int s, int Lp) {
     return r < 0 ? r + Lp : r;
 }
 
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-// Philox4x32-10 (Salmon et al. 2011): ten rounds, the key bumped by the Weyl constants between them
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
-__global__ void __launch_bounds__(PLACE_NT) k_place_draw(uint32_t k0, uint32_t k1, int32_t* __restrict__ counter, int stream_id,
-                                                         int clip_base, int B, int Lp, int shift_on, float gain_db,
-                                                         int32_t* __restrict__ shift, float* __restrict__ gain) {
-    const uint32_t step = (uint32_t)*counter;
-    for (int b = threadIdx.x; b < B; b += PLACE_NT) {
-        uint32_t c[4] = {step, (uint32_t)(clip_base + b), (uint32_t)stream_id, 0u};
-        philox4x32_10(c, k0, k1);
-        shift[b] = shift_on ? (int32_t)(((uint64_t)c[0] * (uint64_t)(uint32_t)Lp) >> 32) : 0;
-        const float u = (float)(c[1] >> 8) * 0x1p-24f;                       // 24 bits: exact in f32, u in [0, 1)
-        const float db = fmaf(u, 2.0f * gain_db, -gain_db);
-        gain[b] = exp2f(db * 0.16609640474436813f);                          // log2(10) / 20; gain_db = 0 -> exactly 1.0f
-    }
-    __syncthreads();                          // every thread has read the counter
-    if (threadIdx.x == 0) *counter = (int32_t)(step + 1u);
+__global__ void __launch_bounds__(DRAW_NT) k_place_draw(uint32_t k0, uint32_t k1, int32_t* __restrict__ counter, int stream_id,
+                                                        int clip_base, int B, int Lp, int shift_on, float gain_db,
+                                                        int32_t* __restrict__ shift, float* __restrict__ gain) {
+    draw_clips(k0, k1, counter, stream_id, clip_base, B, TAG_PLACE, [=](int b, const uint32_t (&c)[4]) {
+        shift[b] = shift_on ? draw_below(c[0], Lp) : 0;
+        gain[b] = draw_gain(c[1], gain_db);
+    });
 }
 
 // grid (tiles of PLACE_NT * ROWS_PER_THREAD samples, clips); thread t of a tile writes samples tile0 + t + k * PLACE_NT
@@ -122,8 +96,9 @@ extern "C" paa_status paa_place_draw(uint64_t seed, int32_t* d_counter, int stre
     if (!d_counter || !d_shift || !d_gain) PAA_FAIL(PAA_ERR_ARG, "paa_place_draw: null argument");
     if (B < 1 || Lp < 1) PAA_FAIL(PAA_ERR_ARG, "paa_place_draw: B=%d Lp=%d (>= 1 each)", B, Lp);
     if (!(gain_db >= 0.0f && gain_db <= 20.0f)) PAA_FAIL(PAA_ERR_ARG, "paa_place_draw: gain_db=%g outside [0, 20]", (double)gain_db);
-    hipLaunchKernelGGL(k_place_draw, dim3(1), dim3(PLACE_NT), 0, (hipStream_t)stream, (uint32_t)(seed & 0xffffffffu),
-                       (uint32_t)(seed >> 32), d_counter, stream_id, clip_base, B, Lp, shift_on, gain_db, d_shift, d_gain);
+    const PhiloxKey k = key_of(seed);
+    hipLaunchKernelGGL(k_place_draw, dim3(1), dim3(DRAW_NT), 0, (hipStream_t)stream, k.k0, k.k1, d_counter, stream_id, clip_base, B,
+                       Lp, shift_on, gain_db, d_shift, d_gain);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }
@@ -132,7 +107,7 @@ extern "C" paa_status paa_place_rows(const float* d_p, int Lp, const int32_t* d_
                                      int L, void* stream) {
     if (!d_p || !d_shift || !d_rows) PAA_FAIL(PAA_ERR_ARG, "paa_place_rows: null argument");
     if (B < 1 || L < 1 || Lp < 1) PAA_FAIL(PAA_ERR_ARG, "paa_place_rows: B=%d L=%d Lp=%d (>= 1 each)", B, L, Lp);
-    const dim3 grid(cdiv(L, PLACE_NT * ROWS_PER_THREAD), B < 65535 ? B : 65535);
+    const dim3 grid = clips_grid(cdiv(L, PLACE_NT * ROWS_PER_THREAD), B);
     hipLaunchKernelGGL(k_place_rows, grid, dim3(PLACE_NT), 0, (hipStream_t)stream, d_p, Lp, d_shift, d_gain, d_rows, B, L);
     PAA_LAUNCH_CHECK();
     return PAA_OK;

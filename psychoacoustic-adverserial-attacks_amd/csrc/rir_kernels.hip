@@ -1,7 +1,7 @@
 // Room responses on the placement layer: clip b hears its row through the response h_c, c = index[b],
 //     out[b][i] = sum_{k=0}^{min(K-1, i)}     h_c[k] * in[b][i - k]          (paa_rir_apply, adjoint = 0: causal FIR, zero history)
 //     out[b][j] = sum_{k=0}^{min(K-1, L-1-j)} h_c[k] * in[b][j + k]          (adjoint = 1: its exact adjoint)
-// and the draw of c_b from Philox4x32-10 with a step counter of its own in device memory (paa_rir_draw).
+// and the draw of c_b from the room stream of philox.h with a step counter of its own in device memory (paa_rir_draw).
 //
 // The apply is a Toeplitz product on the f32-input MFMA (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain at the f32
 // vector peak).  A wave owns 32 x 32 output tiles Y[m][n] = y[base + 32 n + m] and sums over j = 0 .. K + 30 (zero-extended to K + 37 at most),
@@ -14,6 +14,7 @@
 // - 32 floats, one pad dword per 32 so that the 32-dword lane stride of the signal read hits 32 different banks).  Every output
 // has ONE accumulator chain, j ascending, whatever the grid: two calls give the same bits.  No atomics, no allocation.
 #include "paa_common.h"
+#include "philox.h"
 
 using namespace paa;
 
@@ -27,7 +28,6 @@ constexpr int RIR_UNROLL = 4;                             // MFMA steps (of two 
 constexpr int RIR_JC = 2080;                              // j steps per staged chunk (a multiple of 2 RIR_UNROLL): K = 4096 in two
 constexpr int RIR_XS = RIR_SPAN + RIR_JC - 32;            // signal samples a chunk needs
 constexpr int RIR_XS_PHYS = RIR_XS + RIR_XS / 32 + 1;     // with one pad dword per 32
-constexpr int RIR_DRAW_NT = 256;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -36,36 +36,10 @@ __device__ __forceinline__ int wrap_index(int c, int N) {
     return r < 0 ? r + N : r;
 }
 
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-// Philox4x32-10, as place_kernels.hip
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
-__global__ void __launch_bounds__(RIR_DRAW_NT) k_rir_draw(uint32_t k0, uint32_t k1, int32_t* __restrict__ counter, int stream_id,
-                                                          int clip_base, int B, int N, int32_t* __restrict__ index) {
-    const uint32_t step = (uint32_t)*counter;
-    for (int b = threadIdx.x; b < B; b += RIR_DRAW_NT) {
-        uint32_t c[4] = {step, (uint32_t)(clip_base + b), (uint32_t)stream_id, 1u};      // word 3: placement draws with 0
-        philox4x32_10(c, k0, k1);
-        index[b] = (int32_t)(((uint64_t)c[0] * (uint64_t)(uint32_t)N) >> 32);
-    }
-    __syncthreads();                          // every thread has read the counter
-    if (threadIdx.x == 0) *counter = (int32_t)(step + 1u);
+__global__ void __launch_bounds__(DRAW_NT) k_rir_draw(uint32_t k0, uint32_t k1, int32_t* __restrict__ counter, int stream_id,
+                                                      int clip_base, int B, int N, int32_t* __restrict__ index) {
+    draw_clips(k0, k1, counter, stream_id, clip_base, B, TAG_ROOM,
+               [=](int b, const uint32_t (&c)[4]) { index[b] = draw_below(c[0], N); });
 }
 
 // grid (spans of RIR_SPAN outputs, clips); wave w of a block owns the tiles at span0 + w * RIR_WAVE_SPAN + t * 1024
@@ -153,8 +127,9 @@ extern "C" paa_status paa_rir_draw(uint64_t seed, int32_t* d_counter, int stream
                                    void* stream) {
     if (!d_counter || !d_index) PAA_FAIL(PAA_ERR_ARG, "paa_rir_draw: null argument");
     if (B < 1 || N < 1) PAA_FAIL(PAA_ERR_ARG, "paa_rir_draw: B=%d N=%d (>= 1 each)", B, N);
-    hipLaunchKernelGGL(k_rir_draw, dim3(1), dim3(RIR_DRAW_NT), 0, (hipStream_t)stream, (uint32_t)(seed & 0xffffffffu),
-                       (uint32_t)(seed >> 32), d_counter, stream_id, clip_base, B, N, d_index);
+    const PhiloxKey k = key_of(seed);
+    hipLaunchKernelGGL(k_rir_draw, dim3(1), dim3(DRAW_NT), 0, (hipStream_t)stream, k.k0, k.k1, d_counter, stream_id, clip_base, B, N,
+                       d_index);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }
@@ -166,7 +141,7 @@ extern "C" paa_status paa_rir_apply(const float* d_bank, int N, int K, const int
     if (K < 1 || K > PAA_RIR_MAX_TAPS) PAA_FAIL(PAA_ERR_ARG, "paa_rir_apply: K=%d outside [1, %d]", K, PAA_RIR_MAX_TAPS);
     const uintptr_t i0 = (uintptr_t)d_in, o0 = (uintptr_t)d_out, bytes = (uintptr_t)B * (uintptr_t)L * sizeof(float);
     if (i0 < o0 + bytes && o0 < i0 + bytes) PAA_FAIL(PAA_ERR_ARG, "paa_rir_apply: d_in and d_out overlap");
-    const dim3 grid(cdiv(L, RIR_SPAN), B < 65535 ? B : 65535);
+    const dim3 grid = clips_grid(cdiv(L, RIR_SPAN), B);
     if (adjoint)
         hipLaunchKernelGGL(k_rir_apply<1>, grid, dim3(RIR_NT), 0, (hipStream_t)stream, d_bank, N, K, d_index, d_in, d_out, B, L);
     else

@@ -16,7 +16,7 @@ import sys
 import torch
 
 from .core import iso
-from .training_utils import build, channel, evaluation, modes, parser, place, rir, save, scoring_helpers, train
+from .training_utils import build, chain, evaluation, modes, parser, save, scoring_helpers, train
 
 
 def main(args) -> int:
@@ -29,9 +29,7 @@ def main(args) -> int:
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     # refusals before any collective, so that every rank raises
     m = modes.check(modes.Modes.of(args), ("route",), modes.Ctx(world))
-    place.check_flags(args)
-    rir.check_flags(args)
-    channel.check_flags(args)
+    chain.check_flags(args)
     modes.check(m, modes.MARGIN)
     mask_alpha = modes.check(m, modes.LENGTHS).alpha
     build.start_process_group(args, world)
@@ -57,9 +55,7 @@ def main(args) -> int:
     optimizer, scheduler = (build.create_optimizer(args, p) if args.optimizer_type == "adam" else (None, None))
     hist = {k: [] for k in ("train_ctc", "train_wer", "clean_ctc", "clean_wer", "pert_ctc", "pert_wer")}
     extra = {}          # results.json keys of the masking-threshold loss term: present only when masking_loss_alpha > 0
-    place_extra = place.results_extra(args, p.shape[-1])          # and those of placement, present only when it is on
-    place_extra.update(rir.results_extra(args))                   # and those of room responses, likewise
-    place_extra.update(channel.results_extra(args))               # and those of the playback channel
+    place_extra = chain.results_extra(args, p.shape[-1])          # and those of placement, room responses and the playback channel
     extra.update(place_extra)
     goal = scoring_helpers.Objective(args.attack_mode)      # targeted: perturbed WER down; untargeted: perturbed CTC up
     best_epoch, no_improve, best_eval = -1, 0, goal.worst

@@ -12,7 +12,7 @@ from .. import arch as A
 from .. import synth
 from ..core import iso
 from ..model import PaaModel
-from . import channel, place, rir
+from . import chain, place
 from .modes import Modes
 
 
@@ -180,7 +180,7 @@ def create_logger(args, logs_root=None):
     args.attack_size_string = attack_size_string(args)
     root = logs_root or getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}{place.suffix(args)}{rir.suffix(args)}{channel.suffix(args)}_"
+                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}{chain.suffix(args)}_"
                                  f"{args.attack_mode}_{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)
     logger = logging.getLogger("asr_attack")

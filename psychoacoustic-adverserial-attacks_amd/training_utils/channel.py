@@ -22,6 +22,7 @@ import torch
 from .. import _lib
 from . import modes
 from .modes import Ctx, Modes
+from .site import Site
 
 Q32 = 1 << 32
 RQ_MIN, RQ_MAX = 1 << 31, 1 << 33          # the device clamps a ratio to [0.5, 2]
@@ -74,17 +75,16 @@ def results_extra(args) -> dict:
     return out
 
 
-class Channel:
+class Channel(Site):
     """Fixed device buffers and the launches of one channel site (the training step, or one evaluation), beside ``place.Placer``
-    and ``rir.Reverb``.  ``draw`` -> (rq, snr_db) of the next step's clips (Philox counter (step, clip_base + b, stream_id, 2),
-    step read from and advanced in ``counter`` on the device); ``apply`` -> rows[:B] = the drifted input; ``adjoint`` ->
-    grad_rows[:B] = the transpose of ``apply`` on gradient rows; ``add_noise`` -> in place on the rows it is given, samples keyed
-    by (``noise_counter``, clip, sample), a counter of the noise's own."""
+    and ``rir.Reverb``.  ``draw`` -> (rq, snr_db) of the next step's clips (the channel stream of csrc/philox.h); ``apply`` ->
+    rows[:B] = the drifted input; ``adjoint`` -> grad_rows[:B] = the transpose of ``apply`` on gradient rows; ``add_noise`` -> in
+    place on the rows it is given, samples keyed by (``noise_counter``, clip, sample), a counter of the noise's own (the noise
+    stream); ``set_step`` sets both."""
 
     def __init__(self, dev, max_batch: int, L: int, seed: int, stream_id: int, drift_ppm: float = 0.0, noise_snr=None,
                  clip_base: int = 0, with_grad: bool = True):
-        self.dev, self.max_batch, self.L = dev, int(max_batch), int(L)
-        self.seed, self.stream_id, self.clip_base = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id), int(clip_base)
+        super().__init__(dev, max_batch, L, seed, stream_id, clip_base)
         m = modes.check(Modes.of(drift_ppm=drift_ppm, noise_snr_db=noise_snr), ("chan_range",))
         self.drift_on, self.noise_on = m.drift_on, m.noise_on
         self.D = drift_q32(m.drift_ppm)
@@ -92,28 +92,19 @@ class Channel:
         self.rq = torch.full((self.max_batch,), Q32, dtype=torch.int64, device=dev)          # the device reads it as uint64
         self.snr_db = torch.zeros(self.max_batch, dtype=torch.float32, device=dev)
         self.sigma = torch.zeros(self.max_batch, dtype=torch.float32, device=dev)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.noise_counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.rows = torch.zeros(self.max_batch, self.L, dtype=torch.float32, device=dev) if self.drift_on else None
-        self.grad_rows = torch.zeros(self.max_batch, self.L, dtype=torch.float32, device=dev) if self.drift_on and with_grad else None
-        self.explicit = False
+        self.rows = self._zeros() if self.drift_on else None
+        self.grad_rows = self._zeros() if self.drift_on and with_grad else None
 
-    def _fits(self, B):
-        if not 1 <= B <= self.max_batch:
-            raise ValueError(f"batch {B} outside [1, {self.max_batch}]")
-
-    def set_step(self, n: int):
-        """Step counter of the next draw and of the next noise (resume, tests); stream-ordered."""
-        self.counter.fill_(int(n))
-        self.noise_counter.fill_(int(n))
+    def counters(self):
+        return [self.counter, self.noise_counter]
 
     def set_channel(self, ratio, snr_db=None):
         """Pin explicit ratios (floats, or Q32 integers in an integer tensor / list of ints) and SNRs (default: what the buffer
         holds) for the clips of the following steps by a stream-ordered copy: the draw is skipped until ``set_channel(None)``.  The
         noise keeps its own counter and stays fresh.  Which of the two a captured graph holds is fixed by ``capture()``."""
         if ratio is None:
-            self.explicit = False
-            return
+            return self.unpin()
         r = ratio.reshape(-1).tolist() if isinstance(ratio, torch.Tensor) else list(ratio)          # Python floats: no float32 detour
         q = torch.tensor([int(x) if isinstance(x, int) else int(round(float(x) * float(Q32))) for x in r], dtype=torch.int64)
         self._fits(q.numel())
@@ -129,18 +120,17 @@ class Channel:
 
     def draw(self, B: int, clip_base=None):
         self._fits(B)
-        base = self.clip_base if clip_base is None else int(clip_base)
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().paa_chan_draw(self.seed, _lib.ptr(self.counter), self.stream_id, base, B, self.D, self.snr_lo,
-                                                self.snr_hi, _lib.ptr(self.rq), _lib.ptr(self.snr_db), _lib.stream_ptr()))
+            _lib.check(_lib.lib().paa_chan_draw(self.seed, _lib.ptr(self.counter), self.stream_id, self._base(clip_base), B, self.D,
+                                                self.snr_lo, self.snr_hi, _lib.ptr(self.rq), _lib.ptr(self.snr_db),
+                                                _lib.stream_ptr()))
 
     def _launch(self, src, dst, B, adjoint):
         self._fits(B)
         if dst is None:
             raise RuntimeError("the channel was built with drift off (drift_ppm)" if not self.drift_on else
                                "the channel was built without gradient rows")
-        if src.dtype != torch.float32 or not src.is_contiguous() or src.numel() < B * self.L:
-            raise ValueError(f"rows must be contiguous float32 with at least {B} x {self.L} elements")
+        self._check_rows(src, B)
         with torch.cuda.device(self.dev):
             _lib.check(_lib.lib().paa_drift_apply(_lib.ptr(self.rq), _lib.ptr(src), _lib.ptr(dst), B, self.L, adjoint,
                                                   _lib.stream_ptr()))
@@ -157,24 +147,13 @@ class Channel:
     def add_noise(self, rows, clean, B: int, clip_base=None):
         """rows[:B] += sigma_b z, in place; sigma from ``clean`` (B, L) and the SNRs of the last draw / ``set_channel``."""
         self._fits(B)
-        for t, name in ((rows, "rows"), (clean, "clean")):
-            if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < B * self.L:
-                raise ValueError(f"{name} must be contiguous float32 with at least {B} x {self.L} elements")
-        base = self.clip_base if clip_base is None else int(clip_base)
+        self._check_rows(rows, B)
+        self._check_rows(clean, B, "clean")
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().paa_noise_add(self.seed, _lib.ptr(self.noise_counter), self.stream_id, base, _lib.ptr(clean),
-                                                _lib.ptr(self.snr_db), _lib.ptr(self.sigma), _lib.ptr(rows), B, self.L,
-                                                _lib.stream_ptr()))
+            _lib.check(_lib.lib().paa_noise_add(self.seed, _lib.ptr(self.noise_counter), self.stream_id, self._base(clip_base),
+                                                _lib.ptr(clean), _lib.ptr(self.snr_db), _lib.ptr(self.sigma), _lib.ptr(rows), B,
+                                                self.L, _lib.stream_ptr()))
         return rows[:B]
-
-
-def of_args(args, model, seed: int, stream_id: int, with_grad: bool, rank: int, L: int):
-    """The ``Channel`` of one site, or None with the mode off."""
-    m = Modes.of(args)
-    if not m.chan_on:
-        return None
-    nb = int(model.max_batch)
-    return Channel(model.device, nb, L, seed, stream_id, m.drift_ppm, m.noise_snr, clip_base=rank * nb, with_grad=with_grad)
 
 
 def drift(rows, ratio, adjoint: bool = False):

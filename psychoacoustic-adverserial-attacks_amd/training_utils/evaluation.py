@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch
 
 from ..core import loss_helpers
-from . import channel, modes, place, rir
+from . import chain, channel, modes, place, rir
 from .build import batch_lengths
 from .scoring_helpers import Scores
 
@@ -24,7 +24,7 @@ class _PlacedEval:
         place.shift_on(args), place.gain_db(args)          # rooms alone still place: these two flags are read before the rooms'
         rir.check(args)
         channel.check(args)
-        self.pp, self.placed = pp, rir.PlacedRows(args, model, pp.numel(), place.STREAM_EVAL, False, rank)
+        self.pp, self.placed = pp, chain.PlaybackChain(args, model, pp.numel(), place.STREAM_EVAL, False, rank)
 
     def rows(self, B, clean=None):
         return self.placed.rows(self.pp, B, clean)

@@ -41,7 +41,8 @@ A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement of
 and no bound search are the plain step, bit for bit.
 
 Which modes may run together, and which refusal wins when several apply, is decided in one table: training_utils/modes.py.  What
-a mode means is written where it is built: place.py, rir.py (§6g), channel.py (§6k), ``set_lengths`` and PaaModel.set_lengths (§6h).
+a mode means is written where it is built: place.py, rir.py (§6g), channel.py (§6k) and chain.py, which orders the
+three (``chain.PlaybackChain``), ``set_lengths`` and PaaModel.set_lengths (§6h).
 
 The packed vector is ``[ grad (Lp) | loss, sum clean^2, TV(clean), wer_errors, wer_ref_words, clips, masking loss, 0 ]`` in
 float32; the 8 stat slots are defined HERE (ST_*) and documented in include/paa_hip.h (paa_model_fwd_bwd, d_stats).  Every rank
@@ -64,7 +65,7 @@ import contextlib
 import torch
 
 from .. import _lib, runtime
-from . import channel, modes, place, rir
+from . import chain, channel, modes, place, rir
 from .build import batch_lengths, unpack_batch  # noqa: F401  (re-exported)
 from .modes import Ctx, Modes, replace
 
@@ -446,7 +447,9 @@ class PgdStepper(_StepperCore):
         self.world = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.world = torch.distributed.get_world_size(group)
-        rir.check(args)                                                          # refusals: before any launch or collective
+        # refusals, before any launch or collective.  The stepper's own order (not chain.check's): the rooms' and the channel's
+        # before the perturbation length is settled, placement's after it
+        rir.check(args)
         channel.check(args)
         m = Modes.of(args)
         self.place_on, self.rir_on, self.chan_on, self.Lp = m.place_on, m.rir_on, m.chan_on, L
@@ -464,82 +467,79 @@ class PgdStepper(_StepperCore):
         self.packed = torch.zeros(self.Lp + N_STATS, dtype=torch.float32, device=self.dev)
         self.grad = self.packed[: self.Lp].view(1, self.Lp)
         self.stats = self.packed[self.Lp:]
-        if self.place_on or self.rir_on or self.chan_on:
+        if self.place_on or self.rir_on or self.chan_on:          # the playback chain; the attribute is absent with all three off
             rank = torch.distributed.get_rank(self.group) if self.world > 1 else 0
-            self.placed = rir.PlacedRows(args, model, self.Lp, place.STREAM_TRAIN, True, rank, L)
-            pl = self.placer = self.placed.placer
-            self.shift, self.gain, self.counter, self.rows, self.grad_rows = pl.shift, pl.gain, pl.counter, pl.rows, pl.grad_rows
-        if self.rir_on:
-            rv = self.reverb = self.placed.reverb
-            self.room, self.rir_counter, self.wet_rows = rv.index, rv.counter, rv.rows
-        if self.chan_on:
-            self.chan = self.placed.chan
+            self.placed = chain.PlaybackChain(args, model, self.Lp, place.STREAM_TRAIN, True, rank, L)
 
     def _check_adam_shape(self):
         if self.adam_p.numel() != self.Lp:
             raise ValueError(f"optimizer parameter has {self.adam_p.numel()} elements, expected {self.Lp}")
 
-    # ---- random placement of the perturbation ----------------------------------------------------------------------
-    def _reverb(self):
-        if not self.rir_on:
-            raise RuntimeError("the stepper was built with room responses off (rir_bank)")
-        return self.reverb
+    # ---- the playback chain: placement, room responses, the channel ----------------------------------------------------
+    @property
+    def placer(self):
+        return self.placed.placer
 
-    def set_rooms(self, index):
-        """Explicit per-clip room indices instead of the draw, from the next step on (stream-ordered copy into the fixed buffer);
-        ``set_rooms(None)`` returns to drawing.  A captured graph keeps the form it was captured with."""
-        self._reverb().set_rooms(index)
+    @property
+    def reverb(self):
+        return self.placed.reverb
 
-    def set_rir_step(self, n: int):
-        """Device step counter of the next room draw (resume, tests)."""
-        self._reverb().set_step(n)
+    @property
+    def chan(self):
+        return self.placed.chan
 
-    def _chan(self):
-        if not self.chan_on:
-            raise RuntimeError("the stepper was built with the playback channel off (drift_ppm / noise_snr_db)")
-        return self.chan
+    _SITES = {"placer": ("place_on", "placement off (perturbation_seconds / place_shift / place_gain_db)"),
+              "reverb": ("rir_on", "room responses off (rir_bank)"),
+              "chan": ("chan_on", "the playback channel off (drift_ppm / noise_snr_db)")}
 
-    def set_channel(self, ratio, snr_db=None):
-        """Explicit per-clip clock ratios (and noise SNRs in dB) instead of the draw, from the next step on (stream-ordered copy
-        into the fixed buffers); ``set_channel(None)`` returns to drawing.  The noise samples keep their own counter and stay
-        fresh.  A captured graph keeps the form it was captured with."""
-        self._chan().set_channel(ratio, snr_db)
-
-    def set_chan_step(self, n: int):
-        """Device step counters of the next channel draw and the next noise (resume, tests)."""
-        self._chan().set_step(n)
-
-    def _placer(self):
-        if not self.place_on:
-            raise RuntimeError("the stepper was built with placement off (perturbation_seconds / place_shift / place_gain_db)")
-        return self.placer
+    def _site(self, name):
+        """The chain's site ``name``; raises when the stepper was built with its mode off."""
+        on, off = self._SITES[name]
+        if not getattr(self, on):
+            raise RuntimeError(f"the stepper was built with {off}")
+        return getattr(self.placed, name)
 
     def set_placement(self, shift, gain=None):
         """Explicit per-clip shifts (and gains, default 1) instead of the draw, from the next step on (stream-ordered copy into the
         fixed buffers); ``set_placement(None)`` returns to drawing.  A captured graph keeps the form it was captured with."""
-        self._placer().set_placement(shift, gain)
+        self._site("placer").set_placement(shift, gain)
+
+    def set_rooms(self, index):
+        """The same for per-clip room indices."""
+        self._site("reverb").set_rooms(index)
+
+    def set_channel(self, ratio, snr_db=None):
+        """The same for per-clip clock ratios (and noise SNRs in dB).  The noise samples keep their own counter and stay fresh."""
+        self._site("chan").set_channel(ratio, snr_db)
 
     def set_place_step(self, n: int):
-        """Device step counter of the next draw (resume, tests)."""
-        self._placer().set_step(n)
+        """Device step counter of the next placement draw (resume, tests)."""
+        self._site("placer").set_step(n)
+
+    def set_rir_step(self, n: int):
+        """... of the next room draw."""
+        self._site("reverb").set_step(n)
+
+    def set_chan_step(self, n: int):
+        """... of the next channel draw and the next noise."""
+        self._site("chan").set_step(n)
 
     @property
     def clip_base(self):
         """Global id of this rank's first clip in the draws' counters (default rank * model.max_batch); assignable per step.  A
         captured graph holds the value it was captured with."""
-        return (self.placer if self.rir_on or self.chan_on else self._placer()).clip_base
+        if not (self.rir_on or self.chan_on):
+            self._site("placer")
+        return self.placed.clip_base
 
     @clip_base.setter
     def clip_base(self, v):
-        (self.placer if self.rir_on or self.chan_on else self._placer()).clip_base = int(v)
-        if self.rir_on:
-            self.reverb.clip_base = int(v)
-        if self.chan_on:
-            self.chan.clip_base = int(v)
+        if not (self.rir_on or self.chan_on):
+            self._site("placer")
+        self.placed.clip_base = v
 
     def _replay_state(self):
-        return super()._replay_state() + ([self.counter] if self.place_on else []) + ([self.rir_counter] if self.rir_on else []) \
-            + ([self.chan.counter, self.chan.noise_counter] if self.chan_on else [])
+        return super()._replay_state() + (self.placed.counters() if self.place_on or self.rir_on or self.chan_on else [])
 
     # ---- bookkeeping carried by the packed vector -------------------------------------------------------------
     def set_wer_counts(self, errors: float, ref_words: float):
@@ -553,9 +553,9 @@ class PgdStepper(_StepperCore):
         out = {"grad": self.grad, "stats": self.stats}
         if logits_out is not None:
             out["logits"] = logits_out
-        placed = self.place_on or self.rir_on or self.chan_on      # rir.PlacedRows: one gradient row per clip, then their adjoint into self.grad
+        placed = self.place_on or self.rir_on or self.chan_on      # chain.PlaybackChain: one gradient row per clip, then their adjoint into self.grad
         if placed:
-            out["grad"] = self.grad_rows[:B]
+            out["grad"] = self.placed.placer.grad_rows[:B]
         r = self.model.fwd_bwd(clean, self.placed.rows(p, B, clean) if placed else p, labels, self.direction, want_grad=True,
                                want_logits=want_logits, out=out)
         if placed:

@@ -21,6 +21,7 @@ import torch
 from .. import _lib
 from . import modes
 from .modes import Ctx, Modes
+from .site import Site
 
 logger = logging.getLogger(__name__)
 
@@ -69,11 +70,6 @@ def check(args, L: int, Lp: int, eager_adam: bool = False) -> None:
                        "samples every step", Lp, hop, Lp % hop)
 
 
-def refuse_for_clips(args) -> None:
-    """paa_amd.attack_clips: one perturbation row per clip has no placement."""
-    modes.check(Modes.of(args), ("place_clips",))
-
-
 def suffix(args) -> str:
     """Run-directory part of a run with placement: "_place<Lp samples>[s][g<G>]"; empty with placement off, so other runs keep
     their directory (and resume from it)."""
@@ -95,37 +91,25 @@ def results_extra(args, Lp: int) -> dict:
     return {"perturbation_length": int(Lp), "place_shift": str(Modes.of(args).place_shift), "place_gain_db": gain_db(args)}
 
 
-class Placer:
+class Placer(Site):
     """Fixed device buffers and the three launches of one placement site (the training step, or one evaluation).
-    ``draw`` -> shift / gain of the next step's clips (Philox counter (step, clip_base + b, stream_id, 0), step read from and
-    advanced in ``counter`` on the device), ``place`` -> rows[:B], ``reduce`` -> the adjoint of ``place`` on grad_rows[:B]."""
+    ``draw`` -> shift / gain of the next step's clips (the placement stream of csrc/philox.h), ``place`` -> rows[:B], ``reduce`` ->
+    the adjoint of ``place`` on grad_rows[:B]."""
 
     def __init__(self, dev, max_batch: int, L: int, Lp: int, seed: int, stream_id: int, shift: bool, gain_db_: float,
                  clip_base: int = 0, with_grad: bool = True):
-        self.dev, self.max_batch, self.L, self.Lp = dev, int(max_batch), int(L), int(Lp)
-        self.seed, self.stream_id = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id)
-        self.shift_on, self.gain_db, self.clip_base = bool(shift), float(gain_db_), int(clip_base)
+        super().__init__(dev, max_batch, L, seed, stream_id, clip_base)
+        self.Lp, self.shift_on, self.gain_db = int(Lp), bool(shift), float(gain_db_)
         self.shift = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
         self.gain = torch.ones(self.max_batch, dtype=torch.float32, device=dev)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.rows = torch.zeros(self.max_batch, self.L, dtype=torch.float32, device=dev)
-        self.grad_rows = torch.zeros(self.max_batch, self.L, dtype=torch.float32, device=dev) if with_grad else None
-        self.explicit = False
-
-    def _fits(self, B):
-        if not 1 <= B <= self.max_batch:
-            raise ValueError(f"batch {B} outside [1, {self.max_batch}]")
-
-    def set_step(self, n: int):
-        """Step counter of the next draw (resume, tests); stream-ordered."""
-        self.counter.fill_(int(n))
+        self.rows = self._zeros()
+        self.grad_rows = self._zeros() if with_grad else None
 
     def set_placement(self, shift, gain=None):
         """Pin explicit shifts (and gains, default 1) for the clips of the following steps by a stream-ordered copy: the draw is
         skipped until ``set_placement(None)``.  Which of the two a captured graph holds is fixed by ``capture()``."""
         if shift is None:
-            self.explicit = False
-            return
+            return self.unpin()
         s = torch.as_tensor(shift, dtype=torch.int32).reshape(-1)
         g = torch.ones(s.numel(), dtype=torch.float32) if gain is None else torch.as_tensor(gain, dtype=torch.float32).reshape(-1)
         self._fits(s.numel())
@@ -139,11 +123,10 @@ class Placer:
 
     def draw(self, B: int, clip_base=None):
         self._fits(B)
-        base = self.clip_base if clip_base is None else int(clip_base)
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().paa_place_draw(self.seed, _lib.ptr(self.counter), self.stream_id, base, B, self.Lp,
-                                                 int(self.shift_on), self.gain_db, _lib.ptr(self.shift), _lib.ptr(self.gain),
-                                                 _lib.stream_ptr()))
+            _lib.check(_lib.lib().paa_place_draw(self.seed, _lib.ptr(self.counter), self.stream_id, self._base(clip_base), B,
+                                                 self.Lp, int(self.shift_on), self.gain_db, _lib.ptr(self.shift),
+                                                 _lib.ptr(self.gain), _lib.stream_ptr()))
 
     def place(self, p, B: int):
         self._fits(B)

@@ -21,8 +21,9 @@ import numpy as np
 import torch
 
 from .. import _lib, synth
-from . import channel, modes, place
+from . import modes
 from .modes import Ctx, Modes
+from .site import Site
 
 MAX_TAPS = 16384                      # PAA_RIR_MAX_TAPS of include/paa_hip.h
 MAX_COUNT = 65536
@@ -62,11 +63,6 @@ def check(args, eager_adam: bool = False) -> None:
     if m.rir_on:          # the synthetic bank's flags range-checked, or a bank file read and checked, here on the host
         _synthetic_flags(args) if str(args.rir_bank) == "synthetic" else bank_of(args)
     modes.check(m, modes.ROOMS, Ctx(1, eager_adam))
-
-
-def refuse_for_clips(args) -> None:
-    """paa_amd.attack_clips: reverberation of per-clip perturbations is not part of this."""
-    modes.check(Modes.of(args), ("rir_clips",))
 
 
 def synthetic_rt60(N: int, rt60_lo: float, rt60_hi: float, seed: int) -> np.ndarray:
@@ -156,40 +152,27 @@ def draw_seed(args) -> int:
     return int(getattr(args, "seed", 5) if seed is None else seed)
 
 
-class Reverb:
+class Reverb(Site):
     """Fixed device buffers and the launches of one reverberation site (the training step, or one evaluation), beside
-    ``place.Placer``.  ``draw`` -> room index of the next step's clips (Philox counter (step, clip_base + b, stream_id, 1), step
-    read from and advanced in ``counter`` on the device), ``apply`` -> rows[:B] = h_c * in, ``adjoint`` -> grad_rows[:B] = the
-    adjoint of ``apply`` on the gradient rows of the model."""
+    ``place.Placer``.  ``draw`` -> room index of the next step's clips (the room stream of csrc/philox.h, a counter of its own),
+    ``apply`` -> rows[:B] = h_c * in, ``adjoint`` -> grad_rows[:B] = the adjoint of ``apply`` on the gradient rows of the model."""
 
     def __init__(self, dev, bank, max_batch: int, L: int, seed: int, stream_id: int, clip_base: int = 0, with_grad: bool = True):
-        self.dev, self.max_batch, self.L = dev, int(max_batch), int(L)
+        super().__init__(dev, max_batch, L, seed, stream_id, clip_base)
         bank = torch.as_tensor(bank)
         if bank.dim() != 2 or not bank.is_floating_point() or not 1 <= bank.shape[1] <= MAX_TAPS:
             raise ValueError(f"a bank is a float (N, K <= {MAX_TAPS}) array, got {bank.dtype} {tuple(bank.shape)}")
         self.bank = bank.to(dev, torch.float32).contiguous()
         self.N, self.K = int(bank.shape[0]), int(bank.shape[1])
-        self.seed, self.stream_id, self.clip_base = int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id), int(clip_base)
         self.index = torch.zeros(self.max_batch, dtype=torch.int32, device=dev)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.rows = torch.zeros(self.max_batch, self.L, dtype=torch.float32, device=dev)
-        self.grad_rows = torch.zeros(self.max_batch, self.L, dtype=torch.float32, device=dev) if with_grad else None
-        self.explicit = False
-
-    def _fits(self, B):
-        if not 1 <= B <= self.max_batch:
-            raise ValueError(f"batch {B} outside [1, {self.max_batch}]")
-
-    def set_step(self, n: int):
-        """Step counter of the next draw (resume, tests); stream-ordered."""
-        self.counter.fill_(int(n))
+        self.rows = self._zeros()
+        self.grad_rows = self._zeros() if with_grad else None
 
     def set_rooms(self, index):
         """Pin explicit room indices for the clips of the following steps by a stream-ordered copy: the draw is skipped until
         ``set_rooms(None)``.  Which of the two a captured graph holds is fixed by ``capture()``."""
         if index is None:
-            self.explicit = False
-            return
+            return self.unpin()
         c = torch.as_tensor(index, dtype=torch.int32).reshape(-1)
         self._fits(c.numel())
         self.index[: c.numel()].copy_(c, non_blocking=True)
@@ -197,15 +180,13 @@ class Reverb:
 
     def draw(self, B: int, clip_base=None):
         self._fits(B)
-        base = self.clip_base if clip_base is None else int(clip_base)
         with torch.cuda.device(self.dev):
-            _lib.check(_lib.lib().paa_rir_draw(self.seed, _lib.ptr(self.counter), self.stream_id, base, B, self.N,
+            _lib.check(_lib.lib().paa_rir_draw(self.seed, _lib.ptr(self.counter), self.stream_id, self._base(clip_base), B, self.N,
                                                _lib.ptr(self.index), _lib.stream_ptr()))
 
     def _launch(self, src, dst, B, adjoint):
         self._fits(B)
-        if src.dtype != torch.float32 or not src.is_contiguous() or src.numel() < B * self.L:
-            raise ValueError(f"rows must be contiguous float32 with at least {B} x {self.L} elements")
+        self._check_rows(src, B)
         with torch.cuda.device(self.dev):
             _lib.check(_lib.lib().paa_rir_apply(_lib.ptr(self.bank), self.N, self.K, _lib.ptr(self.index), _lib.ptr(src),
                                                 _lib.ptr(dst), B, self.L, adjoint, _lib.stream_ptr()))
@@ -218,57 +199,6 @@ class Reverb:
     def adjoint(self, grad_rows, B: int):
         """The model's gradient rows (B, L) -> self.grad_rows[:B], the gradient with respect to the rows ``apply`` read."""
         return self._launch(grad_rows, self.grad_rows, B, 1)
-
-
-class PlacedRows:
-    """The rows the model sees at one site (the training step, or one evaluation) with placement, room responses and / or the
-    playback channel (channel.py) on: a ``place.Placer``, with room responses on a ``Reverb``, with the channel on a
-    ``channel.Channel``, all keyed by ``draw_seed`` and the global clip id ``rank * max_batch + b``.  The chain is place -> drift ->
-    rooms -> + noise: drift belongs to the emitter, the room to the path, noise to the microphone.  With placement off the rows are
-    placed at explicit zero shifts and unit gains, and nothing is drawn for them."""
-
-    def __init__(self, args, model, Lp: int, stream_id: int, with_grad: bool = True, rank: int = 0, L=None):
-        m, nb, L, seed = Modes.of(args), int(model.max_batch), int(model.length if L is None else L), draw_seed(args)
-        self.placer = place.Placer(model.device, nb, L, Lp, seed, stream_id, place.shift_on(args), place.gain_db(args),
-                                   clip_base=rank * nb, with_grad=with_grad)
-        if not m.place_on:
-            self.placer.set_placement([0] * nb)
-        self.reverb = Reverb(model.device, bank_of(args), nb, L, seed, stream_id, clip_base=rank * nb,
-                             with_grad=with_grad) if m.rir_on else None
-        self.chan = channel.of_args(args, model, seed, stream_id, with_grad, rank, L)
-
-    def rows(self, p, B: int, clean=None):
-        """draw -> rows [-> channel draw -> drift] [-> room draw -> rows through the rooms] [-> + noise]; an explicit placement /
-        explicit channels / explicit rooms skip their draw.  ``clean`` (B, L): the clean batch, whose level scales the noise."""
-        pl, rv, ch = self.placer, self.reverb, self.chan
-        if not pl.explicit:
-            pl.draw(B)
-        rows, buf = pl.place(p, B), pl.rows          # buf: the whole buffer the last launch wrote, rows its first B
-        if ch is not None:
-            if not ch.explicit:
-                ch.draw(B)
-            if ch.drift_on:
-                rows, buf = ch.apply(buf, B), ch.rows
-        if rv is not None:
-            if not rv.explicit:
-                rv.draw(B)
-            rows, buf = rv.apply(buf, B), rv.rows
-        if ch is not None and ch.noise_on:
-            if clean is None:
-                raise ValueError("ambient noise (noise_snr_db) needs the clean batch: rows(p, B, clean)")
-            ch.add_noise(buf, clean, B)
-        return rows
-
-    def reduce(self, B: int, grad):
-        """The model's gradient rows (``placer.grad_rows``) [-> the rooms' adjoint] [-> the drift's transpose] -> adjoint gather-sum
-        into ``grad``.  Noise does not depend on the perturbation: the backward pass does not see it."""
-        pl, rv, ch = self.placer, self.reverb, self.chan
-        g = pl.grad_rows
-        if rv is not None:
-            g = rv.adjoint(g, B)
-        if ch is not None and ch.drift_on:
-            g = ch.adjoint(g, B)
-        pl.reduce(B, grad, None if g is pl.grad_rows else g)
 
 
 def reverberate(rows, bank, index):

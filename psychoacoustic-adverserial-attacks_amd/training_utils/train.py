@@ -13,7 +13,7 @@ import torch
 
 from .. import _lib, runtime
 from ..core import loss_helpers
-from . import channel, modes, place, rir
+from . import chain, modes
 from .modes import Ctx, Modes
 from .pgd import FREQ_NORMS, PgdStepper, adam_unsupported, batch_lengths
 
@@ -148,9 +148,7 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
     # AMSGrad, ...): there it is what the reference runs, and the data-parallel machinery has nothing to add.
     eager_adam = args.optimizer_type == "adam" and adam_route(optimizer, world) == "eager"
     modes.check(m, ("alpha_eager",), Ctx(world, eager_adam))          # refusals: before any launch or collective
-    place.check(args, L, Lp, eager_adam)
-    rir.check(args, eager_adam)
-    channel.check(args, eager_adam)
+    chain.check(args, L, Lp, eager_adam)
     modes.check(m, modes.LENGTHS + ("len_eager",), Ctx(world, eager_adam))
     step_opt = optimizer if args.optimizer_type == "adam" and not eager_adam else None
     mask_alpha, lengths_mode = m.alpha, m.lengths_on
@@ -164,12 +162,9 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
         stepper = PgdStepper(model, args, L, interp, spl_thresh, optimizer=step_opt, device_wer=canon is not None, canon=canon,
                              p_length=Lp)
         model._stepper = stepper
-        if stepper.place_on:          # a resumed run goes on drawing where the epochs before it stopped, not from step 0 again
-            stepper.set_place_step(int(epoch) * len(train_data_loader))
-        if stepper.rir_on:            # the same for the room draw's counter
-            stepper.set_rir_step(int(epoch) * len(train_data_loader))
-        if stepper.chan_on:           # and for the channel's two counters
-            stepper.set_chan_step(int(epoch) * len(train_data_loader))
+        if stepper.place_on or stepper.rir_on or stepper.chan_on:
+            # a resumed run goes on drawing where the epochs before it stopped, not from step 0 again
+            stepper.placed.set_step(int(epoch) * len(train_data_loader))
     if not lengths_mode and stepper.lengths_on:
         stepper.set_lengths(None)             # a model left in the length mode by an earlier caller: padded means padded
     if canon is not None:

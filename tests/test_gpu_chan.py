@@ -310,7 +310,7 @@ def test_channel_step_vs_oracle(case, variant):
     # the chain place -> drift -> rooms -> + noise in numpy float64
     rows0 = PR.place(p0.numpy()[0], L, shifts, g32)
     if case != "noise":          # noise alone is added in place on the placed rows
-        assert torch.equal(st.rows.cpu(), torch.from_numpy(rows0))
+        assert torch.equal(st.placer.rows.cpu(), torch.from_numpy(rows0))
     wet = rows0.astype(np.float64)
     if ratios is not None:
         wet = CR.apply64(rq, wet)
@@ -320,7 +320,7 @@ def test_channel_step_vs_oracle(case, variant):
         assert int(st.chan.noise_counter.item()) == s0 + 1
         sig = CR.sigma64(clean.numpy(), np.asarray(snrs, dtype=np.float32))
         wet = wet + np.stack([sig[b] * CR.noise64(5, s0, b, 0, L) for b in range(B)])
-    last = st.wet_rows if rooms is not None else (st.chan.rows if ratios is not None else st.rows)
+    last = st.reverb.rows if rooms is not None else (st.chan.rows if ratios is not None else st.placer.rows)
     seen = last[:B].cpu().numpy().astype(np.float64)
     assert np.abs(seen - wet).max() <= 1e-5 * np.abs(wet).max()
     ref = opgd.pgd_step(sd, a, args, clean, labels, torch.from_numpy(wet.astype(np.float32)), spl)

@@ -141,7 +141,12 @@ def _draw(seed, counter, stream_id, clip_base, B, Lp, shift_on, G, shift, gain):
 
 @pytest.mark.parametrize("Lp", [1000, 16000])
 def test_place_draw(Lp):
-    B, base, seed = 5, 7, 5
+    for B in (5, 1, 257):          # 257: one past the block, the draw's clip loop takes a second pass
+        _place_draw(Lp, B)
+
+
+def _place_draw(Lp, B):
+    base, seed = 7, 5
     counter = Guarded((1,), torch.int32)
     for shift_on, G in ((1, 0.0), (1, 6.0), (0, 6.0)):
         counter.t.zero_()
@@ -221,7 +226,7 @@ def test_placed_step_vs_oracle(case, variant):
     spl = OP.spl_thresh_tensor(args)
     m = PaaModel(a, sdn, B, L, "fp32")
     st = PgdStepper(m, args, L, None, build.init_phon_threshold_tensor(args))
-    assert st.place_on and st.Lp == Lp and st.packed.numel() == Lp + 8 and st.rows.shape == (B, L) and st.grad_rows.shape == (B, L)
+    assert st.place_on and st.Lp == Lp and st.packed.numel() == Lp + 8 and st.placer.rows.shape == (B, L) and st.placer.grad_rows.shape == (B, L)
     st.set_placement(shifts, gains)
     p = p0.cuda()
     r = st.step(p, clean.cuda(), labels)
@@ -229,7 +234,7 @@ def test_placed_step_vs_oracle(case, variant):
     g = st.grad.cpu().numpy()[0]
     g32 = None if gains is None else np.asarray(gains, dtype=np.float32)
     rows0 = torch.from_numpy(PR.place(p0.numpy()[0], L, shifts, g32))
-    assert torch.equal(st.rows.cpu(), rows0)
+    assert torch.equal(st.placer.rows.cpu(), rows0)
     ref = opgd.pgd_step(sd, a, args, clean, labels, rows0, spl)
     gref = PR.reduce64(ref["grad"].numpy(), shifts, g32, Lp)[0]
     e_g = rel_err(g, gref)
@@ -276,18 +281,18 @@ def test_draw_in_graph_follows_the_device_counter():
     st_e.set_place_step(c0)
     g, _ = st_g.capture(p_g, clean, labels)
     torch.cuda.synchronize()
-    assert int(st_g.counter.item()) == c0                       # the warm-up step's draw is taken back
+    assert int(st_g.placer.counter.item()) == c0                       # the warm-up step's draw is taken back
     p_g.copy_(p0)
     for k in range(3):
         g.replay()
         torch.cuda.synchronize()
         s_ref, a_ref = PR.draw(5, c0 + k, 0, B, 0, L, True, 6.0)
-        assert st_g.shift.cpu().tolist() == s_ref.tolist(), k
-        assert np.all(np.abs(st_g.gain.cpu().numpy() - a_ref) <= 1e-6 * a_ref)
-        assert int(st_g.counter.item()) == c0 + k + 1
+        assert st_g.placer.shift.cpu().tolist() == s_ref.tolist(), k
+        assert np.all(np.abs(st_g.placer.gain.cpu().numpy() - a_ref) <= 1e-6 * a_ref)
+        assert int(st_g.placer.counter.item()) == c0 + k + 1
         st_e.step(p_e, clean, labels)
         torch.cuda.synchronize()
-        assert torch.equal(st_e.shift, st_g.shift) and torch.equal(st_e.gain, st_g.gain)
+        assert torch.equal(st_e.placer.shift, st_g.placer.shift) and torch.equal(st_e.placer.gain, st_g.placer.gain)
     assert torch.equal(p_g, p_e)                                 # three replays = three eager steps
     assert not torch.equal(p_g, p0)
 

@@ -151,7 +151,12 @@ def test_rir_refusals_leave_outputs_alone():
 # ---- 2. paa_rir_draw -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N", [1, 3, 64])
 def test_rir_draw(N):
-    B, base, seed = 5, 7, 5
+    for B in (5, 1, 257):          # 257: one past the block, the draw's clip loop takes a second pass
+        _rir_draw(N, B)
+
+
+def _rir_draw(N, B):
+    base, seed = 7, 5
     counter = Guarded((1,), torch.int32)
     counter.t.zero_()
     for step in range(3):
@@ -202,7 +207,7 @@ def test_reverberant_step_vs_oracle(case, variant):
     m = PaaModel(a, sdn, B, L, "fp32")
     st = PgdStepper(m, args, L, None, build.init_phon_threshold_tensor(args))
     assert st.rir_on and st.place_on == (case != "alone") and st.Lp == Lp and st.packed.numel() == Lp + 8
-    assert st.rows.shape == (B, L) and st.wet_rows.shape == (B, L) and st.reverb.grad_rows.shape == (B, L)
+    assert st.placer.rows.shape == (B, L) and st.reverb.rows.shape == (B, L) and st.reverb.grad_rows.shape == (B, L)
     if st.place_on:
         st.set_placement(shifts, gains)
     else:
@@ -215,9 +220,9 @@ def test_reverberant_step_vs_oracle(case, variant):
     g = st.grad.cpu().numpy()[0]
     g32 = None if gains is None else np.asarray(gains, dtype=np.float32)
     rows0 = PR.place(p0.numpy()[0], L, shifts, g32)
-    assert torch.equal(st.rows.cpu(), torch.from_numpy(rows0))
+    assert torch.equal(st.placer.rows.cpu(), torch.from_numpy(rows0))
     wet64 = RR.apply64(bank_np, rooms, rows0)                                    # the rows convolved in numpy float64 first
-    wet_dev = st.wet_rows.cpu().numpy().astype(np.float64)
+    wet_dev = st.reverb.rows.cpu().numpy().astype(np.float64)
     assert np.all(np.abs(wet_dev - wet64) <= RR.bound(bank_np, rooms, rows0))
     ref = opgd.pgd_step(sd, a, args, clean, labels, torch.from_numpy(wet64.astype(np.float32)), spl)
     gref = PR.reduce64(RR.adjoint64(bank_np, rooms, ref["grad"].numpy()), shifts, g32, Lp)[0]        # and the adjoint in numpy
@@ -260,17 +265,17 @@ def test_draws_in_graph_follow_the_device_counters():
     seq = ["paa_place_draw", "paa_place_rows", "paa_rir_draw", "paa_rir_apply", "paa_model_fwd_bwd_rows", "paa_rir_apply", "paa_place_reduce",
            "paa_sign_step", "paa_project"]
     assert cap == seq + seq                                      # the warm-up step, then the captured one
-    assert int(st_g.counter.item()) == c0 and int(st_g.rir_counter.item()) == r0      # capture() leaves both counters as it found them
+    assert int(st_g.placer.counter.item()) == c0 and int(st_g.reverb.counter.item()) == r0      # capture() leaves both counters as it found them
     p_g.copy_(p0)
     for k in range(3):
         g.replay()
         torch.cuda.synchronize()
-        assert st_g.room.cpu().tolist() == RR.draw(5, r0 + k, 0, B, 0, 8).tolist(), k
-        assert st_g.shift.cpu().tolist() == PR.draw(5, c0 + k, 0, B, 0, L)[0].tolist(), k
-        assert int(st_g.rir_counter.item()) == r0 + k + 1 and int(st_g.counter.item()) == c0 + k + 1
+        assert st_g.reverb.index.cpu().tolist() == RR.draw(5, r0 + k, 0, B, 0, 8).tolist(), k
+        assert st_g.placer.shift.cpu().tolist() == PR.draw(5, c0 + k, 0, B, 0, L)[0].tolist(), k
+        assert int(st_g.reverb.counter.item()) == r0 + k + 1 and int(st_g.placer.counter.item()) == c0 + k + 1
         st_e.step(p_e, clean, labels)
         torch.cuda.synchronize()
-        assert torch.equal(st_e.room, st_g.room) and torch.equal(st_e.shift, st_g.shift)
+        assert torch.equal(st_e.reverb.index, st_g.reverb.index) and torch.equal(st_e.placer.shift, st_g.placer.shift)
     assert torch.equal(p_g, p_e) and not torch.equal(p_g, p0)    # three replays = three eager steps
 
 
@@ -286,15 +291,15 @@ def test_set_rooms_pins_indices():
             st.step(p, clean, labels)
         assert "paa_rir_draw" not in names and "paa_place_draw" not in names and names.count("paa_rir_apply") == 2
     torch.cuda.synchronize()
-    assert st.room.cpu().tolist() == [6, 1] and int(st.rir_counter.item()) == 0
-    want = RR.apply64(rir.bank_of(args), [6, 1], st.rows.cpu().numpy())
-    assert np.all(np.abs(st.wet_rows.cpu().numpy() - want) <= RR.bound(rir.bank_of(args), [6, 1], st.rows.cpu().numpy()))
-    assert torch.equal(rir.reverberate(st.rows, rir.bank_of(args), [6, 1]), st.wet_rows)
+    assert st.reverb.index.cpu().tolist() == [6, 1] and int(st.reverb.counter.item()) == 0
+    want = RR.apply64(rir.bank_of(args), [6, 1], st.placer.rows.cpu().numpy())
+    assert np.all(np.abs(st.reverb.rows.cpu().numpy() - want) <= RR.bound(rir.bank_of(args), [6, 1], st.placer.rows.cpu().numpy()))
+    assert torch.equal(rir.reverberate(st.placer.rows, rir.bank_of(args), [6, 1]), st.reverb.rows)
     st.set_rooms(None)                                           # back to drawing, from the counter where it stood
     with record_launches() as names:
         st.step(p, clean, labels)
     torch.cuda.synchronize()
-    assert "paa_rir_draw" in names and st.room.cpu().tolist() == RR.draw(5, 0, 0, B, 0, 8).tolist() and int(st.rir_counter.item()) == 1
+    assert "paa_rir_draw" in names and st.reverb.index.cpu().tolist() == RR.draw(5, 0, 0, B, 0, 8).tolist() and int(st.reverb.counter.item()) == 1
     with pytest.raises(ValueError):
         st.set_rooms([0, 1, 2])
 
