@@ -217,6 +217,39 @@ paa_status paa_clip_search(const float* d_delta /* (B, L) */, int B, int L, cons
                            int targeted, int wer_milli, float shrink, float floor_scale,
                            float* d_scale /* (B) in/out */, float* d_best /* (B, L) */, float* d_best_scale /* (B) */,
                            int32_t* d_best_step /* (B) */, int32_t* d_step /* [1] */, void* stream);
+/* ---- per-clip adaptive masking-loss weight (Qin et al. 2019 stage 2 schedule, extension; additions to ABI 350) ----
+ * paa_masking_loss_rows: paa_masking_loss with one weight per row.  alpha_rows is 1 or p_rows:
+ *   alpha_rows = 1   paa_masking_loss itself: d_alpha device [1] or NULL = 1.0, the same launches, the same bits (paa_masking_loss
+ *                    IS this call with alpha_rows = 1)
+ *   alpha_rows = B   needs p_rows = B and a non-null d_alpha (B): row b of d_grad gets -= d_alpha[b] * grad l_b.  The row is the
+ *                    workgroup's blockIdx.y, so the weight stays one scalar load per workgroup.
+ * Any other combination is PAA_ERR_ARG before any launch.  Nothing else differs: d_loss_rows / d_loss_sum are the unweighted l_b and
+ * their sum, d_weight the hinge weight W.  No atomics. */
+paa_status paa_masking_loss_rows(paa_proj* h, const paa_params* prm, const float* d_p, int p_rows, const float* d_clean, int B, int L,
+                                 const float* d_alpha, int alpha_rows, float* d_grad, float* d_loss_rows, float* d_loss_sum,
+                                 float* d_weight, void* stream);
+/* Decide / keep / move alpha, per clip b, with step = *d_step, n = step + 1, (e, w, _) = d_counts[b] (paa_wer_counts of the step),
+ * l = d_loss_rows[b] (l_b of the step, paa_masking_loss_rows) and a = d_alpha[b].  All float arithmetic in f32, part of the contract:
+ *   success   exactly paa_clip_search's test, the same integer compares
+ *   keep      success && l < d_best_loss[b] (strict f32 compare: a NaN l never keeps, an equal l keeps the earlier delta):
+ *             d_best[b] <- d_delta[b] (the whole row, as paa_clip_search copies it), d_best_loss[b] <- l,
+ *             d_best_alpha[b] <- a (the alpha this delta was optimised under), d_best_step[b] <- step
+ *   raise     success && n % up_every == 0:     d_alpha[b] <- fminf(fmaxf(a * up, alpha_min), alpha_max)
+ *   lower     !success && n % down_every == 0:  d_alpha[b] <- fminf(fmaxf(a * down, alpha_min), alpha_max)
+ *   otherwise nothing of clip b is written
+ *   afterwards  *d_step = step + 1 ON THE DEVICE, so a captured graph counts on.
+ * (Qin's constants: up 1.2 every 20 steps, down 0.8 every 50, alpha_min = alpha0 / 100.)  The counters and l_b both belong to the
+ * delta that ENTERED the step, so the call sits after paa_wer_counts and BEFORE the update: the delta kept is the delta judged.  Two
+ * launches, as paa_clip_search and for its reason (a one-workgroup decide kernel writing the scalars and one flag per row, then the
+ * same (chunks, B) copy grid over the same flag array): the two entries never run in one step, and calls on different streams of one
+ * device must not overlap.  Capturable, allocates nothing, no atomics.  PAA_ERR_ARG before any launch: a null pointer, B < 1,
+ * B > 65535, L < 1, wer_milli < 1, up_every < 1, down_every < 1, up not finite or <= 1, down outside (0, 1), not
+ * 0 < alpha_min <= alpha_max < inf. */
+paa_status paa_clip_anneal(const float* d_delta /* (B, L) */, int B, int L, const int32_t* d_counts /* (B, 3) paa_wer_counts */,
+                           const float* d_loss_rows /* (B) l_b of this step */, int targeted, int wer_milli,
+                           int up_every, int down_every, float up, float down, float alpha_min, float alpha_max,
+                           float* d_alpha /* (B) in/out */, float* d_best /* (B, L) */, float* d_best_loss /* (B) in/out */,
+                           float* d_best_alpha /* (B) */, int32_t* d_best_step /* (B) */, int32_t* d_step /* [1] */, void* stream);
 /* train.py:136 with one perturbation row per clip: out[b] = clamp(clean[b] + p[b], -1, 1); d_p (p_rows, L), p_rows in
  * {1, B}; p_rows = 1 is paa_compose_clamp. */
 paa_status paa_compose_clamp_rows(const float* d_clean, const float* d_p, int p_rows, float* d_out, int B, int L,

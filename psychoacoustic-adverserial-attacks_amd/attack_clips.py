@@ -16,6 +16,13 @@ successful delta (``found``, ``found_step``, ``bound_scale``, ``last_scale``), o
 ``--loss_type margin`` (targeted attacks): the steps optimise the alignment-margin loss, which is zero exactly when
 the greedy decode is the target — the search's success test.  The step's ``loss`` then holds the margin loss; the records'
 ``clean_ctc`` / ``final_ctc`` stay CTC.
+
+``--alpha_search qin`` (needs ``--masking_loss_alpha`` > 0, the weight every clip starts from) answers "how quiet, under
+the masking threshold, can this clip's successful perturbation be?": every clip carries its own weight of the masking loss, raised
+while its attack succeeds and lowered while it fails, and the record describes the successful delta with the smallest masking loss
+(``alpha_found``, ``alpha_step``, ``best_masking_loss``, ``best_alpha``, ``last_alpha``).  Together with ``--bound_search shrink`` the
+run has two stages (Qin et al. 2019): the bound search for ``--stage1_steps`` steps without the masking loss, then the alpha
+schedule for the remaining steps, started from every clip's stage-1 delta under the bound stage 1 found.
 """
 from __future__ import annotations
 
@@ -41,6 +48,10 @@ SUMMARY_FIELDS = ("clean_wer", "adv_wer", "final_ctc", "l2", "linf", "snr_db")
 # --bound_search shrink only: found (the step's own counters said "success" at least once), the step of the reported delta (-1: not
 # found), the scale that delta satisfies (best_scale, or the last scale when not found) and the scale the search ended at
 SEARCH_FIELDS = ("found", "found_step", "bound_scale", "last_scale")
+# --alpha_search qin only: alpha_found (a successful delta was kept), its step (-1: none), the step's own l_b of the reported delta
+# (NaN: none kept), the alpha it was optimised under (the last alpha when none was kept) and the alpha the schedule ended at
+ANNEAL_FIELDS = ("alpha_found", "alpha_step", "best_masking_loss", "best_alpha", "last_alpha")
+STAGE1_FIELD = "stage1_masking_loss"       # two-stage run only: l_b of the delta that entered stage 2
 
 
 def create_arg_parser():
@@ -55,6 +66,19 @@ def create_arg_parser():
     p.add_argument("--search_success_wer", type=float, default=0.5,
                    help="bound search, untargeted: success is per-clip WER >= this (rounded to thousandths); targeted success is "
                         "always the target transcript exactly")
+    p.add_argument("--alpha_search", type=str, choices=["off", "qin"], default="off",
+                   help="qin: every clip's masking_loss_alpha starts at --masking_loss_alpha, is multiplied by --alpha_up every "
+                        "--alpha_up_every steps while its attack succeeds and by --alpha_down every --alpha_down_every steps while it "
+                        "fails; the record reports the successful perturbation with the smallest masking loss")
+    p.add_argument("--alpha_up", type=float, default=1.2, help="alpha search: factor on success, > 1")
+    p.add_argument("--alpha_down", type=float, default=0.8, help="alpha search: factor on failure, in (0, 1)")
+    p.add_argument("--alpha_up_every", type=int, default=20, help="alpha search: steps between two raises")
+    p.add_argument("--alpha_down_every", type=int, default=50, help="alpha search: steps between two lowerings")
+    p.add_argument("--alpha_min", type=float, default=None, help="alpha search: smallest alpha (default masking_loss_alpha / 100)")
+    p.add_argument("--alpha_max", type=float, default=None, help="alpha search: largest alpha (default masking_loss_alpha * 100)")
+    p.add_argument("--stage1_steps", type=int, default=None,
+                   help="--bound_search shrink with --alpha_search qin: steps of the bound search before the alpha schedule takes "
+                        "over (default pgd_steps // 2)")
     return p
 
 
@@ -102,6 +126,10 @@ def summarize(records, targeted: bool = False):
         hit = [r for r in records if r["found"]]
         out["success_rate"] = len(hit) / n
         out["mean_bound_scale"] = sum(float(r["bound_scale"]) for r in hit) / len(hit) if hit else float("nan")
+    if records and "alpha_found" in records[0]:    # --alpha_search qin: the share of clips with a kept delta, their mean l_b
+        hit = [r for r in records if r["alpha_found"]]
+        out["alpha_success_rate"] = len(hit) / n
+        out["mean_best_masking_loss"] = sum(float(r["best_masking_loss"]) for r in hit) / len(hit) if hit else float("nan")
     return out
 
 
@@ -136,18 +164,67 @@ def _device_wers(args, processor, logits, texts, frames=None, blank=0):
     return [e / max(w, 1) for e, w, _ in loss_helpers.wer_counts_device(logits, refs, canon, frames=frames, blank=blank).cpu().tolist()]
 
 
+def _judged_refs(args, processor, texts, targeted):
+    """(canon table, the reference rows success is judged against, why the device WER route is not available or None)."""
+    judged = [" ".join([args.target] * args.target_reps)] * len(texts) if targeted else texts
+    canon = loss_helpers.canon_table(processor)
+    refs = loss_helpers.encode_refs(judged) if canon is not None else None
+    why = ("the vocabulary is not one character per token" if canon is None else
+           f"a reference needs more than {loss_helpers.R_CAP} entries" if refs is None else None)
+    return canon, refs, why
+
+
 def search_route(args, processor, texts):
     """(SearchConfig, canon table, the step's reference rows) of a batch under --bound_search shrink; the references are the target
     transcript in targeted mode.  Raises the table's refusal when the device WER route is not available."""
     cfg = modes.SearchConfig.of(args)
     m = modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS, modes.Ctx(search=cfg))
-    judged = [" ".join([args.target] * args.target_reps)] * len(texts) if cfg.targeted else texts
-    canon = loss_helpers.canon_table(processor)
-    refs = loss_helpers.encode_refs(judged) if canon is not None else None
-    why = ("the vocabulary is not one character per token" if canon is None else
-           f"a reference needs more than {loss_helpers.R_CAP} entries" if refs is None else None)
+    canon, refs, why = _judged_refs(args, processor, texts, cfg.targeted)
     modes.check(m, ("search_route",), modes.Ctx(search=cfg, wer_why=why))
     return cfg, canon, refs
+
+
+def anneal_route(args, processor, texts):
+    """The same for --alpha_search qin: (AnnealConfig, canon table, reference rows)."""
+    ctx = modes.anneal_ctx(args)
+    m = modes.check(modes.Modes.of(args), modes.ANNEAL_FLAGS, ctx)
+    canon, refs, why = _judged_refs(args, processor, texts, ctx.anneal.targeted)
+    modes.check(m, ("anneal_route",), ctx._replace(wer_why=why))
+    return ctx.anneal, canon, refs
+
+
+def _run_search(stepper, delta, x, labels, steps, refs):
+    """``steps`` steps of the bound search on one batch -> (reported delta, found_step, bound_scale, last_scale), the last three on
+    the host.  The reported delta is ``best_b`` of a clip that fell, the last iterate of the others."""
+    B = x.shape[0]
+    stepper.set_refs(refs)
+    stepper.search_reset(B)
+    stepper.stats_log.cursor.zero_()                                    # nobody reads the per-step log here: keep it from filling
+    step_logits = torch.empty(B, stepper.model.frames, stepper.model.arch.vocab_size, dtype=torch.float32, device=x.device)
+    for _ in range(int(steps)):
+        stepper.step(delta.data, x, labels, logits_out=step_logits)
+    found_step = stepper.best_step[:B].clone()
+    hit = found_step >= 0
+    delta = torch.where(hit[:, None], stepper.best[:B], delta.detach())
+    bound_scale = torch.where(hit, stepper.best_scale[:B], stepper.scale[:B]).cpu()
+    return delta, found_step.cpu(), bound_scale, stepper.scale[:B].cpu()
+
+
+def _run_anneal(stepper, delta, x, labels, steps, refs):
+    """``steps`` steps of the alpha schedule on one batch -> (last iterate, best rows, and on the host: alpha_step, best_loss,
+    best_alpha, last_alpha, l_b of the delta that entered)."""
+    B = x.shape[0]
+    stepper.set_refs(refs)
+    stepper.anneal_reset(B)
+    stepper.stats_log.cursor.zero_()
+    step_logits = torch.empty(B, stepper.model.frames, stepper.model.arch.vocab_size, dtype=torch.float32, device=x.device)
+    entered = None
+    for i in range(int(steps)):
+        stepper.step(delta.data, x, labels, logits_out=step_logits)
+        if i == 0:
+            entered = stepper.mask_rows[:B].clone()
+    return (delta.detach(), stepper.best[:B].clone(), stepper.best_step[:B].cpu(), stepper.best_loss[:B].cpu(),
+            stepper.best_alpha[:B].cpu(), stepper.alpha_rows[:B].cpu(), entered.cpu())
 
 
 def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper=None, lengths=None):
@@ -156,9 +233,11 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
     record's norms and SNR are those of delta_b[:len_b] against x_b[:len_b].  With --bound_search shrink the delta returned,
     scored and composed is the REPORTED one: ``best_b`` of a clip that fell, the last iterate of the others."""
     B, L = x.shape
-    search = None
+    search = anneal = None
     if modes.Modes.of(args).search_on:       # refusals first: before any launch of the batch
         search, canon, search_refs = search_route(args, processor, texts)
+    if modes.Modes.of(args).anneal_on:
+        anneal, canon, search_refs = anneal_route(args, processor, texts)
     labels = loss_helpers.make_labels(texts, processor, args, B)
     delta = torch.from_numpy(init_rows(L, idx, int(args.seed))).to(x.device)
     frames, blank = None, int(model.arch.pad_token_id)
@@ -169,30 +248,44 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
     elif model.lengths_on:
         model.set_lengths(None)
     project_rows(delta, x, args, interp, spl_thresh, lengths)             # build.py:301-304, per clip
-    skw = {} if search is None else dict(device_wer=True, canon=canon, search=search)      # the search runs on the device WER route
-    if args.optimizer_type == "adam":
-        optimizer = torch.optim.Adam([delta], lr=args.lr)
-        stepper = ClipStepper(model, args, L, interp, spl_thresh, optimizer=optimizer, **skw)
-    elif stepper is None:
-        stepper = ClipStepper(model, args, L, interp, spl_thresh, **skw)
-    if search is None:
-        for _ in range(int(args.pgd_steps)):
-            stepper.step(delta.data, x, labels, want_logits=False)          # reads the model's length buffer, set above
-        delta = delta.detach()
+    steps, stage1 = int(args.pgd_steps), 0
+    if anneal is None:
+        skw = {} if search is None else dict(device_wer=True, canon=canon, search=search)      # the search runs on the device WER route
+        if args.optimizer_type == "adam":
+            optimizer = torch.optim.Adam([delta], lr=args.lr)
+            stepper = ClipStepper(model, args, L, interp, spl_thresh, optimizer=optimizer, **skw)
+        elif stepper is None:
+            stepper = ClipStepper(model, args, L, interp, spl_thresh, **skw)
+        if search is None:
+            for _ in range(steps):
+                stepper.step(delta.data, x, labels, want_logits=False)          # reads the model's length buffer, set above
+            delta = delta.detach()
+        else:
+            delta, found_step, bound_scale, last_scale = _run_search(stepper, delta, x, labels, steps, search_refs)
     else:
-        stepper.set_refs(search_refs)
-        stepper.search_reset(B)
-        stepper.stats_log.cursor.zero_()                                    # nobody reads the per-step log here: keep it from filling
-        step_logits = torch.empty(B, model.frames, model.arch.vocab_size, dtype=torch.float32, device=x.device)
-        for _ in range(int(args.pgd_steps)):
-            stepper.step(delta.data, x, labels, logits_out=step_logits)
-        found_step = stepper.best_step[:B].clone()
-        hit = found_step >= 0
-        delta = torch.where(hit[:, None], stepper.best[:B], delta.detach())
-        bound_scale = torch.where(hit, stepper.best_scale[:B], stepper.scale[:B]).cpu()
-        last_scale, found_step = stepper.scale[:B].cpu(), found_step.cpu()
+        adam = args.optimizer_type == "adam"
+        akw = dict(device_wer=True, canon=canon, anneal=anneal)
+        if search is not None:       # stage 1: the bound search as it runs alone, the masking loss off (steppers of a batch: not reused)
+            stage1 = modes.stage1_of(getattr(args, "stage1_steps", None), steps)
+            args1 = copy.copy(args)
+            args1.masking_loss_alpha = 0.0
+            st1 = ClipStepper(model, args1, L, interp, spl_thresh, optimizer=torch.optim.Adam([delta], lr=args.lr) if adam else None,
+                              device_wer=True, canon=canon, search=search)
+            delta, found_step, bound_scale, last_scale = _run_search(st1, delta, x, labels, stage1, search_refs)
+            entered_delta = delta.clone()                        # stage 2 starts from the stage-1 reported delta ...
+            akw["bound_scale"] = bound_scale.to(x.device)        # ... under the bound that delta satisfies
+            stepper = None
+        if adam or stepper is None or stepper.anneal != anneal:
+            stepper = ClipStepper(model, args, L, interp, spl_thresh, optimizer=torch.optim.Adam([delta], lr=args.lr) if adam else None,
+                                  **akw)
+        last, best, alpha_step, best_loss, best_alpha, last_alpha, entered_loss = _run_anneal(stepper, delta, x, labels, steps - stage1,
+                                                                                             search_refs)
+        kept = (alpha_step >= 0).to(x.device)
+        if search is not None:       # a clip stage 2 never kept keeps its stage-1 best, where there is one
+            last = torch.where((found_step >= 0).to(x.device)[:, None], entered_delta, last)
+        delta = torch.where(kept[:, None], best, last)
     clean_out = model.forward(x, None, labels)
-    if search is None:
+    if search is None and anneal is None:
         adv_out = model.forward(x, delta, labels, clamp=True)
     else:       # ``found`` came from the step's own forward pass: score the reported delta through the very call the step makes
         adv_out = model.fwd_bwd(x, delta, labels, stepper.direction, want_grad=False, want_logits=True)
@@ -233,6 +326,12 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
         if search is not None:
             rec |= {"found": bool(found_step[b] >= 0), "found_step": int(found_step[b]), "bound_scale": float(bound_scale[b]),
                     "last_scale": float(last_scale[b])}
+        if anneal is not None:
+            ok = bool(alpha_step[b] >= 0)
+            rec |= {"alpha_found": ok, "alpha_step": int(alpha_step[b]), "best_masking_loss": float(best_loss[b]) if ok else float("nan"),
+                    "best_alpha": float(best_alpha[b] if ok else last_alpha[b]), "last_alpha": float(last_alpha[b])}
+            if search is not None:
+                rec[STAGE1_FIELD] = float(entered_loss[b])
         records.append(rec)
     return records, delta, compose_rows(x, delta, lengths), stepper
 
@@ -241,6 +340,7 @@ def main(args) -> int:
     # what per-clip perturbations do not run with, and the refusals of --clip_lengths true: before any launch or collective
     lengths_mode = modes.check(modes.Modes.of(args), ("place_clips", "rir_clips", "chan_range", "chan_clips") + modes.LENGTHS).lengths_on
     modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS + modes.MARGIN, modes.Ctx(search=modes.SearchConfig.of(args)))
+    modes.check(modes.Modes.of(args), modes.ANNEAL_FLAGS, modes.anneal_ctx(args))
     if not torch.cuda.is_available():
         raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")
     if not str(args.device).startswith("cuda"):

@@ -3,6 +3,7 @@ default frame geometry (n_fft = win_length = 1024, hop_length = 256), computed b
 CPU fallback."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .. import _lib, runtime
@@ -30,11 +31,28 @@ def masking_threshold(clean: torch.Tensor, args, psd: bool = False):
     return (theta, pmax, pb) if psd else (theta, pmax)
 
 
-def masking_loss(delta: torch.Tensor, clean: torch.Tensor, args, grad: bool = False):
+def _alpha_dev(alpha, B, dev):
+    """Per-clip weights as a float32 (B) device tensor.  A host array is validated (finite, >= 0); a device tensor is taken as it
+    is."""
+    if isinstance(alpha, torch.Tensor) and alpha.is_cuda:
+        if alpha.dtype != torch.float32 or alpha.dim() != 1 or alpha.numel() != B or not alpha.is_contiguous():
+            raise ValueError(f"alpha must be a contiguous float32 tensor of {B} elements, got {alpha.dtype} {tuple(alpha.shape)}")
+        return alpha.to(dev)
+    a = np.asarray(alpha.cpu() if isinstance(alpha, torch.Tensor) else alpha, dtype=np.float64).reshape(-1)
+    if a.size != B:
+        raise ValueError(f"alpha must hold one value per clip ({B}), got {a.size}")
+    if not (np.isfinite(a).all() and (a >= 0).all()):
+        raise ValueError(f"every alpha must be finite and >= 0, got {a.tolist()}")
+    return torch.from_numpy(a.astype(np.float32)).to(dev)
+
+
+def masking_loss(delta: torch.Tensor, clean: torch.Tensor, args, grad: bool = False, alpha=None):
     """The masking-threshold loss term of ``delta`` against the clean clips ``clean`` (B, L):
     l_b = 1 / (T F) sum_{t,k} max(c_b |STFT(delta)|^2 - 10^((theta_b + masking_margin_db) / 10), 0).  ``delta`` is (1, L) or
     (L,) (the one row against every clip) or (B, L) (row b against clip b).  Returns (loss_rows (B,), grad or None): with
-    ``grad=True`` the gradient of sum_b l_b itself, shaped like ``delta`` (alpha = 1, positive, not subtracted)."""
+    ``grad=True`` the gradient of sum_b l_b itself, shaped like ``delta`` (alpha = 1, positive, not subtracted).  ``alpha``: a (B,)
+    host array or device tensor of per-clip weights, for a (B, L) ``delta`` only (paa_masking_loss_rows): gradient
+    row b is then alpha_b grad l_b; the losses stay unweighted."""
     x = runtime.as_f32_cuda(clean, "clean_audio")
     d = runtime.as_f32_cuda(delta, "delta")
     if x.dim() == 1:
@@ -46,6 +64,14 @@ def masking_loss(delta: torch.Tensor, clean: torch.Tensor, args, grad: bool = Fa
     pr = runtime.get_proj(args, x.device, B, L)
     rows = torch.empty(B, dtype=torch.float32, device=x.device)
     g = torch.zeros_like(d2) if grad else None
+    if alpha is not None:
+        if d2.shape[0] != B:
+            raise ValueError(f"per-clip alpha needs one perturbation row per clip: delta {tuple(d.shape)}, clean_audio {tuple(x.shape)}")
+        al = _alpha_dev(alpha, B, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().paa_masking_loss_rows(pr.h, runtime.params_of(args, "masking"), _lib.ptr(d2), B, _lib.ptr(x), B, L,
+                                                        _lib.ptr(al), B, _lib.ptr(g), _lib.ptr(rows), None, None, _lib.stream_ptr()))
+        return rows, None if g is None else g.neg_().view_as(d)
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().paa_masking_loss(pr.h, runtime.params_of(args, "masking"), _lib.ptr(d2), d2.shape[0], _lib.ptr(x), B, L,
                                                None, _lib.ptr(g), _lib.ptr(rows), None, None, _lib.stream_ptr()))

@@ -1009,12 +1009,16 @@ extern "C" paa_status paa_spectrum_project(paa_proj* h, const paa_params* prm, c
 // Masking-threshold loss: passes 1 and 2 leave every clip's bound A_b in h->d_mask and Pmax_b in the idle frame
 // workspace, then ONE fused launch (k_spec_mloss) and the loss partials' finishing launch.  Frame workspace: [B x parts doubles:
 // loss partials | B doubles: finishing scratch | B floats: Pmax].
-extern "C" paa_status paa_masking_loss(paa_proj* h, const paa_params* prm, const float* d_p, int p_rows, const float* d_clean, int B,
-                                       int L, const float* d_alpha, float* d_grad, float* d_loss_rows, float* d_loss_sum,
-                                       float* d_weight, void* stream) {
-    if (!h || !prm || !d_p) PAA_FAIL(PAA_ERR_ARG, "paa_masking_loss: null argument");
+// alpha_rows = 1: one weight (d_alpha [1], NULL = 1.0), paa_masking_loss itself; alpha_rows = p_rows = B: row b's own weight.
+static paa_status masking_loss_entry(paa_proj* h, const paa_params* prm, const float* d_p, int p_rows, const float* d_clean, int B, int L,
+                                     const float* d_alpha, int alpha_rows, float* d_grad, float* d_loss_rows, float* d_loss_sum,
+                                     float* d_weight, void* stream, const char* who) {
+    if (!h || !prm || !d_p) PAA_FAIL(PAA_ERR_ARG, "%s: null argument", who);
     if (!d_clean || B < 1) PAA_FAIL(PAA_ERR_NEED_CLEAN, "the masking loss requires clean_audio");
-    if (p_rows != 1 && p_rows != B) PAA_FAIL(PAA_ERR_ARG, "paa_masking_loss: p_rows=%d must be 1 or B=%d", p_rows, B);
+    if (p_rows != 1 && p_rows != B) PAA_FAIL(PAA_ERR_ARG, "%s: p_rows=%d must be 1 or B=%d", who, p_rows, B);
+    if (alpha_rows != 1 && !(alpha_rows == B && p_rows == B))
+        PAA_FAIL(PAA_ERR_ARG, "%s: alpha_rows=%d must be 1, or B=%d with p_rows=B (p_rows=%d)", who, alpha_rows, B, p_rows);
+    if (alpha_rows != 1 && !d_alpha) PAA_FAIL(PAA_ERR_ARG, "%s: alpha_rows=%d needs d_alpha", who, alpha_rows);
     hipStream_t st = (hipStream_t)stream;
     const int T = 1 + L / h->hop;
     const int parts = spec_mloss_parts(T);
@@ -1022,15 +1026,29 @@ extern "C" paa_status paa_masking_loss(paa_proj* h, const paa_params* prm, const
     double* scratch = lpart + (size_t)B * parts;
     float* pmax = reinterpret_cast<float*>(scratch + B);
     if (B <= h->max_batch && ((size_t)B * (parts + 1)) * 2 + B > h->frames_floats)
-        PAA_FAIL(PAA_ERR_SIZE, "paa_masking_loss: workspace too small");
+        PAA_FAIL(PAA_ERR_SIZE, "%s: workspace too small", who);
     PAA_TRY(masking_pass(h, d_clean, B, L, prm->masking_margin_db, nullptr, nullptr, pmax, false, st));
     SpecArgs a = spec_args(h, L, T, L);
     a.x = d_p; a.mask = h->d_mask; a.mask_rs = (int64_t)T * h->F;
-    a.pmax = pmax; a.alpha = d_alpha; a.grad = d_grad; a.wout = d_weight; a.lpart = lpart;
+    a.pmax = pmax; a.alpha = d_alpha; a.alpha_rs = alpha_rows == 1 ? 0 : 1; a.grad = d_grad; a.wout = d_weight; a.lpart = lpart;
     a.nclip = p_rows == 1 ? B : 1; a.per_clip = p_rows == 1 ? 0 : 1; a.lstride = parts;
     PAA_TRY(spec_mloss(a, p_rows, st));
     if (d_loss_rows || d_loss_sum) PAA_TRY(spec_mloss_finish(lpart, parts, B, scratch, d_loss_rows, d_loss_sum, st));
     return PAA_OK;
+}
+
+extern "C" paa_status paa_masking_loss_rows(paa_proj* h, const paa_params* prm, const float* d_p, int p_rows, const float* d_clean,
+                                            int B, int L, const float* d_alpha, int alpha_rows, float* d_grad, float* d_loss_rows,
+                                            float* d_loss_sum, float* d_weight, void* stream) {
+    return masking_loss_entry(h, prm, d_p, p_rows, d_clean, B, L, d_alpha, alpha_rows, d_grad, d_loss_rows, d_loss_sum, d_weight, stream,
+                              "paa_masking_loss_rows");
+}
+
+extern "C" paa_status paa_masking_loss(paa_proj* h, const paa_params* prm, const float* d_p, int p_rows, const float* d_clean, int B,
+                                       int L, const float* d_alpha, float* d_grad, float* d_loss_rows, float* d_loss_sum,
+                                       float* d_weight, void* stream) {
+    return masking_loss_entry(h, prm, d_p, p_rows, d_clean, B, L, d_alpha, 1, d_grad, d_loss_rows, d_loss_sum, d_weight, stream,
+                              "paa_masking_loss");
 }
 
 extern "C" paa_status paa_masking_threshold(paa_proj* h, const float* d_clean, int B, int L, float* d_psd, float* d_theta,

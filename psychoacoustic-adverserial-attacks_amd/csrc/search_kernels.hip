@@ -47,7 +47,39 @@ __global__ void __launch_bounds__(SEARCH_NT) k_search_decide(const int32_t* __re
     if (threadIdx.x == 0) *step_ctr = step + 1;
 }
 
-// grid (chunks, B): row blockIdx.y, flag uniform over the block.  16-byte accesses where both row bases are aligned (L odd
+// Per-clip adaptive masking-loss weight: the decide kernel of paa_clip_anneal.  Same success test, same shape
+// (ONE workgroup, one flag per row for k_search_keep), but the row is kept only where its masking loss improves on the best so far
+// (strict f32 compare: a NaN loss never keeps, an equal loss keeps the earlier delta), and alpha moves on the periods of n = step + 1:
+//     keep   success && l < best_loss[b]      best_loss[b] <- l;  best_alpha[b] <- alpha[b];  best_step[b] <- step;  flag (row copy)
+//     raise  success && n % up_every == 0     alpha[b] <- fminf(fmaxf(alpha[b] * up, alpha_min), alpha_max)
+//     lower  !success && n % down_every == 0  alpha[b] <- fminf(fmaxf(alpha[b] * down, alpha_min), alpha_max)
+// best_alpha is the alpha the kept delta was optimised under: it is read before alpha moves.
+__global__ void __launch_bounds__(SEARCH_NT) k_anneal_decide(const int32_t* __restrict__ counts, const float* __restrict__ loss_rows,
+                                                             int B, int targeted, int wer_milli, int up_every, int down_every, float up,
+                                                             float down, float alpha_min, float alpha_max, float* __restrict__ alpha,
+                                                             float* __restrict__ best_loss, float* __restrict__ best_alpha,
+                                                             int32_t* __restrict__ best_step, int32_t* __restrict__ step_ctr) {
+    const int32_t step = *step_ctr;
+    const int64_t n = (int64_t)step + 1;
+    const bool up_now = n % up_every == 0, down_now = n % down_every == 0;
+    for (int b = threadIdx.x; b < B; b += SEARCH_NT) {
+        const int32_t e = counts[3 * b], w = counts[3 * b + 1];
+        const bool ok = targeted ? (e == 0 && w > 0) : (w > 0 && (int64_t)e * 1000 >= (int64_t)wer_milli * w);
+        const float l = loss_rows[b], a = alpha[b];
+        const bool keep = ok && l < best_loss[b];
+        g_search_flag[b] = keep ? 1 : 0;
+        if (keep) {
+            best_loss[b] = l;
+            best_alpha[b] = a;
+            best_step[b] = step;
+        }
+        if (ok ? up_now : down_now) alpha[b] = fminf(fmaxf(a * (ok ? up : down), alpha_min), alpha_max);
+    }
+    __syncthreads();                          // every thread has read the counter
+    if (threadIdx.x == 0) *step_ctr = step + 1;
+}
+
+// grid (chunks, B): row blockIdx.y, flag uniform over the block. 16-byte accesses where both row bases are aligned (L odd
 // misaligns every second row), element by element otherwise.
 __global__ void __launch_bounds__(SEARCH_NT) k_search_keep(const float* __restrict__ delta, float* __restrict__ best, int L) {
     const int b = blockIdx.y;
@@ -82,6 +114,31 @@ extern "C" paa_status paa_clip_search(const float* d_delta, int B, int L, const 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_search_decide, dim3(1), dim3(SEARCH_NT), 0, st, d_counts, B, targeted ? 1 : 0, wer_milli, shrink,
                        floor_scale, d_scale, d_best_scale, d_best_step, d_step);
+    PAA_LAUNCH_CHECK();
+    const int chunks = std::min(cdiv(L, KEEP_CHUNK), KEEP_MAX_CHUNKS);
+    hipLaunchKernelGGL(k_search_keep, dim3(chunks, B), dim3(SEARCH_NT), 0, st, d_delta, d_best, L);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
+extern "C" paa_status paa_clip_anneal(const float* d_delta, int B, int L, const int32_t* d_counts, const float* d_loss_rows, int targeted,
+                                      int wer_milli, int up_every, int down_every, float up, float down, float alpha_min,
+                                      float alpha_max, float* d_alpha, float* d_best, float* d_best_loss, float* d_best_alpha,
+                                      int32_t* d_best_step, int32_t* d_step, void* stream) {
+    if (!d_delta || !d_counts || !d_loss_rows || !d_alpha || !d_best || !d_best_loss || !d_best_alpha || !d_best_step || !d_step)
+        PAA_FAIL(PAA_ERR_ARG, "paa_clip_anneal: null argument");
+    if (B < 1 || L < 1) PAA_FAIL(PAA_ERR_ARG, "paa_clip_anneal: B=%d L=%d (>= 1 each)", B, L);
+    if (B > SEARCH_MAX_B) PAA_FAIL(PAA_ERR_ARG, "paa_clip_anneal: B=%d exceeds %d", B, SEARCH_MAX_B);
+    if (wer_milli < 1) PAA_FAIL(PAA_ERR_ARG, "paa_clip_anneal: wer_milli=%d (>= 1)", wer_milli);
+    if (up_every < 1 || down_every < 1)
+        PAA_FAIL(PAA_ERR_ARG, "paa_clip_anneal: up_every=%d down_every=%d (>= 1 each)", up_every, down_every);
+    if (!(up > 1.0f && up < INFINITY)) PAA_FAIL(PAA_ERR_ARG, "paa_clip_anneal: up=%g must be finite and > 1", (double)up);
+    if (!(down > 0.0f && down < 1.0f)) PAA_FAIL(PAA_ERR_ARG, "paa_clip_anneal: down=%g outside (0, 1)", (double)down);
+    if (!(alpha_min > 0.0f && alpha_min <= alpha_max && alpha_max < INFINITY))
+        PAA_FAIL(PAA_ERR_ARG, "paa_clip_anneal: need 0 < alpha_min=%g <= alpha_max=%g < inf", (double)alpha_min, (double)alpha_max);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_anneal_decide, dim3(1), dim3(SEARCH_NT), 0, st, d_counts, d_loss_rows, B, targeted ? 1 : 0, wer_milli, up_every,
+                       down_every, up, down, alpha_min, alpha_max, d_alpha, d_best_loss, d_best_alpha, d_best_step, d_step);
     PAA_LAUNCH_CHECK();
     const int chunks = std::min(cdiv(L, KEEP_CHUNK), KEEP_MAX_CHUNKS);
     hipLaunchKernelGGL(k_search_keep, dim3(chunks, B), dim3(SEARCH_NT), 0, st, d_delta, d_best, L);

@@ -30,11 +30,12 @@ struct SpecArgs {
     // MLOSS (spec_mloss): x = the perturbation rows, mask / mask_rs = every clip's bound A_b; a row is held against `nclip` clips
     // starting at clip (per_clip ? row : 0)
     const float* pmax;     // (clips) Pmax_b of the clean clips
-    const float* alpha;    // device [1], nullable (1.0)
+    const float* alpha;    // device [1] (alpha_rs = 0) or (rows) (alpha_rs = 1: row r reads alpha[r]), nullable (1.0)
     float* grad;           // (rows, L): grad -= alpha * dloss; nullable (losses only)
     float* wout;           // (rows, T, F) hinge weight W; nullable
     double* lpart;         // loss partials, (clips, lstride): one double per (clip, workgroup, wave)
     int nclip, per_clip, lstride;
+    int alpha_rs;          // stride of alpha over the rows: 0 or 1 (paa_masking_loss_rows)
     const float* rscale;   // PHON, row projections: (rows) per-row bound scale s, nullable; the threshold moves by 20 log10(s) dB
 };
 

@@ -664,7 +664,7 @@ __global__ __launch_bounds__(256) void k_spec_psd(SpecArgs a) {
 // the gradient.  The slab shape of k_spec_fused: MLOSS_NW waves, one frame each, the windowed frames w 1024 irfft(H) left in LDS.
 // The adjoint tail differs from the iSTFT tail three ways: no division by the window envelope, no trimming — the reflect padding's
 // gradient is FOLDED onto the samples it mirrors (padded index 512 - i onto sample i, L + 511 + i onto L - 1 - i, i = 1 .. 512) —
-// and the result is subtracted, times alpha, from grad (each sample is owned by one thread of one workgroup).
+// and the result is subtracted, times alpha (the row's own with alpha_rs = 1), from grad (each sample is owned by one thread of one workgroup).
 // Output sample m lies in padded hop-block 2 + m / 256, blocks 2 .. T + 1; block j is the sum of frames j-3 .. j.  Workgroup g
 // holds frames c0 - 3 .. c0 + 4 and owns blocks [lo, hi):  T <= 8: ONE workgroup, c0 = 3 (slot f = frame f), all blocks;  else
 // c0 = 2 + 5 g and 5 blocks, but the LAST workgroup is shifted to c0 = T - 3 and owns T - 3 .. T + 1 (the one before it stops
@@ -715,7 +715,7 @@ __global__ __launch_bounds__(MLOSS_NW * 64) void k_spec_mloss(SpecArgs a) {
         }
         return s;
     };
-    const float alpha = a.alpha ? a.alpha[0] : 1.f;
+    const float alpha = a.alpha ? a.alpha[row * a.alpha_rs] : 1.f;      // row = blockIdx.y: uniform, a scalar load
     float* gr = a.grad + (size_t)row * a.L;
     for (int i = tid; i < (hi - lo) * HOP; i += NW * 64) {
         const int m = HOP * (lo - 2) + i;                     // sample of the row

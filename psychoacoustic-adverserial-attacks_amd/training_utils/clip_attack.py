@@ -21,6 +21,13 @@ Bound search: with ``search=SearchConfig(...)`` every clip carr
 ``paa_clip_search`` sits between the device WER counters and the update: a clip whose counters say "success" has its delta_b (the
 one that entered the step), s_b and the step number kept in ``best`` / ``best_scale`` / ``best_step`` and its s_b shrunk; the
 projections then run as ``paa_project_rows_scaled`` under the new scales.  No host sync, so the step stays one capturable sequence.
+
+Adaptive masking-loss weight: with ``anneal=AnnealConfig(...)`` every clip carries its own alpha_b (alpha0 =
+``masking_loss_alpha`` after ``anneal_reset``).  The masking loss runs as ``paa_masking_loss_rows`` with ``alpha_rows``, and
+``paa_clip_anneal`` sits where the bound search would: a successful clip whose l_b improves on its best has delta_b, l_b, alpha_b and
+the step kept in ``best`` / ``best_loss`` / ``best_alpha`` / ``best_step``; alpha_b rises on success and falls on failure, on the
+periods of the config.  ``bound_scale`` (B, device) fixes per-clip bound scales nothing writes (``paa_project_rows_scaled``): the
+scales stage 1 of the two-stage run found.
 """
 from __future__ import annotations
 
@@ -28,7 +35,8 @@ import numpy as np
 import torch
 
 from .. import _lib, runtime, synth
-from .modes import LENGTHS, SEARCH_FLAGS, Ctx, Modes, SearchConfig, check, replace  # noqa: F401  (SearchConfig: re-exported)
+from .modes import (LENGTHS, SEARCH_FLAGS, AnnealConfig, Ctx, Modes, SearchConfig, check,  # noqa: F401  (configs: re-exported)
+                    replace)
 from .pgd import N_STATS, ST_LOSS, _StepperCore
 
 
@@ -36,12 +44,25 @@ class ClipStepper(_StepperCore):
     """The per-clip step: ``step(delta, clean, labels)`` updates ``delta`` (B, L) in place, row b from clip b alone."""
 
     def __init__(self, model, args, length: int, interp=None, spl_thresh=None, optimizer=None, device_wer=False, canon=None,
-                 r_cap=None, log_cap=4096, search=None):
+                 r_cap=None, log_cap=4096, search=None, anneal=None, bound_scale=None):
         """``device_wer`` / ``canon`` / ``r_cap`` / ``log_cap`` as PgdStepper's; ``wer_rows[:B]`` keeps the per-clip (errors,
         reference words, hypothesis words) of the last step.  ``search``: a ``SearchConfig`` switches the per-clip bound search on
         (module docstring); it needs ``device_wer=True``, and ``refs`` are then the transcripts success is judged against (the
-        target transcript in targeted mode).  Call ``search_reset(B)`` before the first step of every batch."""
-        self.search = search
+        target transcript in targeted mode).  Call ``search_reset(B)`` before the first step of every batch.  ``anneal``: an
+        ``AnnealConfig`` switches the per-clip alpha schedule on (module docstring); it needs ``device_wer=True`` and
+        ``masking_loss_alpha`` > 0 (alpha0), and excludes ``search``.  Call ``anneal_reset(B)`` before the first step of every batch.
+        ``bound_scale``: a float32 (B) device tensor of fixed per-clip bound scales for the projections."""
+        self.search, self.anneal = search, anneal
+        if anneal is not None:
+            if search is not None:
+                raise ValueError("anneal and search cannot share a stepper: the two-stage run uses one stepper per stage")
+            m = replace(Modes.of(args), anneal_on=True)
+            check(m, ("anneal_alpha0", "anneal_range"), Ctx(anneal=anneal, alpha0=m.alpha))
+            if not device_wer:
+                raise ValueError("the alpha schedule decides success from the on-device WER counters: build the stepper with "
+                                 "device_wer=True")
+        if bound_scale is not None and search is not None:
+            raise ValueError("bound_scale fixes the scales the bound search would move: pass one or the other")
         if search is not None:
             check(replace(Modes.of(args), search_on=True), SEARCH_FLAGS, Ctx(search=search))
             if not device_wer:
@@ -61,6 +82,35 @@ class ClipStepper(_StepperCore):
             self.best_scale = torch.ones(nb, dtype=torch.float32, device=self.dev)     # ... the scale it was projected under
             self.best_step = torch.full((nb,), -1, dtype=torch.int32, device=self.dev)  # ... its step, -1: no success yet
             self.search_step = torch.zeros(1, dtype=torch.int32, device=self.dev)      # device step counter
+        if anneal is not None:
+            nb = self.max_batch
+            self.alpha_rows = torch.full((nb,), self.mask_alpha, dtype=torch.float32, device=self.dev)   # alpha_b of the next step
+            self.best = torch.zeros(nb, self.L, dtype=torch.float32, device=self.dev)  # delta_b of clip b's least audible success
+            self.best_loss = torch.full((nb,), float("inf"), dtype=torch.float32, device=self.dev)   # ... its l_b
+            self.best_alpha = torch.zeros(nb, dtype=torch.float32, device=self.dev)    # ... the alpha it was optimised under
+            self.best_step = torch.full((nb,), -1, dtype=torch.int32, device=self.dev)  # ... its step, -1: none kept yet
+            self.anneal_step = torch.zeros(1, dtype=torch.int32, device=self.dev)      # device step counter
+        self.bound_scale = None
+        if bound_scale is not None:
+            if not (isinstance(bound_scale, torch.Tensor) and bound_scale.is_cuda):
+                raise ValueError("bound_scale must be a float32 (B) device tensor: the step reads it on the stream")
+            self.bound_scale = _scale_dev(bound_scale, 1, self.dev)
+
+    def anneal_reset(self, B=None):
+        """A new batch: alpha_rows = alpha0, best_loss = +inf, best_step = -1, step = 0 (stream-ordered fills, outside any graph).
+        ``best`` rows and ``best_alpha`` need no reset: they are read only where best_step >= 0."""
+        if self.anneal is None:
+            raise RuntimeError("the stepper was built without an alpha schedule (anneal=AnnealConfig(...))")
+        B = self.max_batch if B is None else int(B)
+        self.alpha_rows[:B].fill_(self.mask_alpha)
+        self.best_loss[:B].fill_(float("inf"))
+        self.best_step[:B].fill_(-1)
+        self.anneal_step.zero_()
+
+    def set_masking_alpha(self, alpha: float):
+        if getattr(self, "anneal", None) is not None and not float(alpha) > 0:
+            raise ValueError("the alpha schedule needs masking_loss_alpha > 0: that value is the weight every clip starts from")
+        super().set_masking_alpha(alpha)
 
     def search_reset(self, B=None):
         """A new batch: scale = 1, best_step = -1, step = 0 (stream-ordered fills, outside any graph).  ``best`` rows and
@@ -77,6 +127,8 @@ class ClipStepper(_StepperCore):
         st = super()._replay_state()
         if self.search is not None:
             st += [self.scale, self.best, self.best_scale, self.best_step, self.search_step]
+        if self.anneal is not None:
+            st += [self.alpha_rows, self.best, self.best_loss, self.best_alpha, self.best_step, self.anneal_step]
         return st
 
     def _check_adam_shape(self):
@@ -103,8 +155,9 @@ class ClipStepper(_StepperCore):
         if logits_out is not None:
             out["logits"] = logits_out
         r = self.model.fwd_bwd(clean, delta, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
+        ac = self.anneal
         if self.mask_alpha > 0:
-            self._masking_loss(delta, clean, grad, self.mask_rows[:B])
+            self._masking_loss(delta, clean, grad, self.mask_rows[:B], None if ac is None else self.alpha_rows)
             r["masking_loss"] = self.mask_rows[:B]
         if self.device_wer:
             self._wer(r["logits"], B)
@@ -116,11 +169,20 @@ class ClipStepper(_StepperCore):
                                                int(sc.wer_milli), float(sc.shrink), float(sc.floor_scale), _lib.ptr(self.scale),
                                                _lib.ptr(self.best), _lib.ptr(self.best_scale), _lib.ptr(self.best_step),
                                                _lib.ptr(self.search_step), st))
+            if ac is not None:       # ... and so is l_b: the delta kept is the delta judged
+                _lib.check(lib.paa_clip_anneal(_lib.ptr(delta), B, L, _lib.ptr(self.wer_rows), _lib.ptr(self.mask_rows),
+                                               int(bool(ac.targeted)), int(ac.wer_milli), int(ac.up_every), int(ac.down_every),
+                                               float(ac.up), float(ac.down), float(ac.alpha_min), float(ac.alpha_max),
+                                               _lib.ptr(self.alpha_rows), _lib.ptr(self.best), _lib.ptr(self.best_loss),
+                                               _lib.ptr(self.best_alpha), _lib.ptr(self.best_step), _lib.ptr(self.anneal_step), st))
             self._update(delta, grad, B * L)
+            scale = self.scale if sc is not None else self.bound_scale
+            if scale is not None and scale.numel() < B:
+                raise ValueError(f"bound_scale holds {scale.numel()} values, the batch has {B} clips")
             for prm in self._prm:
-                if sc is not None:
+                if scale is not None:
                     _lib.check(lib.paa_project_rows_scaled(self.proj.h, prm, _lib.ptr(delta), _lib.ptr(delta), B, _lib.ptr(clean),
-                                                           L, _lib.ptr(self.scale), st))
+                                                           L, _lib.ptr(scale), st))
                 else:
                     _lib.check(lib.paa_project_rows(self.proj.h, prm, _lib.ptr(delta), _lib.ptr(delta), B, _lib.ptr(clean), L, st))
                 if self.lengths_on:
@@ -150,9 +212,10 @@ class ClipStepper(_StepperCore):
         wrapped so that every replay first pushes the step's scalars, and the warm-up step is undone (delta, moments and step
         count as before the call).  With a bound search the warm-up step is undone with either update — delta and the search
         buffers (scale, best, best_scale, best_step, step) are as before the call, so the first replay is the step an eager
-        call would have been."""
+        call would have been.  The same holds for the alpha schedule and its buffers (alpha_rows, best, best_loss, best_alpha,
+        best_step, step)."""
         delta, clean = self._checked(delta, clean)
-        keep = delta.detach().clone() if self.search is not None else None
+        keep = delta.detach().clone() if self.search is not None or self.anneal is not None else None
         lab, logits_out = self._warm_up(delta, clean, labels, logits_out, refs, lengths)
         if keep is not None:
             delta.detach().copy_(keep)

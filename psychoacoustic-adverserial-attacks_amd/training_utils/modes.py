@@ -50,6 +50,7 @@ class Modes:
     loss_type: str = "ctc"         # --loss_type: "ctc" or "margin" (the alignment-margin loss)
     kappa: float = 1.0             # --margin_kappa, in logits
     targeted: bool = False         # --attack_mode targeted
+    anneal_on: bool = False        # --alpha_search other than "off" (attack_clips only)
     search_on: bool = False        # --bound_search other than "off" (attack_clips only)
 
     @classmethod
@@ -63,7 +64,7 @@ class Modes:
         return cls(norms, "masking" in norms, alpha, on, shift, gain, str(get("rir_bank", "none")) != "none",
                    str(get("clip_lengths", "padded")) == "true", bool(get("device_wer", False)), get("optimizer_type", None),
                    drift_ppm=_num(get("drift_ppm", 0.0) or 0.0), noise_snr=_pair(get("noise_snr_db", None)),
-                   search_on=str(get("bound_search", "off")) != "off", loss_type=str(get("loss_type", "ctc")),
+                   search_on=str(get("bound_search", "off")) != "off", anneal_on=str(get("alpha_search", "off")) != "off", loss_type=str(get("loss_type", "ctc")),
                    kappa=_num(get("margin_kappa", 1.0)), targeted=str(get("attack_mode", "untargeted")) == "targeted")
 
     drift_on = property(lambda m: isinstance(m.drift_ppm, float) and m.drift_ppm > 0)
@@ -78,6 +79,12 @@ class Modes:
 SIZED_NORMS = ("l2", "linf", "snr", "tv", "fletcher_munson", "max_phon")      # the norms a bound scale tightens (min_max_freqs has no size)
 
 
+def _wer_milli(args):
+    """--search_success_wer in thousandths (0: not a usable number)."""
+    wer = getattr(args, "search_success_wer", 0.5)
+    return int(round(float(wer) * 1000)) if isinstance(wer, (int, float)) and wer == wer and abs(wer) < 1e6 else 0
+
+
 class SearchConfig(namedtuple("SearchConfig", "shrink floor_scale wer_milli targeted")):
     """The per-clip bound search (DESIGN.md §6j): on success a clip's bound scale is multiplied by ``shrink`` down to ``floor_scale``;
     untargeted success is per-clip WER >= ``wer_milli`` / 1000, targeted success the target transcript exactly."""
@@ -87,9 +94,7 @@ class SearchConfig(namedtuple("SearchConfig", "shrink floor_scale wer_milli targ
         """The flags of ``args`` as they are (the "search_range" rule judges them); None with the search off."""
         if str(getattr(args, "bound_search", "off")) == "off":
             return None
-        wer = getattr(args, "search_success_wer", 0.5)
-        milli = int(round(float(wer) * 1000)) if isinstance(wer, (int, float)) and wer == wer and abs(wer) < 1e6 else 0
-        return cls(getattr(args, "search_shrink", 0.8), getattr(args, "search_floor", 0.01), milli,
+        return cls(getattr(args, "search_shrink", 0.8), getattr(args, "search_floor", 0.01), _wer_milli(args),
                    getattr(args, "attack_mode", "untargeted") == "targeted")
 
     def bad(self):
@@ -104,17 +109,75 @@ class SearchConfig(namedtuple("SearchConfig", "shrink floor_scale wer_milli targ
         return None
 
 
+class AnnealConfig(namedtuple("AnnealConfig", "up down up_every down_every alpha_min alpha_max wer_milli targeted")):
+    """The per-clip masking-loss weight schedule: on success a clip's alpha is multiplied by ``up`` every ``up_every``
+    steps, on failure by ``down`` every ``down_every`` steps, clamped to [``alpha_min``, ``alpha_max``]; success as SearchConfig's."""
+
+    @classmethod
+    def of(cls, args):
+        """The flags of ``args`` as they are (the "anneal_range" rule judges them); None with the schedule off.  A clamp that is not
+        given derives from alpha0 = --masking_loss_alpha: alpha0 / 100 (Qin's floor) and alpha0 * 100."""
+        if str(getattr(args, "alpha_search", "off")) == "off":
+            return None
+        a0 = getattr(args, "masking_loss_alpha", 0.0) or 0.0
+        a0 = float(a0) if isinstance(a0, (int, float)) and not isinstance(a0, bool) else 0.0
+        lo, hi = getattr(args, "alpha_min", None), getattr(args, "alpha_max", None)
+        return cls(getattr(args, "alpha_up", 1.2), getattr(args, "alpha_down", 0.8), getattr(args, "alpha_up_every", 20),
+                   getattr(args, "alpha_down_every", 50), a0 / 100.0 if lo is None else lo, a0 * 100.0 if hi is None else hi,
+                   _wer_milli(args),
+                   getattr(args, "attack_mode", "untargeted") == "targeted")
+
+    def bad(self, alpha0=None):
+        """None, or the first value out of range (the ranges of paa_clip_anneal; with ``alpha0``, the clamps must enclose it)."""
+        num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+        period = lambda v: isinstance(v, int) and not isinstance(v, bool) and v >= 1
+        if not (num(self.up) and 1.0 < self.up < float("inf")):
+            return f"alpha_up must be finite and > 1, got {self.up}"
+        if not (num(self.down) and 0.0 < self.down < 1.0):
+            return f"alpha_down must lie in (0, 1), got {self.down}"
+        if not period(self.up_every):
+            return f"alpha_up_every must be an integer >= 1, got {self.up_every}"
+        if not period(self.down_every):
+            return f"alpha_down_every must be an integer >= 1, got {self.down_every}"
+        if not (num(self.alpha_min) and num(self.alpha_max) and 0.0 < self.alpha_min <= self.alpha_max < float("inf")):
+            return f"need 0 < alpha_min <= alpha_max < inf, got alpha_min {self.alpha_min}, alpha_max {self.alpha_max}"
+        if not (isinstance(self.wer_milli, int) and self.wer_milli >= 1):
+            return "search_success_wer must be at least 0.0005 (it is rounded to thousandths)"
+        if alpha0 is not None and not self.alpha_min <= alpha0 <= self.alpha_max:
+            return (f"the clamps must enclose the starting weight: alpha_min {self.alpha_min} <= masking_loss_alpha {alpha0} <= "
+                    f"alpha_max {self.alpha_max}")
+        return None
+
+
 # eager_adam: torch's own optimizer.step() runs the update, not the device step; L / Lp: clip / perturbation length, where known;
-# search: the SearchConfig of the run; wer_why: why the device WER route is not available (None: it is)
-class Ctx(namedtuple("Ctx", "world eager_adam L Lp search wer_why", defaults=(1, False, None, None, None, None))):
+# search: the SearchConfig of the run; wer_why: why the device WER route is not available (None: it is); anneal: the AnnealConfig of
+# the run; alpha0: the weight the schedule starts from; stage1 / steps: --stage1_steps as given (None: not given) and --pgd_steps
+class Ctx(namedtuple("Ctx", "world eager_adam L Lp search wer_why anneal alpha0 stage1 steps",
+                     defaults=(1, False, None, None, None, None, None, None, None, None))):
     __slots__ = ()
     search_why = property(lambda c: "bound search is on without a SearchConfig" if c.search is None else c.search.bad())
+    anneal_why = property(lambda c: "alpha search is on without an AnnealConfig" if c.anneal is None else c.anneal.bad(c.alpha0))
+    stage1_steps = property(lambda c: stage1_of(c.stage1, c.steps))
+
+
+def stage1_of(stage1, steps):
+    """Steps of stage 1 in the two-stage run: --stage1_steps, or half of --pgd_steps."""
+    return int(steps) // 2 if stage1 is None else stage1
+
+
+def _stage_bad(m, c):
+    both = m.search_on and m.anneal_on
+    if not both:
+        return c.stage1 is not None
+    s = c.stage1_steps
+    return not (isinstance(s, int) and not isinstance(s, bool) and 1 <= s <= int(c.steps) - 1)
 # mode: the field of Modes that must be on for the rule to apply, or None; when(modes, ctx); msg: formatted with m = modes, c = ctx
 Rule = namedtuple("Rule", "mode when exc msg")
 _PAIRS = ": both pair the perturbation's frames with the clean clip's frames"
 _DEVICE_STEP = " the device step: use the defaults of torch.optim.Adam(lr=...) or --optimizer_type pgd"
 _NO_LEN = "--clip_lengths true does not support "
 _SEARCH = "--bound_search shrink "
+_ANNEAL = "--alpha_search qin "
 _UNIVERSAL = "the universal perturbation (paa_amd.run_attack); per-clip perturbations have no "
 NIE = NotImplementedError
 RULES = {
@@ -165,6 +228,17 @@ RULES = {
                            _SEARCH + "needs a norm with a size to shrink; {m.norms} has none"),
     "search_route": Rule("search_on", lambda m, c: c.wer_why is not None, NIE,
                          _SEARCH + "decides success from the on-device WER counters, which are not available: {c.wer_why}"),
+    # per-clip adaptive masking-loss weight
+    "anneal_alpha0": Rule("anneal_on", lambda m, c: not m.alpha > 0, ValueError,
+                          _ANNEAL + "needs --masking_loss_alpha > 0: that value is the weight every clip starts from"),
+    "anneal_range": Rule("anneal_on", lambda m, c: c.anneal is None or c.anneal.bad(c.alpha0) is not None,
+                         ValueError, "{c.anneal_why}"),
+    "anneal_stage": Rule(None, lambda m, c: c.steps is not None and _stage_bad(m, c), ValueError,
+                         "--stage1_steps applies to the two-stage run (--bound_search shrink with --alpha_search qin) and must lie in "
+                         "[1, pgd_steps - 1]: got stage1_steps {c.stage1_steps} with pgd_steps {c.steps}, bound search "
+                         "{m.search_on}, alpha search {m.anneal_on}"),
+    "anneal_route": Rule("anneal_on", lambda m, c: c.wer_why is not None, NIE,
+                         _ANNEAL + "decides success from the on-device WER counters, which are not available: {c.wer_why}"),
     # the alignment-margin loss
     "margin_untargeted": Rule("margin_on", lambda m, c: not m.targeted, ValueError,
                               "--loss_type margin needs --attack_mode targeted: the hinge is flat wherever the aligned class already "
@@ -183,6 +257,17 @@ LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir", "len_chan")
 SEARCH_FLAGS = ("search_range", "search_masking", "search_no_size")       # known from the flags alone
 MARGIN = ("margin_untargeted", "margin_kappa")                            # known from the flags alone
 SEARCH = SEARCH_FLAGS + ("search_route",)                                  # ... and once the vocabulary and the references are known
+
+
+ANNEAL_FLAGS = ("anneal_alpha0", "anneal_range", "anneal_stage")           # known from the flags alone
+ANNEAL = ANNEAL_FLAGS + ("anneal_route",)                                  # ... and once the vocabulary and the references are known
+
+
+def anneal_ctx(args, **kw):
+    """The context the schedule's rules read, from the flags of ``args``."""
+    a0 = Modes.of(args).alpha
+    return Ctx(search=SearchConfig.of(args), anneal=AnnealConfig.of(args), alpha0=a0 if isinstance(a0, float) else None,
+               stage1=getattr(args, "stage1_steps", None), steps=getattr(args, "pgd_steps", None), **kw)
 
 
 def check(m: Modes, keys, c: Ctx = Ctx()) -> Modes:

@@ -36,9 +36,13 @@
     bound search (``search=SearchConfig``;     paa_clip_search                                           after the device WER counters, before
     per-clip step only; needs device WER)                                                                 the update
                                                paa_project_rows_scaled                                    in place of paa_project_rows
+    alpha schedule (``anneal=AnnealConfig``;   paa_masking_loss_rows                                      in place of paa_masking_loss
+    per-clip step only; needs device WER and   paa_clip_anneal                                            after the device WER counters, before
+    ``masking_loss_alpha`` > 0; no search)                                                                the update
+    fixed bound scales (``bound_scale=``)      paa_project_rows_scaled                                    in place of paa_project_rows
 
-A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off, the channel off, lengths off
-and no bound search are the plain step, bit for bit.
+A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off, the channel off, lengths off,
+no bound search and no alpha schedule are the plain step, bit for bit.
 
 Which modes may run together, and which refusal wins when several apply, is decided in one table: training_utils/modes.py.  What
 a mode means is written where it is built: place.py, rir.py (§6g), channel.py (§6k) and chain.py, which orders the
@@ -317,10 +321,17 @@ class _StepperCore:
             self.stats[ST_MASK_LOSS] = 0.0
         self.mask_alpha = alpha
 
-    def _masking_loss(self, p, clean, grad, loss_rows=None):
-        """grad -= alpha * grad(sum_b l_b); sum_b l_b -> slot 6.  p (rows, L), rows in {1, B}."""
+    def _masking_loss(self, p, clean, grad, loss_rows=None, alpha_rows=None):
+        """grad -= alpha * grad(sum_b l_b); sum_b l_b -> slot 6.  p (rows, L), rows in {1, B}.  ``alpha_rows`` (B) on the device: row
+        b's own weight through paa_masking_loss_rows; None is paa_masking_loss with the stepper's scalar."""
         B = clean.shape[0]
         with torch.cuda.device(self.dev):
+            if alpha_rows is not None:
+                _lib.check(_lib.lib().paa_masking_loss_rows(self.proj.h, self._mask_prm, _lib.ptr(p), p.shape[0], _lib.ptr(clean), B,
+                                                            self.L, _lib.ptr(alpha_rows), B, _lib.ptr(grad), _lib.ptr(loss_rows),
+                                                            _lib.ptr(self.stats[ST_MASK_LOSS:ST_MASK_LOSS + 1]), None,
+                                                            _lib.stream_ptr()))
+                return
             _lib.check(_lib.lib().paa_masking_loss(self.proj.h, self._mask_prm, _lib.ptr(p), p.shape[0] if p.dim() == 2 else 1,
                                                    _lib.ptr(clean), B, self.L, _lib.ptr(self.alpha_dev), _lib.ptr(grad),
                                                    _lib.ptr(loss_rows), _lib.ptr(self.stats[ST_MASK_LOSS:ST_MASK_LOSS + 1]), None,
