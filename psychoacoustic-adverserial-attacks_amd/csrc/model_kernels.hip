@@ -1019,9 +1019,9 @@ __global__ __launch_bounds__(512) void k_ctc(const float* __restrict__ logits, c
 }
 
 // ---- wave-synchronous CTC (label capacity 2 S_max + 1 <= 1024) ----------------------------------------------------------
-// One wave runs alpha forwards, a second wave runs beta backwards, each lane owning NS consecutive states of the extended
-// label sequence in registers: no workgroup barrier in the time loop, the two boundary states of the neighbouring lane
-// arrive by DPP wave shifts, the emission log-probabilities of the next frame are fetched one step ahead.  The recursion
+// One workgroup per clip runs alpha forwards and beta backwards at the same time in separate waves; lane i owns the NS
+// consecutive states i NS .. i NS + NS - 1 of the extended label sequence (slot j of lane i = state i NS + j), in registers;
+// the emission log-probabilities of the next frame are fetched one step ahead.  The recursion
 // is in the LOG domain and therefore total: any target the frame count admits gets a finite loss whatever the dynamic
 // range of the posteriors (a probability-domain recursion rescaled by the row maximum — the previous version of this
 // kernel — flushes states more than 2^-1074 below the best state of a frame, which on peaked logits is where the whole
@@ -1092,7 +1092,62 @@ __device__ __forceinline__ double ctc_lse3(double x0, double x1, double x2) {
     return m + (double)(__builtin_amdgcn_logf(s) * 0.69314718055994531f);
 }
 
-// the two recursions of one clip: wave 0 alpha, wave 1 beta; LDS_TAB: the clip's lp table is first copied to LDS
+// The recursion kernels.  A step of a state is ctc_lse3(own, neighbour 1, neighbour 2 + skip mask) + emission, in that order, and
+// a row of the work buffer is [slot][lane] (k_ctc_grad reads it): nll and dlogits have the same bits whichever kernel and NS a
+// label capacity selects (tests/test_gpu_rows.py: the capacity tests and the fixture of the bits before the kernels were merged).
+//   k_ctc_rec_mw<NS, K>, NS >= 2: 2 NS / K waves per clip — waves [0, NS / K) alpha, the rest beta — wave w of a direction owning
+// the K consecutive slots w K .. w K + K - 1 of every lane.  A step is K lse3 per wave; neighbours inside the wave's own slots come
+// from its registers (the previous step's values), the two beyond them from a double-buffered LDS exchange array behind ONE
+// workgroup barrier (step i reads buffer i & 1 and writes the other: every wave has finished reading a buffer before any wave
+// passes the next barrier and overwrites it; the last row is in buffer T & 1).  K = 1, one wave per state slot, is the shortest
+// step and is used wherever a workgroup holds the 2 NS waves (NS <= 8); 2 S + 1 up to 1024 = 16 states per lane would need 32, so
+// NS = 16 runs K = 2: sixteen waves of two states.
+//   Measured history (B = 32).  Round 2 ran every NS as k_ctc_rec does, NS states per lane one after the other in one wave per
+// direction: six lse3 of ~25 dependent-latency instructions each per step at S = 150, ~0.5 us per step, 240 us for T = 499 with the
+// rest of the chip idle; one wave per slot: 178 us.  At S = 450, T = 1499 (30 s clips) sixteen states per lane one after the other
+// were ~2 ms of a 73 ms step; with sixteen waves of two the step went 72.9 -> 68.8 ms (together with ring-GEMM changes).
+//   k_ctc_rec<1>, NS = 1: one wave per direction, one state per lane, neighbours by DPP wave shifts and NO barrier in the time
+// loop.  k_ctc_rec_mw<1, 1> computes the same bits with two waves, but pays the LDS round trip and the barrier on a step that is a
+// single lse3: 135.8 us per call (135.1 / 136.6) against 85.5 us (85.9 / 85.1) of k_ctc_rec<1, true> at T = 499, 30-token labels,
+// alternating runs on one MI355X (profiles/ctc_rec_ab.txt) — so this kernel stays for NS = 1, and only <1, .> is launched.
+
+// Extended labels of one clip -> lab [2 S_max + 1] in LDS: blank, l_0, blank, l_1, ..., blank; returns S, the number of labels.
+// Valid labels are the non-negative entries of the row, in order (HF masked_select).  The row is first copied to LDS
+// (lab + 2 S_max + 1, [S_max]) by all nt threads — one global round trip instead of S_max dependent ones — then compacted by thread 0.
+// Two workgroup barriers: what the workgroup wrote to LDS before the call is visible after it as well.
+__device__ __forceinline__ int ctc_ext_labels(const int32_t* __restrict__ row, int S_max, int blank, int* lab, int tid, int nt) {
+    __shared__ int s_len;
+    int* raw = lab + 2 * S_max + 1;
+    for (int s = tid; s < S_max; s += nt) raw[s] = row[s];
+    __syncthreads();
+    if (tid == 0) {
+        int k = 0;
+        lab[0] = blank;
+        for (int s = 0; s < S_max; ++s) {
+            const int v = raw[s];
+            if (v >= 0) { lab[2 * k + 1] = v; lab[2 * k + 2] = blank; ++k; }
+        }
+        s_len = k;
+    }
+    __syncthreads();
+    return s_len;
+}
+// the n doubles of a clip's lp table -> LDS, by all nt threads
+__device__ __forceinline__ void ctc_table_to_lds(const double* __restrict__ lp, double* dst, int n, int tid, int nt) {
+    const double2* src2 = reinterpret_cast<const double2*>(lp);
+    double2* dst2 = reinterpret_cast<double2*>(dst);
+    for (int i = tid; i < n / 2; i += nt) dst2[i] = src2[i];
+    if ((n & 1) && tid == 0) dst[n - 1] = lp[n - 1];
+}
+// nll = -lse(alpha_{T-1}(S'-1), alpha_{T-1}(S'-2)): float64 to the work buffer (k_ctc_grad reads it), +inf out where no alignment exists
+__device__ __forceinline__ void ctc_finish(double a_last, double a_prev, const CtcWork& w, float* nll_out) {
+    const double nll = -ctc_lse3(a_last, a_prev, CTC_NEG);
+    *w.nll = nll;
+    *nll_out = nll < 1e29 ? (float)nll : INFINITY;
+}
+
+// Wave 0 alpha, wave 1 beta, neighbours by DPP; LDS_TAB: the clip's lp table is first copied to LDS.  Only <1, .> is launched: it
+// stays because k_ctc_rec_mw<1, 1> measured 135.8 us against its 85.5 us (header above); the generic-NS form is round 2's kernel.
 template <int NS, bool LDS_TAB>
 __global__ __launch_bounds__(128) void k_ctc_rec(const int32_t* __restrict__ labels, int Tall, int V, int S_max, int blank,
                                                  float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc,
@@ -1100,15 +1155,9 @@ __global__ __launch_bounds__(128) void k_ctc_rec(const int32_t* __restrict__ lab
     extern __shared__ __attribute__((aligned(16))) double smd[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int T = ctc_frames(frames, b, Tall);
-    const int SPmax = 2 * S_max + 1;
     constexpr int ROW = 64 * NS;
     const CtcWork w = ctc_work(work + (size_t)b * wpc, Tall, V, ROW);
-    int* lab = reinterpret_cast<int*>(smd + (LDS_TAB ? (size_t)T * V : 0));      // [SPmax] extended labels
-    __shared__ int s_len;
-    // extended labels: valid labels are the non-negative entries, in order (HF masked_select).  The label row is first
-    // copied to LDS by all threads (one global round trip instead of S_max dependent ones), then compacted by thread 0.
-    int* raw = lab + SPmax;                                       // [S_max]
-    for (int s = tid; s < S_max; s += 128) raw[s] = labels[(size_t)b * S_max + s];
+    int* lab = reinterpret_cast<int*>(smd + (LDS_TAB ? (size_t)T * V : 0));      // [2 S_max + 1] extended labels, [S_max] label row
     if (LDS_TAB) {          // lp table -> LDS, 8 independent 16-byte loads in flight per thread
         const int n2 = T * V / 2;
         const double2* src = reinterpret_cast<const double2*>(w.lp);
@@ -1124,19 +1173,8 @@ __global__ __launch_bounds__(128) void k_ctc_rec(const int32_t* __restrict__ lab
         for (int i = nfull + tid; i < n2; i += 128) dst[i] = src[i];
         if (((T * V) & 1) && tid == 0) smd[T * V - 1] = w.lp[T * V - 1];
     }
-    __syncthreads();
-    if (tid == 0) {
-        int k = 0;
-        lab[0] = blank;
-        for (int s = 0; s < S_max; ++s) {
-            const int v = raw[s];
-            if (v >= 0) { lab[2 * k + 1] = v; lab[2 * k + 2] = blank; ++k; }
-        }
-        s_len = k;
-    }
+    const int SP = 2 * ctc_ext_labels(labels + (size_t)b * S_max, S_max, blank, lab, tid, 128) + 1;
     const double* tab = LDS_TAB ? smd : w.lp;
-    __syncthreads();
-    const int S = s_len, SP = 2 * S + 1;
     int l[NS];
     unsigned skf = 0, skb = 0;
 #pragma unroll
@@ -1211,9 +1249,7 @@ __global__ __launch_bounds__(128) void k_ctc_rec(const int32_t* __restrict__ lab
                 const int s = lane * NS + j;
                 if (s == SP - 1) {
                     const double l2 = SP >= 2 ? (j >= 1 ? a[j >= 1 ? j - 1 : 0] : prev) : CTC_NEG;
-                    const double nll = -ctc_lse3(a[j], l2, CTC_NEG);
-                    *w.nll = nll;
-                    nll_out[b] = nll < 1e29 ? (float)nll : INFINITY;
+                    ctc_finish(a[j], l2, w, nll_out + b);
                 }
             }
         }
@@ -1221,113 +1257,13 @@ __global__ __launch_bounds__(128) void k_ctc_rec(const int32_t* __restrict__ lab
     if (wave == 0) recursion(std::true_type{}); else recursion(std::false_type{});
 }
 
-// The same two recursions with ONE WAVE PER STATE SLOT (round 3): 2 NS waves per clip — waves [0, NS) alpha, [NS, 2 NS) beta — wave j
-// of a direction owning state lane * NS + j of every lane.  k_ctc_rec above evaluates its NS states per lane one after the other
-// (six lse3 of ~25 dependent-latency instructions each per time step at S = 150: ~0.5 us per step, 240 us for T = 499, with the rest
-// of the chip idle between the forward and the backward pass); here a step is ONE lse3 per wave plus the exchange of the two
-// neighbour states through a double-buffered LDS array and one workgroup barrier (step t reads buffer t & 1 and writes the other:
-// every wave has finished reading a buffer before any wave passes the next barrier and overwrites it).  Same arithmetic per
-// state, same row layout in the work buffer (k_ctc_grad reads it unchanged): results are bit-identical to k_ctc_rec.
-template <int NS, bool LDS_TAB>
-__global__ __launch_bounds__(128 * NS) void k_ctc_rec_mw(const int32_t* __restrict__ labels, int Tall, int V, int S_max, int blank,
-                                                          float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc,
-        const int32_t* __restrict__ frames) {
-    static_assert(NS >= 2 && NS <= 8, "one wave per state slot: 4 .. 16 waves");
-    extern __shared__ __attribute__((aligned(16))) double smd[];
-    constexpr int NT = 128 * NS, ROW = 64 * NS;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int T = ctc_frames(frames, b, Tall);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool fwd = wave < NS;
-    const int j = fwd ? wave : wave - NS;                       // state slot of this wave
-    const int SPmax = 2 * S_max + 1;
-    const CtcWork w = ctc_work(work + (size_t)b * wpc, Tall, V, ROW);
-    double* xch = smd + (LDS_TAB ? (size_t)T * V : 0);          // [2 directions][2 buffers][NS][64]
-    int* lab = reinterpret_cast<int*>(xch + 4 * ROW);           // [SPmax] extended labels
-    __shared__ int s_len;
-    int* raw = lab + SPmax;                                     // [S_max]
-    for (int s = tid; s < S_max; s += NT) raw[s] = labels[(size_t)b * S_max + s];
-    if (LDS_TAB) {          // lp table -> LDS
-        const int n2 = T * V / 2;
-        const double2* src = reinterpret_cast<const double2*>(w.lp);
-        double2* dst = reinterpret_cast<double2*>(smd);
-        for (int i = tid; i < n2; i += NT) dst[i] = src[i];
-        if (((T * V) & 1) && tid == 0) smd[T * V - 1] = w.lp[T * V - 1];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int k = 0;
-        lab[0] = blank;
-        for (int s = 0; s < S_max; ++s) {
-            const int v = raw[s];
-            if (v >= 0) { lab[2 * k + 1] = v; lab[2 * k + 2] = blank; ++k; }
-        }
-        s_len = k;
-    }
-    const double* tab = LDS_TAB ? smd : w.lp;
-    __syncthreads();
-    const int S = s_len, SP = 2 * S + 1;
-    const int s = lane * NS + j;                                // this lane's state
-    const int l = s < SP ? lab[s] : blank;
-    bool skip;                                                  // the skip transition (s -+ 2) is open
-    if (fwd) skip = s < SP && s >= 2 && l != blank && l != lab[s - 2];
-    else skip = s + 2 < SP && lab[s + 2] != blank && lab[s + 2] != l;
-    if (fwd) w.lab[j * 64 + lane] = s < SP ? l : -1;
-    const double skn = skip ? 0.0 : CTC_NEG, dead = s < SP ? 0.0 : CTC_NEG;
-    double* rows = fwd ? w.arow : w.brow;
-    double* xd = xch + (fwd ? 0 : 2 * ROW);                     // this direction's two buffers
-    // neighbours: fwd s - 1, s - 2; bwd s + 1, s + 2 — (slot, lane shift) of each, CTC_NEG past the ends of the wave
-    const int j1 = fwd ? (j >= 1 ? j - 1 : NS - 1) : (j + 1 < NS ? j + 1 : 0);
-    const int j2 = fwd ? (j >= 2 ? j - 2 : NS + j - 2) : (j + 2 < NS ? j + 2 : j + 2 - NS);
-    const int d1 = fwd ? (j >= 1 ? 0 : -1) : (j + 1 < NS ? 0 : 1);
-    const int d2 = fwd ? (j >= 2 ? 0 : -1) : (j + 2 < NS ? 0 : 1);
-    const int l1 = lane + d1, l2 = lane + d2;
-    const bool ok1 = l1 >= 0 && l1 < 64, ok2 = l2 >= 0 && l2 < 64;
-    const int o1 = j1 * 64 + (ok1 ? l1 : 0), o2 = j2 * 64 + (ok2 ? l2 : 0), o0 = j * 64 + lane;
-
-    const int t0 = fwd ? 0 : T - 1;
-    double em = tab[(size_t)t0 * V + l] + dead;
-    const bool on = fwd ? (s == 0 || s == 1) : (s == SP - 1 || s == SP - 2);
-    double a = (on && s < SP) ? em : CTC_NEG;
-    rows[(size_t)t0 * ROW + o0] = a;
-    xd[ROW + o0] = a;                                           // step 1 reads buffer 1
-    if (T > 1) em = tab[(size_t)(fwd ? 1 : T - 2) * V + l] + dead;
-    for (int i = 1; i < T; ++i) {
-        const int t = fwd ? i : T - 1 - i;
-        double emn = 0.0;
-        if (i + 1 < T) emn = tab[(size_t)(fwd ? i + 1 : T - 2 - i) * V + l] + dead;       // next step's emission flies under this step
-        __syncthreads();                                        // every wave's value of the previous step is in buffer i & 1
-        const double* in = xd + (i & 1) * ROW;
-        const double x1 = ok1 ? in[o1] : CTC_NEG;
-        const double x2 = ok2 ? in[o2] : CTC_NEG;
-        a = ctc_lse3(a, x1, x2 + skn) + em;
-        xd[((i + 1) & 1) * ROW + o0] = a;
-        rows[(size_t)t * ROW + o0] = a;
-        em = emn;
-    }
-    __syncthreads();                                            // the last alpha row is in buffer T & 1
-    if (tid == 0) {   // log P = lse(alpha_{T-1}(S'-1), alpha_{T-1}(S'-2))
-        const double* fin = xch + (T & 1) * ROW;
-        const int sa = SP - 1, sb = SP - 2;
-        const double va = fin[(sa % NS) * 64 + sa / NS];
-        const double vb = SP >= 2 ? fin[(sb % NS) * 64 + sb / NS] : CTC_NEG;
-        const double nll = -ctc_lse3(va, vb, CTC_NEG);
-        *w.nll = nll;
-        nll_out[b] = nll < 1e29 ? (float)nll : INFINITY;
-    }
-}
-
-// The same with K states per lane and wave (long label sequences: 2 S + 1 up to 1024 = 16 states per lane needs 32 one-state waves,
-// more than a workgroup holds): 2 NS / K waves per clip, wave w of a direction owning the K consecutive slots w K .. w K + K - 1 of
-// every lane.  A step is K lse3 per wave; neighbours inside the wave's own slots come from its registers (the previous step's
-// values), the two beyond its range from the exchange buffer.  Same arithmetic per state and same row layout as k_ctc_rec /
-// k_ctc_rec_mw: bit-identical results.  At S = 450, T = 1499 (30 s clips) the one-wave-per-direction kernel evaluated 16 states per
-// lane one after the other: ~2 ms of a 73 ms step.
 template <int NS, int K, bool LDS_TAB>
-__global__ __launch_bounds__(128 * NS / K) void k_ctc_rec_mwk(const int32_t* __restrict__ labels, int Tall, int V, int S_max, int blank,
-                                                               float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc,
+__global__ __launch_bounds__(128 * NS / K) void k_ctc_rec_mw(const int32_t* __restrict__ labels, int Tall, int V, int S_max, int blank,
+                                                              float* __restrict__ nll_out, float* __restrict__ work, int64_t wpc,
         const int32_t* __restrict__ frames) {
-    static_assert(K >= 2 && NS % K == 0 && NS / K >= 2 && 2 * NS / K <= 16, "K states per lane and wave, 4 .. 16 waves");
+    // whole slot groups, and a workgroup's 16 waves; every neighbour beyond a wave's own slots goes through the exchange buffer,
+    // whichever wave and lane owns it, so one wave per direction (NS = K) and states two lanes away (NS = 1) are covered as well
+    static_assert(K >= 1 && NS % K == 0 && 2 * NS / K <= 16, "K slots per wave, at most 16 waves");
     extern __shared__ __attribute__((aligned(16))) double smd[];
     constexpr int NWD = NS / K, NT = 128 * NWD, ROW = 64 * NS;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -1335,33 +1271,12 @@ __global__ __launch_bounds__(128 * NS / K) void k_ctc_rec_mwk(const int32_t* __r
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool fwd = wave < NWD;
     const int jw = fwd ? wave : wave - NWD;                     // slot group of this wave
-    const int SPmax = 2 * S_max + 1;
     const CtcWork w = ctc_work(work + (size_t)b * wpc, Tall, V, ROW);
     double* xch = smd + (LDS_TAB ? (size_t)T * V : 0);          // [2 directions][2 buffers][NS][64]
-    int* lab = reinterpret_cast<int*>(xch + 4 * ROW);           // [SPmax] extended labels
-    __shared__ int s_len;
-    int* raw = lab + SPmax;                                     // [S_max]
-    for (int s = tid; s < S_max; s += NT) raw[s] = labels[(size_t)b * S_max + s];
-    if (LDS_TAB) {
-        const int n2 = T * V / 2;
-        const double2* src = reinterpret_cast<const double2*>(w.lp);
-        double2* dst = reinterpret_cast<double2*>(smd);
-        for (int i = tid; i < n2; i += NT) dst[i] = src[i];
-        if (((T * V) & 1) && tid == 0) smd[T * V - 1] = w.lp[T * V - 1];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int k = 0;
-        lab[0] = blank;
-        for (int s = 0; s < S_max; ++s) {
-            const int v = raw[s];
-            if (v >= 0) { lab[2 * k + 1] = v; lab[2 * k + 2] = blank; ++k; }
-        }
-        s_len = k;
-    }
+    int* lab = reinterpret_cast<int*>(xch + 4 * ROW);           // [2 S_max + 1] extended labels, [S_max] label row
+    if (LDS_TAB) ctc_table_to_lds(w.lp, smd, T * V, tid, NT);
+    const int SP = 2 * ctc_ext_labels(labels + (size_t)b * S_max, S_max, blank, lab, tid, NT) + 1;
     const double* tab = LDS_TAB ? smd : w.lp;
-    __syncthreads();
-    const int S = s_len, SP = 2 * S + 1;
     int l[K], o0[K];
     double skn[K], dead[K];
     bool on[K];
@@ -1387,8 +1302,8 @@ __global__ __launch_bounds__(128 * NS / K) void k_ctc_rec_mwk(const int32_t* __r
 #pragma unroll
     for (int m = 1; m <= 2; ++m) {
         int slot = fwd ? jw * K - m : (jw + 1) * K + m - 1, ln = lane;
-        if (slot < 0) { slot += NS; ln -= 1; }
-        if (slot >= NS) { slot -= NS; ln += 1; }
+        while (slot < 0) { slot += NS; ln -= 1; }                // twice at NS = 1
+        while (slot >= NS) { slot -= NS; ln += 1; }
         okn[m] = ln >= 0 && ln < 64;
         on_[m] = slot * 64 + (okn[m] ? ln : 0);
     }
@@ -1446,9 +1361,7 @@ __global__ __launch_bounds__(128 * NS / K) void k_ctc_rec_mwk(const int32_t* __r
         const int sa = SP - 1, sb = SP - 2;
         const double va = fin[(sa % NS) * 64 + sa / NS];
         const double vb = SP >= 2 ? fin[(sb % NS) * 64 + sb / NS] : CTC_NEG;
-        const double nll = -ctc_lse3(va, vb, CTC_NEG);
-        *w.nll = nll;
-        nll_out[b] = nll < 1e29 ? (float)nll : INFINITY;
+        ctc_finish(va, vb, w, nll_out + b);
     }
 }
 
@@ -1495,59 +1408,33 @@ __global__ __launch_bounds__(256) void k_ctc_grad(int Tall, int Tpad, int V, flo
     }
 }
 
+// slots per wave of k_ctc_rec_mw: one, and two where one would need more waves than a workgroup holds
+constexpr int ctc_rec_k(int ns) { return ns == 16 ? 2 : 1; }
+template <int NS, bool LDS_TAB>
+constexpr auto ctc_rec_kernel() {
+    if constexpr (NS == 1) return &k_ctc_rec<1, LDS_TAB>;
+    else return &k_ctc_rec_mw<NS, ctc_rec_k(NS), LDS_TAB>;
+}
+
 template <int NS>
 static paa_status launch_ctc_ws(const float* logits, const int32_t* labels, int B, int T, int Tpad, int V, int S_max, int blank,
                                 float gscale, float* nll, float* dlogits, Bf dlb, float* work, int64_t wpc, const int32_t* frames, hipStream_t st) {
-    const int SPmax = 2 * S_max + 1;
+    constexpr int K = ctc_rec_k(NS), NT = 128 * NS / K;
     hipLaunchKernelGGL(k_ctc_logsoftmax, dim3(cdiv((int64_t)B * T, 8)), dim3(256), 0, st, logits, B, T, Tpad, V, work, wpc, frames);
     PAA_LAUNCH_CHECK();
+    // dynamic LDS: [lp table] | exchange buffers | extended labels + label row; the table goes to LDS where all of it fits 150 KiB
     const size_t tab = sizeof(double) * (size_t)T * V;
-    const size_t small = sizeof(int) * ((size_t)SPmax + S_max) + 64;
-    if constexpr (NS >= 2 && NS <= 8) {       // one wave per state slot (k_ctc_rec_mw)
-        const size_t xch = sizeof(double) * 4 * 64 * NS;
-        const bool ltab = tab + xch + small <= 150 * 1024;
-        const size_t ldsm = xch + small + (ltab ? tab : 0);
-        static bool attr_mw = false;
-        if (!attr_mw) {
-            PAA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctc_rec_mw<NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-            attr_mw = true;
-        }
-        if (ltab) hipLaunchKernelGGL((k_ctc_rec_mw<NS, true>), dim3(B), dim3(128 * NS), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
-        else hipLaunchKernelGGL((k_ctc_rec_mw<NS, false>), dim3(B), dim3(128 * NS), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
-        PAA_LAUNCH_CHECK();
-        if (dlogits) {
-            hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc, frames);
-            PAA_LAUNCH_CHECK();
-        }
-        return PAA_OK;
+    const size_t xch = NS >= 2 ? sizeof(double) * 4 * 64 * NS : 0;          // k_ctc_rec (NS = 1) exchanges by DPP
+    const size_t small = sizeof(int) * ((size_t)(2 * S_max + 1) + S_max) + 64;
+    const bool ltab = tab + xch + small <= 150 * 1024;
+    const size_t lds = xch + small + (ltab ? tab : 0);
+    const auto rec_lds = ctc_rec_kernel<NS, true>(), rec_glb = ctc_rec_kernel<NS, false>();
+    static bool attr = false;
+    if (!attr) {
+        PAA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rec_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+        attr = true;
     }
-    if constexpr (NS == 16) {                 // two states per lane and wave, sixteen waves (k_ctc_rec_mwk)
-        const size_t xch = sizeof(double) * 4 * 64 * NS;
-        const bool ltab = tab + xch + small <= 150 * 1024;
-        const size_t ldsm = xch + small + (ltab ? tab : 0);
-        static bool attr_mwk = false;
-        if (!attr_mwk) {
-            PAA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctc_rec_mwk<NS, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-            attr_mwk = true;
-        }
-        if (ltab) hipLaunchKernelGGL((k_ctc_rec_mwk<NS, 2, true>), dim3(B), dim3(128 * NS / 2), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
-        else hipLaunchKernelGGL((k_ctc_rec_mwk<NS, 2, false>), dim3(B), dim3(128 * NS / 2), ldsm, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
-        PAA_LAUNCH_CHECK();
-        if (dlogits) {
-            hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc, frames);
-            PAA_LAUNCH_CHECK();
-        }
-        return PAA_OK;
-    }
-    const bool lds_tab = tab + small <= 150 * 1024;
-    const size_t lds = small + (lds_tab ? tab : 0);
-    if (lds_tab) {
-        static bool attr = false;
-        if (!attr) { PAA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctc_rec<NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)); attr = true; }
-        hipLaunchKernelGGL((k_ctc_rec<NS, true>), dim3(B), dim3(128), lds, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
-    } else {
-        hipLaunchKernelGGL((k_ctc_rec<NS, false>), dim3(B), dim3(128), lds, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
-    }
+    hipLaunchKernelGGL(ltab ? rec_lds : rec_glb, dim3(B), dim3(NT), lds, st, labels, T, V, S_max, blank, nll, work, wpc, frames);
     PAA_LAUNCH_CHECK();
     if (dlogits) {
         hipLaunchKernelGGL((k_ctc_grad<NS>), dim3(cdiv(Tpad, 4), B), dim3(256), sizeof(unsigned) * 4 * V, st, T, Tpad, V, gscale, dlogits, dlb, work, wpc, frames);
@@ -1637,25 +1524,11 @@ __global__ __launch_bounds__(64) void k_align_rec(const float* __restrict__ logi
     const int SPmax = 2 * S_max + 1;
     const int nblk = max(T < AL_BLK ? T : AL_BLK, 2 * NS);         // as the launcher sizes it: fin needs 2 NS rows
     unsigned* tab = sma;                                           // [nblk][64] back-pointer words of the staged block
-    int* lab = reinterpret_cast<int*>(sma + (size_t)64 * nblk);    // [SPmax] extended labels
-    int* raw = lab + SPmax;                                        // [S_max]
+    int* lab = reinterpret_cast<int*>(sma + (size_t)64 * nblk);    // [2 S_max + 1] extended labels, [S_max] label row
     double* fin = reinterpret_cast<double*>(tab);                  // [64 NS] final values (before the table is staged)
-    __shared__ int s_len;
     const AlignWork w = align_work(work + (size_t)b * wpc, Tall);
     const float* lg = logits + (size_t)b * Tpad * V;
-    for (int s = lane; s < S_max; s += 64) raw[s] = labels[(size_t)b * S_max + s];
-    __syncthreads();
-    if (lane == 0) {           // valid labels are the non-negative entries, in order (as k_ctc_rec compacts them)
-        int k = 0;
-        lab[0] = blank;
-        for (int s = 0; s < S_max; ++s) {
-            const int v = raw[s];
-            if (v >= 0) { lab[2 * k + 1] = v; lab[2 * k + 2] = blank; ++k; }
-        }
-        s_len = k;
-    }
-    __syncthreads();
-    const int S = s_len, SP = 2 * S + 1;
+    const int S = ctc_ext_labels(labels + (size_t)b * S_max, S_max, blank, lab, lane, 64), SP = 2 * S + 1;
     int l[NS];
     unsigned skf = 0;
 #pragma unroll

@@ -9,6 +9,10 @@ in different orders; a wrong divisor or a missing eps is two orders above that o
 
 Every output lives between two guard blocks of a sentinel bit pattern that must survive; planes written next to an f32 result must be
 the planes of THAT result bit for bit; every launch is repeated and must reproduce its bits."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -369,12 +373,12 @@ def test_softmax_mats_wide_range():
 
 # ===================================================================================== CTC ===
 # (T, V, S_max): recursion kernel and side of the LDS-table switch (8 T V + exchange + labels <= 150 KiB)
-CTC_CASES = [(37, 5, 20),        # k_ctc_rec<1>, table in LDS, T V odd (the copy tail), V < 32
-             (80, 256, 31),      # k_ctc_rec<1>, table in global memory
-             (70, 256, 100),     # k_ctc_rec_mw<4>, table in LDS (152820 bytes of 153600)
-             (80, 256, 60),      # k_ctc_rec_mw<2>, table in global memory
-             (71, 65, 300),      # k_ctc_rec_mwk<16, 2>, table in LDS, T V odd, V = 64 + 1
-             (80, 256, 300),     # k_ctc_rec_mwk<16, 2>, table in global memory
+CTC_CASES = [(37, 5, 20),        # k_ctc_rec<1> (NS = 1), table in LDS, T V odd (the copy tail), V < 32
+             (80, 256, 31),      # k_ctc_rec<1> (NS = 1), table in global memory
+             (70, 256, 100),     # k_ctc_rec_mw<4, 1>, table in LDS (152820 bytes of 153600)
+             (80, 256, 60),      # k_ctc_rec_mw<2, 1>, table in global memory
+             (71, 65, 300),      # k_ctc_rec_mw<16, 2>, table in LDS, T V odd, V = 64 + 1
+             (80, 256, 300),     # k_ctc_rec_mw<16, 2>, table in global memory
              (41, 29, 520)]      # k_ctc (2 S_max + 1 > 1024), T V odd
 FEASIBLE = np.array([True, True, True, False, True])
 
@@ -459,6 +463,169 @@ def test_ctc_padded(T, V, S_max):
         print(f"    grad_scale 0.5: grad {e3:.2e}")
         assert same_bits(nll_h, nll) and e3 < 1e-5 and np.isnan(dl_h[3, :T]).all()
         assert same_bits(hi_h[fin], R.planes_of(dl_h[fin], "hi")[0]) and not hi_h[:, T:].any() and not dl_h[:, T:].view(np.int32).any()
+
+
+# ---- the wave-synchronous recursion as a family: one arithmetic per state whatever the number of states per lane (NS) --------------
+# Cases by name -> (logits (B, Tpad, V), labels (B, S_max), T, frames or None).  Without frames a case runs through paa_ctc_padded
+# with hi + lo planes, with frames through paa_ctc_len.  tools/ctc_parent_bits.py walks the same dictionary.
+CAP_SMAX = [25, 60, 100, 150, 250, 400]            # NS = 1, 2, 4, 6, 8, 16
+CAP_T, CAP_V, CAP_FRAMES = 64, 16, [64, 9, 50]
+FULL_SMAX = [31, 63, 127, 191, 255, 511]           # 2 S_max + 1 = 64 NS - 1: the last lane's last slots hold live states
+FULL_V = 6
+WS_BITS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ctc_rec_parent.json")
+
+
+def cap_inputs(S_max):
+    """Three clips whose label rows do not depend on the capacity: 25 random labels with one repeat; a single label; 25 labels (they
+    fit the 50 frames CAP_FRAMES gives that clip).  Padded with -100 to S_max."""
+    gen = torch.Generator().manual_seed(60)
+    logits = torch.randn(3, CAP_T, CAP_V, generator=gen) * 2
+    lab = torch.full((3, S_max), -100, dtype=torch.int64)
+    lab[0, :25] = torch.randint(1, CAP_V - 1, (25,), generator=gen)
+    lab[0, 6] = lab[0, 5]
+    lab[1, 0] = 3
+    lab[2, :25] = torch.randint(1, CAP_V - 1, (25,), generator=gen)
+    return logits, lab
+
+
+def full_inputs(S_max):
+    """T = 2 S_max + 8 frames, three clips: exactly S_max labels with adjacent repeats at positions 1-2 and at the last two; S_max - 1
+    labels; one label.  S_max labels with r repeats need S_max + r <= 2 S_max - 1 frames: every clip is feasible, also in the
+    T - 3 frames full_frames gives clip 1."""
+    gen = torch.Generator().manual_seed(70 + S_max)
+    T = 2 * S_max + 8
+    logits = torch.randn(3, T, FULL_V, generator=gen) * 2
+    lab = torch.full((3, S_max), -100, dtype=torch.int64)
+    lab[0] = torch.randint(1, FULL_V - 1, (S_max,), generator=gen)
+    lab[0, 2] = lab[0, 1]
+    lab[0, S_max - 1] = lab[0, S_max - 2]
+    lab[1, :S_max - 1] = torch.randint(1, FULL_V - 1, (S_max - 1,), generator=gen)
+    lab[2, 0] = 2
+    return logits, lab, T
+
+
+def full_frames(T):
+    return [T, T - 3, 5]
+
+
+def ws_cases():
+    cases = {}
+    for S_max in CAP_SMAX:
+        logits, lab = cap_inputs(S_max)
+        cases[f"cap{S_max}"] = (logits, lab, CAP_T, None)
+        cases[f"cap{S_max}_len"] = (logits, lab, CAP_T, CAP_FRAMES)
+    for S_max in FULL_SMAX:
+        logits, lab, T = full_inputs(S_max)
+        cases[f"full{S_max}"] = (logits, lab, T, None)
+        cases[f"full{S_max}_len"] = (logits, lab, T, full_frames(T))
+    for T, V, S_max in CTC_CASES[:6]:
+        logits, lab, _ = ctc_inputs(T, V, S_max, 40 + T + V)
+        cases[f"rows{T}x{V}x{S_max}"] = (logits, lab, T, None)
+    return cases
+
+
+_ws_cases, _ws_runs = {}, {}
+
+
+def ws_case(name):
+    if not _ws_cases:
+        _ws_cases.update(ws_cases())
+    return _ws_cases[name]
+
+
+def ws_run(name, blank):
+    """(nll, dlogits, hi, lo) of a case on the GPU, computed once per session; hi and lo are None for the paa_ctc_len cases"""
+    if (name, blank) in _ws_runs:
+        return _ws_runs[name, blank]
+    logits, lab, T, frames = ws_case(name)
+    B, Tpad, V = logits.shape
+    S_max = lab.shape[1]
+    lg, labd = logits.cuda(), lab.to(torch.int32).cuda()
+    if frames is None:
+        out = Ctc(lg, labd, T, Tpad, V, S_max, blank, 1.0, float("nan")).outs()
+    else:
+        L = _lib.lib()
+        nll, dl = Guarded((B,)), Guarded((B, T, V))
+        work = torch.full((L.paa_ctc_work_floats(B, T, V, S_max),), float("nan"), device="cuda")
+        fr = torch.tensor(frames, dtype=torch.int32, device="cuda")
+        _lib.check(L.paa_ctc_len(_lib.ptr(lg), _lib.ptr(labd), _lib.ptr(fr), B, T, V, S_max, blank, 1.0, nll.ptr, dl.ptr,
+                                 _lib.ptr(work), _lib.stream_ptr()))
+        sync()
+        nll.check()
+        dl.check()
+        out = (nll.numpy(), dl.numpy(), None, None)
+    _ws_runs[name, blank] = out
+    return out
+
+
+def ws_bits(name, blank):
+    """what the fixture keeps of a run: nll as uint32 bit patterns, SHA-256 of the dlogits bytes of the first T frames of every clip"""
+    nll, dl = ws_run(name, blank)[:2]
+    T = ws_case(name)[2]
+    return {"nll": [int(v) for v in nll.view(np.uint32)], "dlogits_sha256": hashlib.sha256(np.ascontiguousarray(dl[:, :T]).tobytes()).hexdigest()}
+
+
+def ctc_ref_frames(logits, lab, frames, blank):
+    """float64 CTC of every clip over its own first frames[b] frames: nll (B), gradient (B, T, V) with zero rows beyond"""
+    B, T, V = logits.shape
+    nll, g = np.zeros(B), np.zeros((B, T, V))
+    for b, tb in enumerate(frames):
+        n1, g1 = R.ctc_padded(logits[b:b + 1, :tb], lab[b:b + 1], tb, blank)
+        nll[b], g[b, :tb] = n1[0], g1[0]
+    return nll, g
+
+
+def test_ctc_capacity_does_not_change_the_bits():
+    """The same label rows padded to six capacities run the recursion at NS = 1, 2, 4, 6, 8, 16 states per lane: nll, dlogits and
+    the bf16 planes are bit-equal across all six, with and without per-clip frame counts."""
+    for blank in (0, CAP_V - 1):
+        for suffix in ("", "_len"):
+            first = ws_run(f"cap{CAP_SMAX[0]}{suffix}", blank)
+            assert np.isfinite(first[0]).all() and np.isfinite(first[1]).all()
+            if suffix:
+                for b, tb in enumerate(CAP_FRAMES):
+                    assert not first[1][b, tb:].view(np.int32).any(), "rows beyond the clip's frames are not +0"
+            for S_max in CAP_SMAX[1:]:
+                out = ws_run(f"cap{S_max}{suffix}", blank)
+                for what, a, b in zip(("nll", "dlogits", "hi plane", "lo plane"), first, out):
+                    assert same_bits(a, b), f"{what} at S_max={S_max} differs from S_max={CAP_SMAX[0]} (blank {blank}, frames {suffix != ''})"
+
+
+@pytest.mark.parametrize("S_max", FULL_SMAX)
+def test_ctc_full_label_rows(S_max):
+    """Label rows that fill the capacity (2 S_max + 1 = 64 NS - 1 states: every lane and every slot live) against float64"""
+    logits, lab, T = full_inputs(S_max)
+    for blank in (0, FULL_V - 1):
+        for frames in (None, full_frames(T)):
+            nr, gr = R.ctc_padded(logits, lab, T, blank) if frames is None else ctc_ref_frames(logits, lab, frames, blank)
+            assert np.isfinite(nr).all() and np.isfinite(gr).all()
+            nll, dl = ws_run(f"full{S_max}" + ("" if frames is None else "_len"), blank)[:2]
+            assert np.isfinite(nll).all()
+            e1, e2 = rel_err(nll, nr), rel_err(dl, gr)
+            ec = max(rel_err(dl[b], gr[b]) for b in range(3))
+            print(f"ctc full rows S_max={S_max} T={T} blank={blank} frames={frames}: nll {e1:.2e} grad {e2:.2e} worst clip {ec:.2e}")
+            assert e1 < 2e-6 and e2 < 1e-5 and ec < 1e-5
+            if frames is not None:
+                for b, tb in enumerate(frames):
+                    assert not dl[b, tb:].view(np.int32).any(), "rows beyond the clip's frames are not +0"
+
+
+def test_ctc_bits_of_the_parent():
+    """nll and dlogits of every case above and of the wave-synchronous CTC_CASES are, bit for bit, what the commit named in the
+    fixture computed (tools/ctc_parent_bits.py wrote it from a build of that commit): merging the recursion kernels changed no bit."""
+    with open(WS_BITS) as f:
+        gold = json.load(f)
+    names = list(ws_cases())
+    assert sorted(gold["cases"]) == sorted(names)
+    for name in names:
+        V = ws_case(name)[0].shape[2]
+        assert sorted(gold["cases"][name]) == sorted([str(0), str(V - 1)])
+        for blank in (0, V - 1):
+            got, want = ws_bits(name, blank), gold["cases"][name][str(blank)]
+            if got["nll"] != want["nll"]:
+                b = next(i for i, (x, y) in enumerate(zip(got["nll"], want["nll"])) if x != y)
+                raise AssertionError(f"{name}, blank {blank}: nll of clip {b} is {got['nll'][b]:#010x}, {gold['commit']} gave {want['nll'][b]:#010x}")
+            assert got["dlogits_sha256"] == want["dlogits_sha256"], f"{name}, blank {blank}: dlogits differ from those of {gold['commit']}"
 
 
 # =============================================================================== GELU grad ===

@@ -40,8 +40,8 @@ def _ctc(logits, labels, frames=None, T_=None):
     return nll.cpu().numpy(), dl.cpu().numpy()
 
 
-# S_max 8: one state per lane (k_ctc_rec); 40: the one-wave-per-slot form (k_ctc_rec_mw); 300: k_ctc_rec_mwk; 600: the
-# block-level kernel.  Label lengths: feasible in 24 / 9 frames, and one label for the one-frame clip.
+# S_max 8: one state per lane (k_ctc_rec<1>); 40: one wave per state slot (k_ctc_rec_mw<2, 1>); 300: two slots per wave
+# (k_ctc_rec_mw<16, 2>); 600: the block-level kernel.  Label lengths: feasible in 24 / 9 frames, and one label for the one-frame clip.
 @pytest.mark.parametrize("S_max", [8, 40, 300, 600])
 def test_ctc_len_equals_the_clip_alone(S_max):
     rng = np.random.default_rng(S_max)
