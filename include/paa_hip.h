@@ -346,6 +346,34 @@ paa_status paa_drift_apply(const uint64_t* d_rq, const float* d_in, float* d_out
 paa_status paa_noise_add(uint64_t seed, int32_t* d_counter, int stream_id, int clip_base, const float* d_clean,
                          const float* d_snr_db, float* d_sigma /* (B) */, float* d_rows, int B, int L, void* stream);
 
+/* ---- per-clip perturbations through the playback chain: the two ends and the vote (extension) -------------------
+ * A batch of B clips, each with a perturbation of its own, is heard through G draws of the chain above: R = B * G rows,
+ * r = b * G + g.  What is played is the mixture: one loudspeaker emits x_b + delta_b at the gain a_r of draw r,
+ *   rows[r][i] = a_r * (clean[b][i] + delta[b][i])                                       (paa_eot_rows)
+ *   grad[b][i] = sum_g a_r * G[r][i]                                                     (paa_eot_reduce, its adjoint in delta)
+ * and paa_eot_vote picks, per clip, the word-error counters of the draw that is worst for the attacker.  The links between the
+ * two ends are the entries above, on R rows.  All three are asynchronous on the stream, allocate nothing, are capturable, use no
+ * atomics, and their results do not depend on the grid: two calls give the same bits.  64-bit element offsets; rows need no
+ * alignment (16-byte accesses where a row's pointers share their offset within 16 bytes, after a scalar head and before a scalar
+ * tail; element by element otherwise).  Null pointers (except where stated), B < 1, G < 1, L < 1 or B * G > INT32_MAX: PAA_ERR_ARG
+ * before any launch, outputs untouched.  They are additions to ABI 350.
+ *
+ * paa_eot_rows: ONE f32 add, then ONE f32 multiply, never contracted.  d_clean NULL: the add is skipped (rows = a * delta);
+ * d_gain NULL: the multiply is skipped.  d_clean_rows (nullable; needs d_clean): clean_rows[r][i] = clean[b][i], the level
+ * reference paa_noise_add reads per row.  The outputs must not overlap the inputs. */
+paa_status paa_eot_rows(const float* d_clean /* (B, L) nullable */, const float* d_delta /* (B, L) */,
+                        const float* d_gain /* (B * G) nullable */, float* d_rows /* (B * G, L) */,
+                        float* d_clean_rows /* (B * G, L) nullable */, int B, int G, int L, void* stream);
+/* d_grad_rows (B * G, L) -> d_grad (B, L), WRITTEN, not accumulated.  Every output is owned by one thread; the terms
+ * (double) a_r * (double) G[r][i] (exact in f64) are added in f64, g ascending, and rounded once to f32.  d_gain NULL = 1.  B = 1
+ * gives the bits of paa_place_reduce(B = G, shifts 0, Lp = L). */
+paa_status paa_eot_reduce(const float* d_grad_rows, const float* d_gain /* (B * G) nullable */, float* d_grad, int B, int G, int L,
+                          void* stream);
+/* d_counts_rows (B * G, 3): the (errors, reference words, hypothesis words) of paa_wer_counts per row -> d_counts (B, 3): the
+ * triple of the draw with the fewest errors (targeted = 0) or the most errors (targeted != 0); ties go to the lowest g.  A clip
+ * that "succeeds" on the voted counters succeeds in every draw. */
+paa_status paa_eot_vote(const int32_t* d_counts_rows, int B, int G, int targeted, int32_t* d_counts, void* stream);
+
 /* ------------------------------------------------------------------ model context ---------- */
 /* Wav2Vec2ForCTC forward + CTC loss + backward to the waveform (core/loss_helpers.py:12-23 ->
  * transformers modeling_wav2vec2.py:1667-1736; training_utils/train.py:136-158). */

@@ -23,6 +23,11 @@ while its attack succeeds and lowered while it fails, and the record describes t
 (``alpha_found``, ``alpha_step``, ``best_masking_loss``, ``best_alpha``, ``last_alpha``).  Together with ``--bound_search shrink`` the
 run has two stages (Qin et al. 2019): the bound search for ``--stage1_steps`` steps without the masking loss, then the alpha
 schedule for the remaining steps, started from every clip's stage-1 delta under the bound stage 1 found.
+
+``--eot_draws G`` (with at least one of ``--place_gain_db``, ``--rir_bank``, ``--drift_ppm``, ``--noise_snr_db``) makes the
+attack robust to playback: every step hears each clip's x + delta through G draws of the playback chain and sums the gradient over
+them.  Afterwards the reported delta is scored through ``--eot_eval_draws`` fixed evaluation draws (``eot_adv_wer``, ``eot_clean_wer``,
+``eot_success``, ``eot_draws`` in the records, their means in the summary); the direct scores stay as they are.
 """
 from __future__ import annotations
 
@@ -36,7 +41,7 @@ import torch
 
 from .core import iso, loss_helpers
 from .core.masking import masking_loss
-from .training_utils import build, modes, parser, save
+from .training_utils import build, chain, modes, parser, save
 from .training_utils.clip_attack import ClipStepper, clip_nll, compose_rows, init_rows, project_rows
 
 SPLITS = ("test", "val", "train")
@@ -52,6 +57,9 @@ SEARCH_FIELDS = ("found", "found_step", "bound_scale", "last_scale")
 # (NaN: none kept), the alpha it was optimised under (the last alpha when none was kept) and the alpha the schedule ended at
 ANNEAL_FIELDS = ("alpha_found", "alpha_step", "best_masking_loss", "best_alpha", "last_alpha")
 STAGE1_FIELD = "stage1_masking_loss"       # two-stage run only: l_b of the delta that entered stage 2
+# --eot_draws only: the reported delta through E fixed evaluation draws of the playback chain — mean WER of x + delta, of x alone
+# through the same channels, the share of draws that succeed by the bound search's criterion, and E
+EOT_FIELDS = ("eot_adv_wer", "eot_clean_wer", "eot_success", "eot_draws")
 
 
 def create_arg_parser():
@@ -79,6 +87,12 @@ def create_arg_parser():
     p.add_argument("--stage1_steps", type=int, default=None,
                    help="--bound_search shrink with --alpha_search qin: steps of the bound search before the alpha schedule takes "
                         "over (default pgd_steps // 2)")
+    p.add_argument("--eot_draws", type=int, default=0,
+                   help=f"G in [1, {modes.EOT_DRAWS_MAX}]: every clip's adversarial example x + delta is played through G draws of the "
+                        "playback chain per step (--place_gain_db, --rir_bank, --drift_ppm, --noise_snr_db; at least one) and the "
+                        "gradient is summed over the draws; 0 = off")
+    p.add_argument("--eot_eval_draws", type=int, default=None,
+                   help="--eot_draws: fixed evaluation draws the finished perturbation is scored through (default: eot_draws)")
     return p
 
 
@@ -130,19 +144,34 @@ def summarize(records, targeted: bool = False):
         hit = [r for r in records if r["alpha_found"]]
         out["alpha_success_rate"] = len(hit) / n
         out["mean_best_masking_loss"] = sum(float(r["best_masking_loss"]) for r in hit) / len(hit) if hit else float("nan")
+    if records and "eot_draws" in records[0]:      # --eot_draws: the means of the scores through the evaluation draws
+        out |= {k: sum(float(r[k]) for r in records) / n for k in EOT_FIELDS[:3]}
     return out
 
 
-def results_dict(records, args):
+def eot_eval_draws(args) -> int:
+    """E of --eot_eval_draws (default G); 0 with the mode off."""
+    g = modes.check(modes.Modes.of(args), ("eot_range",)).eot_draws
+    e = getattr(args, "eot_eval_draws", None)
+    e = g if e is None else e
+    if g and not (isinstance(e, int) and not isinstance(e, bool) and 1 <= e <= 4096):
+        raise ValueError(f"eot_eval_draws must be an integer in [1, 4096], got {e}")
+    return int(e) if g else 0
+
+
+def results_dict(records, args, length=None):
+    """``length``: the clip length, for the chain's keys of a run with --eot_draws."""
     targeted = args.attack_mode == "targeted"
-    return {"norm_type": str(args.norm_type), "attack_mode": args.attack_mode, "optimizer_type": args.optimizer_type,
-            "split": args.split, "pgd_steps": int(args.pgd_steps), "clips": list(records),
-            "summary": summarize(records, targeted)}
+    out = {"norm_type": str(args.norm_type), "attack_mode": args.attack_mode, "optimizer_type": args.optimizer_type,
+           "split": args.split, "pgd_steps": int(args.pgd_steps)}
+    if modes.Modes.of(args).eot_on:
+        out |= {"eot_draws": int(args.eot_draws), "eot_eval_draws": eot_eval_draws(args), **chain.results_extra(args, length)}
+    return out | {"clips": list(records), "summary": summarize(records, targeted)}
 
 
-def write_results(path, records, args):
+def write_results(path, records, args, length=None):
     with open(path, "w") as f:
-        json.dump(results_dict(records, args), f, indent=2)
+        json.dump(results_dict(records, args, length), f, indent=2)
 
 
 def _wer(pred, ref):
@@ -200,7 +229,7 @@ def _run_search(stepper, delta, x, labels, steps, refs):
     stepper.set_refs(refs)
     stepper.search_reset(B)
     stepper.stats_log.cursor.zero_()                                    # nobody reads the per-step log here: keep it from filling
-    step_logits = torch.empty(B, stepper.model.frames, stepper.model.arch.vocab_size, dtype=torch.float32, device=x.device)
+    step_logits = torch.empty(B * max(stepper.G, 1), stepper.model.frames, stepper.model.arch.vocab_size, dtype=torch.float32, device=x.device)
     for _ in range(int(steps)):
         stepper.step(delta.data, x, labels, logits_out=step_logits)
     found_step = stepper.best_step[:B].clone()
@@ -227,6 +256,46 @@ def _run_anneal(stepper, delta, x, labels, steps, refs):
             stepper.best_alpha[:B].cpu(), stepper.alpha_rows[:B].cpu(), entered.cpu())
 
 
+def eot_scores(model, processor, args, stepper, x, delta, texts):
+    """The reported ``delta`` (B, L) of a batch through E fixed evaluation draws of the playback chain (``stepper.eval_rows``: the
+    evaluation stream at steps 0, 1, ..., G draws per pass) -> {field of EOT_FIELDS: one value per clip}.  The clean clips go
+    through the same channels, noise included.  A draw succeeds by the bound search's criterion: WER against the clip's own
+    transcript >= --search_success_wer (rounded to thousandths), or in targeted mode the target transcript exactly."""
+    B, G, E = x.shape[0], stepper.G, eot_eval_draws(args)
+    targeted = args.attack_mode == "targeted"
+    milli, blank = modes._wer_milli(args), int(model.arch.pad_token_id)
+    rep = lambda seq: [t for t in seq for _ in range(G)]
+    row_texts = rep(texts)
+    judged = [" ".join([args.target] * args.target_reps)] * (B * G) if targeted else row_texts
+    labels = loss_helpers.make_labels(row_texts, processor, args, B * G)
+    zero, none = stepper.zero_rows[: B * G], torch.zeros_like(delta)
+    adv, cln, hits = [[] for _ in range(B)], [[] for _ in range(B)], [0] * B
+
+    def decode(p):
+        """Greedy transcripts of the rows the microphone hears (clipped, as in the step)."""
+        return loss_helpers.wer_texts(model.forward(zero, p, labels, clamp=True)["logits"], row_texts, processor, None, blank)[0]
+
+    def counts(pred, refs):
+        """Per-row (errors, reference words)."""
+        return [loss_helpers.wer_counts([a], [b.lower()]) for a, b in zip(pred, loss_helpers.clean_transcripts(refs))]
+
+    for k in range(-(-E // G)):
+        keep = min(G, E - k * G)                     # the last pass may hold more draws than are still wanted
+        pred = decode(stepper.eval_rows(delta, x, k))
+        heard = counts(pred, row_texts)
+        judge = counts(pred, judged) if targeted else heard
+        clean = counts(decode(stepper.eval_rows(none, x, k)), row_texts)
+        for b in range(B):
+            for g in range(keep):
+                r = b * G + g
+                adv[b].append(heard[r][0] / max(heard[r][1], 1))
+                cln[b].append(clean[r][0] / max(clean[r][1], 1))
+                e, w = judge[r]
+                hits[b] += int(w > 0 and (e == 0 if targeted else e * 1000 >= milli * w))
+    return {"eot_adv_wer": [sum(v) / E for v in adv], "eot_clean_wer": [sum(v) / E for v in cln],
+            "eot_success": [h / E for h in hits], "eot_draws": [E] * B}
+
+
 def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, stepper=None, lengths=None):
     """Attack one batch of clips (x (B, L) on the device) and return (records, delta, adversarial waveforms).  ``lengths``
     (--clip_lengths true): the clips' true sample counts — the model masks the padding, delta_b[len_b:] stays zero, and the
@@ -249,13 +318,21 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
         model.set_lengths(None)
     project_rows(delta, x, args, interp, spl_thresh, lengths)             # build.py:301-304, per clip
     steps, stage1 = int(args.pgd_steps), 0
+    G = modes.Modes.of(args).eot_draws if modes.Modes.of(args).eot_on else 0
     if anneal is None:
         skw = {} if search is None else dict(device_wer=True, canon=canon, search=search)      # the search runs on the device WER route
+        if G:
+            skw["eot_draws"] = G
         if args.optimizer_type == "adam":
             optimizer = torch.optim.Adam([delta], lr=args.lr)
             stepper = ClipStepper(model, args, L, interp, spl_thresh, optimizer=optimizer, **skw)
         elif stepper is None:
             stepper = ClipStepper(model, args, L, interp, spl_thresh, **skw)
+        if G:       # a clip's draws depend on (seed, its global index, draw, step) alone: row ids from the index, steps from 0
+            if list(idx) != list(range(int(idx[0]), int(idx[0]) + B)):
+                raise ValueError(f"--eot_draws needs a shard of contiguous clip indices, got {list(idx)}")
+            stepper.set_eot_clip(int(idx[0]))
+            stepper.set_eot_step(0)
         if search is None:
             for _ in range(steps):
                 stepper.step(delta.data, x, labels, want_logits=False)          # reads the model's length buffer, set above
@@ -303,6 +380,7 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
         clean_w = [_wer(clean_pred[b], refs[b].lower()) for b in range(B)]
         adv_w = [_wer(adv_pred[b], refs[b].lower()) for b in range(B)]
         target_w = [_wer(adv_pred[b], target.lower()) for b in range(B)] if targeted else None
+    eot = eot_scores(model, processor, args, stepper, x, delta, texts) if G else None
     dm, xm = delta, x
     if lengths is not None:          # the norms and the SNR of delta_b[:len_b] against x_b[:len_b]
         keep = torch.arange(L, device=x.device)[None, :] < lengths.to(x.device)[:, None]
@@ -332,13 +410,21 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
                     "best_alpha": float(best_alpha[b] if ok else last_alpha[b]), "last_alpha": float(last_alpha[b])}
             if search is not None:
                 rec[STAGE1_FIELD] = float(entered_loss[b])
+        if eot is not None:
+            rec |= {k: eot[k][b] for k in EOT_FIELDS}
         records.append(rec)
     return records, delta, compose_rows(x, delta, lengths), stepper
 
 
 def main(args) -> int:
     # what per-clip perturbations do not run with, and the refusals of --clip_lengths true: before any launch or collective
-    lengths_mode = modes.check(modes.Modes.of(args), ("place_clips", "rir_clips", "chan_range", "chan_clips") + modes.LENGTHS).lengths_on
+    # --eot_draws lifts the three "per-clip" refusals and puts its own rules, then the links' own flag checks, in their place
+    eot = modes.check(modes.Modes.of(args), ("eot_range",)).eot_on
+    per_clip = ("chan_range",) + modes.EOT if eot else ("place_clips", "rir_clips", "chan_range", "chan_clips")
+    lengths_mode = modes.check(modes.Modes.of(args), per_clip + modes.LENGTHS).lengths_on
+    if eot:
+        chain.check_flags(args)
+        eot_eval_draws(args)
     modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS + modes.MARGIN, modes.Ctx(search=modes.SearchConfig.of(args)))
     modes.check(modes.Modes.of(args), modes.ANNEAL_FLAGS, modes.anneal_ctx(args))
     if not torch.cuda.is_available():
@@ -350,14 +436,16 @@ def main(args) -> int:
     args.attack_size_string = build.attack_size_string(args)
     root = getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"clips_{args.norm_type}_{args.attack_size_string}{build.masking_loss_suffix(args)}_"
+                                 f"clips_{args.norm_type}_{args.attack_size_string}{build.masking_loss_suffix(args)}"
+                                 f"{chain.suffix(args) + f'_eot{int(args.eot_draws)}' if eot else ''}_"
                                  f"{args.attack_mode}_{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)
     interp = iso.build_weight_interpolator()
     spl_thresh = build.init_phon_threshold_tensor(args)
     batches, length = split_batches(args, world)
     mine = clip_batches(batches, rank, world)
-    model, processor = build.load_model(args, max_batch=max([len(item[1]) for item in mine] or [1]), length=length)
+    rows_per_clip = int(args.eot_draws) if eot else 1          # the model hears every clip through that many draws
+    model, processor = build.load_model(args, max_batch=max([len(item[1]) for item in mine] or [1]) * rows_per_clip, length=length)
     records, stepper = [], None
     n_wav = int(args.num_items_to_inspect)
     for item in mine:
@@ -378,7 +466,7 @@ def main(args) -> int:
                   flush=True)
     records = gather_records(records, world)
     if rank == 0:
-        write_results(os.path.join(args.save_dir, "clip_results.json"), records, args)
+        write_results(os.path.join(args.save_dir, "clip_results.json"), records, args, length)
         print(json.dumps(summarize(records, args.attack_mode == "targeted")), flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -28,6 +28,18 @@ Adaptive masking-loss weight: with ``anneal=AnnealConfig(...)``
 the step kept in ``best`` / ``best_loss`` / ``best_alpha`` / ``best_step``; alpha_b rises on success and falls on failure, on the
 periods of the config.  ``bound_scale`` (B, device) fixes per-clip bound scales nothing writes (``paa_project_rows_scaled``): the
 scales stage 1 of the two-stage run found.
+
+The playback chain: with ``eot_draws=G`` the adversarial example x_b + delta_b of every clip is heard through G
+draws of the chain (``chain.ClipChain``: gain, drift, rooms, noise — the links the flags switch on, at least one), R = B * G model
+rows, r = b * G + g:
+
+    s_r = a_r (x_b + delta_b)     w_r = noise_r + rooms_r(drift_r(s_r))     loss = sum_r CTC(clamp(w_r, -1, 1), labels_b)
+    g_b = sum_g a_r drift_r^T(rooms_r^T(G_r))      then the update and the projections of delta_b against x_b, as above
+
+The model's "clean" operand is a zero buffer and w its p rows, so its clamp is the microphone's clipping.  Launches: [``paa_place_draw``]
+-> ``paa_eot_rows`` -> the links -> ``paa_model_fwd_bwd_rows`` on R rows -> the device WER on R rows -> ``paa_eot_vote`` (a clip's
+counters are those of its draw that is worst for the attacker) -> ``paa_clip_search`` on the voted counters -> the links' adjoints
+-> ``paa_eot_reduce`` -> update -> projections.  Labels and reference rows are given per clip and repeated per draw on the host.
 """
 from __future__ import annotations
 
@@ -35,24 +47,33 @@ import numpy as np
 import torch
 
 from .. import _lib, runtime, synth
-from .modes import (LENGTHS, SEARCH_FLAGS, AnnealConfig, Ctx, Modes, SearchConfig, check,  # noqa: F401  (configs: re-exported)
+from . import chain, place
+from .modes import (EOT, LENGTHS, SEARCH_FLAGS, AnnealConfig, Ctx, Modes, SearchConfig, check,  # noqa: F401  (configs: re-exported)
                     replace)
-from .pgd import N_STATS, ST_LOSS, _StepperCore
+from .pgd import N_STATS, ST_LOSS, PgdStepper, _StepperCore
 
 
 class ClipStepper(_StepperCore):
     """The per-clip step: ``step(delta, clean, labels)`` updates ``delta`` (B, L) in place, row b from clip b alone."""
 
     def __init__(self, model, args, length: int, interp=None, spl_thresh=None, optimizer=None, device_wer=False, canon=None,
-                 r_cap=None, log_cap=4096, search=None, anneal=None, bound_scale=None):
+                 r_cap=None, log_cap=4096, search=None, anneal=None, bound_scale=None, eot_draws=0):
         """``device_wer`` / ``canon`` / ``r_cap`` / ``log_cap`` as PgdStepper's; ``wer_rows[:B]`` keeps the per-clip (errors,
         reference words, hypothesis words) of the last step.  ``search``: a ``SearchConfig`` switches the per-clip bound search on
         (module docstring); it needs ``device_wer=True``, and ``refs`` are then the transcripts success is judged against (the
         target transcript in targeted mode).  Call ``search_reset(B)`` before the first step of every batch.  ``anneal``: an
         ``AnnealConfig`` switches the per-clip alpha schedule on (module docstring); it needs ``device_wer=True`` and
         ``masking_loss_alpha`` > 0 (alpha0), and excludes ``search``.  Call ``anneal_reset(B)`` before the first step of every batch.
-        ``bound_scale``: a float32 (B) device tensor of fixed per-clip bound scales for the projections."""
+        ``bound_scale``: a float32 (B) device tensor of fixed per-clip bound scales for the projections.  ``eot_draws``: G >= 1
+        runs every clip through G draws of the playback chain (module docstring); the model then holds B * G rows, so the
+        stepper takes at most ``model.max_batch // G`` clips."""
         self.search, self.anneal = search, anneal
+        self.G = int(check(Modes.of(args, eot_draws=eot_draws), ("eot_range",)).eot_draws)
+        if self.G:       # refusals first: the new rules, then the links' own (masking, eager Adam) in the chain's order
+            check(Modes.of(args, eot_draws=self.G), EOT)
+            chain.check(args, int(length), int(length))
+            if anneal is not None:
+                raise NotImplementedError("the alpha schedule needs the masking loss, which does not run through the playback chain")
         if anneal is not None:
             if search is not None:
                 raise ValueError("anneal and search cannot share a stepper: the two-stage run uses one stepper per stage")
@@ -68,9 +89,16 @@ class ClipStepper(_StepperCore):
             if not device_wer:
                 raise ValueError("the bound search decides success from the on-device WER counters: build the stepper with "
                                  "device_wer=True")
-        self.max_batch = int(model.max_batch)
+        self.max_batch = int(model.max_batch) // max(self.G, 1)          # clips; the model's rows are clips x draws
+        if self.max_batch < 1:
+            raise ValueError(f"{self.G} draws per clip need a model of at least that many rows, got max_batch {model.max_batch}")
         super().__init__(model, args, length, interp, spl_thresh, optimizer, device_wer, canon, r_cap, log_cap, self.max_batch,
                          int(length))
+        if self.G:
+            self.chain = chain.ClipChain(args, self.dev, self.max_batch * self.G, self.L, self.G, place.STREAM_TRAIN)
+            self.zero_rows = torch.zeros(self.max_batch * self.G, self.L, dtype=torch.float32, device=self.dev)   # the model's "clean"
+            if self.device_wer:
+                self.wer_clips = torch.zeros(self.max_batch, 3, dtype=torch.int32, device=self.dev)       # the voted counters
         self.grad_buf = torch.zeros(self.max_batch * self.L, dtype=torch.float32, device=self.dev)
         self.grad = self.grad_buf[: self.L].view(1, self.L)
         self.stats = torch.zeros(N_STATS, dtype=torch.float32, device=self.dev)
@@ -110,7 +138,78 @@ class ClipStepper(_StepperCore):
     def set_masking_alpha(self, alpha: float):
         if getattr(self, "anneal", None) is not None and not float(alpha) > 0:
             raise ValueError("the alpha schedule needs masking_loss_alpha > 0: that value is the weight every clip starts from")
+        if getattr(self, "G", 0) and float(alpha) > 0:
+            raise NotImplementedError("masking_loss_alpha > 0 does not run through the playback chain (eot_draws): the masking loss "
+                                      "pairs the perturbation's frames with the clean clip's frames")
         super().set_masking_alpha(alpha)
+
+    # ---- the playback chain of per-clip perturbations ------------------------------------------------------
+    def _site(self, name):
+        """The chain's site ``name``; raises when the stepper was built without the chain or with that link off."""
+        if not self.G:
+            raise RuntimeError("the stepper was built without the playback chain (eot_draws=G)")
+        on, off = PgdStepper._SITES[name]
+        if not getattr(self.modes, on):
+            raise RuntimeError(f"the stepper was built with {off}")
+        return getattr(self.chain, name)
+
+    def set_gains(self, gain):
+        """Explicit per-row gains (B * G, r = b * G + g) instead of the draw, from the next step on (stream-ordered copy);
+        ``set_gains(None)`` returns to drawing.  A captured graph keeps the form it was captured with."""
+        pl = self._site("placer")
+        pl.set_placement(None if gain is None else [0] * len(gain), gain)
+
+    def set_rooms(self, index):
+        """The same for per-row room indices."""
+        self._site("reverb").set_rooms(index)
+
+    def set_channel(self, ratio, snr_db=None):
+        """The same for per-row clock ratios (and noise SNRs in dB); the noise samples stay fresh."""
+        self._site("chan").set_channel(ratio, snr_db)
+
+    def set_eot_step(self, n: int):
+        """Device step counters of the chain's next draws (0 at the start of every batch: a clip's draws then depend on the seed,
+        its global index, the draw and the step alone)."""
+        if not self.G:
+            raise RuntimeError("the stepper was built without the playback chain (eot_draws=G)")
+        self.chain.set_step(n)
+
+    def set_eot_clip(self, first: int):
+        """Global index of the batch's first clip: row r of the following steps draws under the id G * first + r
+        (``chain.clip_base``).  A captured graph holds the value it was captured with."""
+        if not self.G:
+            raise RuntimeError("the stepper was built without the playback chain (eot_draws=G)")
+        self.chain.clip_base = self.G * int(first)
+
+    def eval_rows(self, delta, clean, step: int):
+        """The B * G rows of evaluation pass ``step``: delta, clean (B, L) through a chain of the evaluation stream
+        (place.STREAM_EVAL) whose every counter is set to ``step`` first, at this stepper's ``clip_base`` — so two calls hear the
+        same channels and the same noise, whatever ``delta`` holds.  The rows live in the evaluation chain's buffers until the
+        next call.  Allocates on first use; for scoring, not for the step."""
+        if not self.G:
+            raise RuntimeError("the stepper was built without the playback chain (eot_draws=G)")
+        delta, clean = self._checked(delta, clean)
+        if getattr(self, "_eval_chain", None) is None:
+            self._eval_chain = chain.ClipChain(self.args, self.dev, self.max_batch * self.G, self.L, self.G, place.STREAM_EVAL,
+                                               with_grad=False)
+        ev = self._eval_chain
+        ev.clip_base = self.chain.clip_base
+        ev.set_step(int(step))
+        return ev.rows(delta, clean.shape[0], clean)
+
+    def set_refs(self, refs):
+        """As the core's; with the chain on, a batch's (B, r_cap) rows are repeated per draw here on the host."""
+        if self.G > 1:
+            if refs.dim() != 2 or refs.shape[0] > self.max_batch:
+                raise ValueError(f"refs must hold one row per clip (B <= {self.max_batch}), got {tuple(refs.shape)}")
+            refs = refs.repeat_interleave(self.G, dim=0)
+        super().set_refs(refs)
+
+    def _row_labels(self, labels, B):
+        """Labels of B clips -> one row per draw (host-side repeat; rows already B * G are taken as they are)."""
+        if self.G > 1 and labels.shape[0] == B:
+            labels = labels.repeat_interleave(self.G, dim=0)
+        return labels
 
     def search_reset(self, B=None):
         """A new batch: scale = 1, best_step = -1, step = 0 (stream-ordered fills, outside any graph).  ``best`` rows and
@@ -129,6 +228,8 @@ class ClipStepper(_StepperCore):
             st += [self.scale, self.best, self.best_scale, self.best_step, self.search_step]
         if self.anneal is not None:
             st += [self.alpha_rows, self.best, self.best_loss, self.best_alpha, self.best_step, self.anneal_step]
+        if self.G:
+            st += self.chain.counters()
         return st
 
     def _check_adam_shape(self):
@@ -151,21 +252,35 @@ class ClipStepper(_StepperCore):
         lib, L, B = _lib.lib(), self.L, clean.shape[0]
         grad = self.grad_buf[: B * L].view(B, L)
         self.grad = grad
-        out = {"grad": grad, "stats": self.stats}
+        G = self.G
+        R = B * G if G else B                      # rows the model sees
+        out = {"grad": self.chain.placer.grad_rows[:R] if G else grad, "stats": self.stats}
         if logits_out is not None:
             out["logits"] = logits_out
-        r = self.model.fwd_bwd(clean, delta, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
+        if G:       # the model's "clean" operand is zero and its p rows are what the microphone hears: its clamp is the clipping
+            r = self.model.fwd_bwd(self.zero_rows[:R], self.chain.rows(delta, B, clean), labels, self.direction, want_grad=True,
+                                   want_logits=want_logits, out=out)
+            r["grad_rows"] = r["grad"]
+        else:
+            r = self.model.fwd_bwd(clean, delta, labels, self.direction, want_grad=True, want_logits=want_logits, out=out)
         ac = self.anneal
         if self.mask_alpha > 0:
             self._masking_loss(delta, clean, grad, self.mask_rows[:B], None if ac is None else self.alpha_rows)
             r["masking_loss"] = self.mask_rows[:B]
+        counts = None
         if self.device_wer:
-            self._wer(r["logits"], B)
+            self._wer(r["logits"], R)
+            counts = self.wer_rows
+            if G:       # a clip's counters are those of its draw that is worst for the attacker: success means every draw succeeded
+                counts = self.wer_clips
+                with torch.cuda.device(self.dev):
+                    _lib.check(lib.paa_eot_vote(_lib.ptr(self.wer_rows), B, G, int(self.direction < 0), _lib.ptr(counts),
+                                                _lib.stream_ptr()))
         with torch.cuda.device(self.dev):
             st = _lib.stream_ptr()
             sc = self.search
             if sc is not None:       # the counters are those of the delta that entered the step: keep it BEFORE the update
-                _lib.check(lib.paa_clip_search(_lib.ptr(delta), B, L, _lib.ptr(self.wer_rows), int(bool(sc.targeted)),
+                _lib.check(lib.paa_clip_search(_lib.ptr(delta), B, L, _lib.ptr(counts), int(bool(sc.targeted)),
                                                int(sc.wer_milli), float(sc.shrink), float(sc.floor_scale), _lib.ptr(self.scale),
                                                _lib.ptr(self.best), _lib.ptr(self.best_scale), _lib.ptr(self.best_step),
                                                _lib.ptr(self.search_step), st))
@@ -175,6 +290,8 @@ class ClipStepper(_StepperCore):
                                                float(ac.up), float(ac.down), float(ac.alpha_min), float(ac.alpha_max),
                                                _lib.ptr(self.alpha_rows), _lib.ptr(self.best), _lib.ptr(self.best_loss),
                                                _lib.ptr(self.best_alpha), _lib.ptr(self.best_step), _lib.ptr(self.anneal_step), st))
+            if G:       # the chain's adjoints, then the sum over every clip's draws into its own row
+                self.chain.reduce(B, grad)
             self._update(delta, grad, B * L)
             scale = self.scale if sc is not None else self.bound_scale
             if scale is not None and scale.numel() < B:
@@ -204,7 +321,7 @@ class ClipStepper(_StepperCore):
         delta, clean = self._checked(delta, clean)
         self._check_p(delta)
         self._pre_step()
-        return self._body(delta, clean, labels, want_logits, logits_out)
+        return self._body(delta, clean, self._row_labels(labels, clean.shape[0]), want_logits, logits_out)
 
     def capture(self, delta, clean, labels, logits_out=None, refs=None, lengths=None):
         """One step on fixed buffers as ONE hipGraph (``refs`` / ``lengths`` as PgdStepper.capture).  Returns (graph, result dict);
@@ -213,10 +330,13 @@ class ClipStepper(_StepperCore):
         count as before the call).  With a bound search the warm-up step is undone with either update — delta and the search
         buffers (scale, best, best_scale, best_step, step) are as before the call, so the first replay is the step an eager
         call would have been.  The same holds for the alpha schedule and its buffers (alpha_rows, best, best_loss, best_alpha,
-        best_step, step)."""
+        best_step, step), and for the playback chain (``eot_draws``): delta and every draw counter are as before the call, so
+        capture plus n replays is n eager steps, draw for draw."""
         delta, clean = self._checked(delta, clean)
-        keep = delta.detach().clone() if self.search is not None or self.anneal is not None else None
-        lab, logits_out = self._warm_up(delta, clean, labels, logits_out, refs, lengths)
+        keep = delta.detach().clone() if self.search is not None or self.anneal is not None or self.G else None
+        if self.G and logits_out is None:          # one row of logits per draw
+            logits_out = torch.empty(clean.shape[0] * self.G, self.model.frames, self.model.arch.vocab_size, device=self.dev)
+        lab, logits_out = self._warm_up(delta, clean, self._row_labels(labels, clean.shape[0]), logits_out, refs, lengths)
         if keep is not None:
             delta.detach().copy_(keep)
         return self._capture_body(delta, clean, lab, logits_out)

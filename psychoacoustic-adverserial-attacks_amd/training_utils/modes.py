@@ -10,6 +10,7 @@ from dataclasses import dataclass, replace  # noqa: F401  (replace: how a caller
 GAIN_DB_MAX = 20.0
 DRIFT_PPM_MAX = 100000.0
 NOISE_SNR_MIN, NOISE_SNR_MAX = -20.0, 100.0
+EOT_DRAWS_MAX = 64
 
 
 def _pair(v):
@@ -50,6 +51,8 @@ class Modes:
     loss_type: str = "ctc"         # --loss_type: "ctc" or "margin" (the alignment-margin loss)
     kappa: float = 1.0             # --margin_kappa, in logits
     targeted: bool = False         # --attack_mode targeted
+    eot_draws: int = 0             # --eot_draws G (attack_clips only): draws of the playback chain per clip, 0 = off
+    seconds_on: bool = False       # --perturbation_seconds set
     anneal_on: bool = False        # --alpha_search other than "off" (attack_clips only)
     search_on: bool = False        # --bound_search other than "off" (attack_clips only)
 
@@ -65,7 +68,8 @@ class Modes:
                    str(get("clip_lengths", "padded")) == "true", bool(get("device_wer", False)), get("optimizer_type", None),
                    drift_ppm=_num(get("drift_ppm", 0.0) or 0.0), noise_snr=_pair(get("noise_snr_db", None)),
                    search_on=str(get("bound_search", "off")) != "off", anneal_on=str(get("alpha_search", "off")) != "off", loss_type=str(get("loss_type", "ctc")),
-                   kappa=_num(get("margin_kappa", 1.0)), targeted=str(get("attack_mode", "untargeted")) == "targeted")
+                   kappa=_num(get("margin_kappa", 1.0)), targeted=str(get("attack_mode", "untargeted")) == "targeted",
+                   eot_draws=get("eot_draws", 0) or 0, seconds_on=get("perturbation_seconds", None) is not None)
 
     drift_on = property(lambda m: isinstance(m.drift_ppm, float) and m.drift_ppm > 0)
     noise_on = property(lambda m: m.noise_snr is not None)
@@ -74,6 +78,8 @@ class Modes:
     masking = property(lambda m: m.masking_norm or m.alpha > 0)      # either pairs delta's frames with the clean clip's
     chan_why = property(lambda m: _chan_bad(m))
     margin_on = property(lambda m: m.loss_type == "margin")
+    eot_on = property(lambda m: isinstance(m.eot_draws, int) and not isinstance(m.eot_draws, bool) and m.eot_draws >= 1)
+    link_on = property(lambda m: m.place_on or m.rir_on or m.chan_on)      # at least one link of the playback chain
 
 
 SIZED_NORMS = ("l2", "linf", "snr", "tv", "fletcher_munson", "max_phon")      # the norms a bound scale tightens (min_max_freqs has no size)
@@ -246,6 +252,16 @@ RULES = {
     "margin_kappa": Rule("margin_on", lambda m, c: not (isinstance(m.kappa, (int, float)) and not isinstance(m.kappa, bool)
                                                         and 0.0 <= m.kappa < float("inf")), ValueError,
                          "margin_kappa must be finite and >= 0, got {m.kappa}"),
+    # per-clip perturbations through the playback chain
+    "eot_range": Rule(None, lambda m, c: not (isinstance(m.eot_draws, int) and not isinstance(m.eot_draws, bool)
+                                              and 0 <= m.eot_draws <= EOT_DRAWS_MAX), ValueError,
+                      f"eot_draws must be an integer in [0, {EOT_DRAWS_MAX}], got {{m.eot_draws}}"),
+    "eot_links": Rule("eot_on", lambda m, c: not m.link_on, ValueError,
+                      "--eot_draws needs at least one link of the playback chain (--place_gain_db, --rir_bank, --drift_ppm, "
+                      "--noise_snr_db): without one all draws of a clip are equal"),
+    "eot_shift": Rule("eot_on", lambda m, c: m.shift_on or m.seconds_on, NIE,
+                      "--eot_draws does not run with --place_shift random or --perturbation_seconds: a per-clip perturbation is "
+                      "as long as its clip and has no position of its own"),
 }
 
 PLACE_FLAGS = ("shift_range", "gain_range", "place_masking")
@@ -256,6 +272,7 @@ CHANNEL = CHANNEL_FLAGS + ("chan_eager",)
 LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir", "len_chan")
 SEARCH_FLAGS = ("search_range", "search_masking", "search_no_size")       # known from the flags alone
 MARGIN = ("margin_untargeted", "margin_kappa")                            # known from the flags alone
+EOT = ("eot_range", "eot_links", "eot_shift")                              # known from the flags alone
 SEARCH = SEARCH_FLAGS + ("search_route",)                                  # ... and once the vocabulary and the references are known
 
 

@@ -40,6 +40,10 @@
     per-clip step only; needs device WER and   paa_clip_anneal                                            after the device WER counters, before
     ``masking_loss_alpha`` > 0; no search)                                                                the update
     fixed bound scales (``bound_scale=``)      paa_project_rows_scaled                                    in place of paa_project_rows
+    playback chain of per-clip steps           paa_eot_rows, then the links' launches above on B * G       before the forward pass, in place of
+    (``eot_draws=G``; per-clip step only;      rows (paa_place_draw for the gains only)                    paa_place_rows
+    at least one link on)                      paa_eot_vote (device WER only)                              after the device WER counters
+                                               the links' adjoints, paa_eot_reduce                         right before the update
 
 A mode that is off adds no launch: alpha = 0, ``device_wer=False``, placement off, room responses off, the channel off, lengths off,
 no bound search and no alpha schedule are the plain step, bit for bit.
