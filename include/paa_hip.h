@@ -510,6 +510,17 @@ paa_status paa_gemm(const struct paa_gemm_desc* d, void* stream);
  * selects a configuration only a -DPAA_EXPERIMENTS build holds (measured and rejected variants, timing probes); the shipped
  * library falls back to the register-staged kernels for it. */
 void paa_gemm_config(int ring_mode);
+/* Test / measurement aid: path of the fused attention backward.  0 = automatic (default: one pass in split-bf16 mode up to two
+ * 256-key blocks, T <= 512; the kernel pair beyond that and, at every T, in bf16 mode, where one pass measured slower),
+ * 1 = always the dQ and dK/dV kernel pair, 2 = one pass wherever a workspace is given, in either precision.  Any other value
+ * leaves the mode as it is.  Returns the number of one-pass dispatches since the previous call (and resets that count). */
+int paa_attn_bwd_config(int mode);
+/* Measurement aid: the attention backward with a caller-owned one-pass workspace of paa_attn_dq_part_floats() floats (null: the
+ * kernel pair); lo planes all null = bf16 mode, d_klen nullable.  The other backward entries allocate a workspace per call. */
+int64_t paa_attn_dq_part_floats(int B, int nh, int T, int Tp);
+paa_status paa_attn_bwd_ws(const void* qkv_hi, const void* qkv_lo, const void* ctx_hi, const void* ctx_lo, const float* lse,
+                           const void* dctx_hi, const void* dctx_lo, float* delta, void* dqkv_hi, void* dqkv_lo,
+                           const int32_t* d_klen, float* dq_part, int B, int T, int P, int Tp, int H, int nh, void* stream);
 /* Test aid.  option 0: value != 0 makes the GroupNorm backward of conv0 take its statistics-pass + GEMM-pass path (the fallback of
  * the shapes the fused single-pass kernel does not cover) on every shape, so that tests can compare the two on the same operands. */
 paa_status paa_test_option(int option, int value);

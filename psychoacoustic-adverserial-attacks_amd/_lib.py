@@ -133,6 +133,9 @@ _SIGS = {
     "paa_model_layout": (C.c_int, [C.c_void_p, C.c_int]),
     "paa_gemm": (C.c_int, [C.POINTER(PaaGemmDesc), C.c_void_p]),
     "paa_gemm_config": (None, [C.c_int]),
+    "paa_attn_bwd_config": (C.c_int, [C.c_int]),
+    "paa_attn_dq_part_floats": (C.c_int64, [C.c_int] * 4),
+    "paa_attn_bwd_ws": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 6 + [C.c_void_p]),
     "paa_test_option": (C.c_int, [C.c_int, C.c_int]),
     "paa_prof_enable": (C.c_int, [C.c_int]),
     "paa_prof_read": (C.c_int, [C.c_void_p]),

@@ -209,7 +209,7 @@ struct paa_model {
     float *fp_stats, *h0, *pos_pre, *hsum, *enc_stats, *xa, *xb, *final_in;
     float *logits, *dlogits, *nll, *ctc_work;
     Bf dlogitsH, dxaH, dxbH, dqkvH, dfpreH, dposH, dh0H;
-    float *dxa, *dxb, *dctx = nullptr, *dP = nullptr, *dh0, *dfn, *delta = nullptr;
+    float *dxa, *dxb, *dctx = nullptr, *dP = nullptr, *dh0, *dfn, *delta = nullptr, *dq_part = nullptr;
     Bf dctxH{nullptr, nullptr};
     int S_cap;
     // length mode (paa_model_set_lengths): the caller's per-clip sample counts (device, Bmax entries; null = off) and the
@@ -415,6 +415,8 @@ extern "C" paa_status paa_model_create(paa_model** out, const paa_arch* arch, co
         m->dqkvH = take_bf(3 * MH);
         if (m->fused) { m->dctxH = take_bf(MH); m->delta = take(LS); }
         else { m->dctx = take(MH); m->dP = take(PM); }
+        // workspace of the one-pass attention backward, where the automatic dispatch rule takes that path (attn_bwd)
+        if (m->fused && attn_onepass_auto(m->T, m->prec != 0)) m->dq_part = take(attn_dq_part_floats(B, nh, m->T, m->Tp));
         m->dfpreH = take_bf(MF, m->ail); m->dposH = take_bf(MH); m->dh0 = take(MH); m->dh0H = take_bf(MH); m->dfn = take(MC);
         m->frames = reinterpret_cast<int32_t*>(take(B));
         if (!pass) {
@@ -634,7 +636,7 @@ static paa_status backward(paa_model* m, const float* clean, const float* p, int
             AttnArgs aa{};
             aa.qkv = e.qkvH.hi; aa.ctx = e.ctxH.hi; aa.lse = e.lse; aa.dctx = m->dctxH.hi; aa.delta = m->delta; aa.dqkv = m->dqkvH.hi;
             aa.qkv_lo = e.qkvH.lo; aa.ctx_lo = e.ctxH.lo; aa.dctx_lo = m->dctxH.lo; aa.dqkv_lo = m->dqkvH.lo;
-            aa.T = T; aa.P = P; aa.Tp = Tp; aa.H = H; aa.nh = nh; aa.scale = scale; aa.klen = m->fr();
+            aa.T = T; aa.P = P; aa.Tp = Tp; aa.H = H; aa.nh = nh; aa.scale = scale; aa.klen = m->fr(); aa.dq_part = m->dq_part;
             PAA_TRY(attn_bwd(aa, B, hd, st));
         } else {
         PAA_TRY(linear(m, ro(dx2H), e.wo_t, nullptr, m->dctx, NOBF, M, H, H, st));

@@ -108,7 +108,11 @@ struct AttnArgs {
     int nbh;                        // B * nh (set by the launcher)
     float scale;                    // head_dim^-0.5
     const int32_t* klen;            // (B) per-clip key count in [1, T] (device), or null: every clip has T keys
+    float* dq_part;                 // one-pass backward workspace [ceil(T / 256)][B*nh][Tp][64] f32, or null: the two-kernel backward
 };
+int64_t attn_dq_part_floats(int B, int nh, int T, int Tp);
+bool attn_onepass_auto(int T, bool split);  // the automatic rule: split mode, at most two 256-key blocks (T <= 512)
+bool attn_bwd_onepass(int T, bool split);   // does the configured mode (paa_attn_bwd_config) take the one-pass backward here?
 paa_status attn_fwd(const AttnArgs& a, int B, int head_dim, hipStream_t st);
 paa_status attn_bwd(const AttnArgs& a, int B, int head_dim, hipStream_t st);
 
