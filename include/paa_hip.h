@@ -250,6 +250,19 @@ paa_status paa_clip_anneal(const float* d_delta /* (B, L) */, int B, int L, cons
                            int up_every, int down_every, float up, float down, float alpha_min, float alpha_max,
                            float* d_alpha /* (B) in/out */, float* d_best /* (B, L) */, float* d_best_loss /* (B) in/out */,
                            float* d_best_alpha /* (B) */, int32_t* d_best_step /* (B) */, int32_t* d_step /* [1] */, void* stream);
+/* ---- temporal masking: post- and pre-masking of the threshold (extension; addition to ABI 350) ----------------------
+ * post_db / pre_db are HOST arrays of decrements in dB: post_db[j - 1] = w_post[j] applies j frames after a masker, pre_db[j - 1] =
+ * w_pre[j] j frames before it.  With tables set, every masking entry (paa_masking_threshold, the masking projections,
+ * paa_masking_loss*) uses
+ *   theta'(t, k) = max(theta(t, k), max_{1<=j<=n_post, t-j>=0} theta(t - j, k) - w_post[j], max_{1<=j<=n_pre, t+j<T} theta(t + j, k) - w_pre[j])
+ * in place of theta: each term one f32 subtraction, the maximum exact, so the result is independent of order and tiling; the bound is
+ * A' = 10^((theta' + margin - 96 + Pmax_b) / 20), the universal bound the minimum over clips of A'_b.  One more launch
+ * (k_mask_spread) between the threshold pass and the minimum pass; pass 2 then writes theta into a second (max_batch, Tmax, F) plane
+ * that this call allocates on first use (so it is NOT capturable: call it before capture; paa_proj_destroy frees the plane).
+ * n_post = n_pre = 0 turns the mode off: the launches, arguments and bits of a handle that never saw this call.
+ * PAA_ERR_ARG: a null handle, a non-default frame geometry, n outside [0, 32], a null table with n > 0, a value that is not finite,
+ * not positive, or below its predecessor. */
+paa_status paa_proj_set_masking_spread(paa_proj* h, int n_post, const float* post_db, int n_pre, const float* pre_db);
 /* train.py:136 with one perturbation row per clip: out[b] = clamp(clean[b] + p[b], -1, 1); d_p (p_rows, L), p_rows in
  * {1, B}; p_rows = 1 is paa_compose_clamp. */
 paa_status paa_compose_clamp_rows(const float* d_clean, const float* d_p, int p_rows, float* d_out, int B, int L,

@@ -163,7 +163,7 @@ def results_dict(records, args, length=None):
     """``length``: the clip length, for the chain's keys of a run with --eot_draws."""
     targeted = args.attack_mode == "targeted"
     out = {"norm_type": str(args.norm_type), "attack_mode": args.attack_mode, "optimizer_type": args.optimizer_type,
-           "split": args.split, "pgd_steps": int(args.pgd_steps)}
+           "split": args.split, "pgd_steps": int(args.pgd_steps)} | build.masking_time_extra(args)
     if modes.Modes.of(args).eot_on:
         out |= {"eot_draws": int(args.eot_draws), "eot_eval_draws": eot_eval_draws(args), **chain.results_extra(args, length)}
     return out | {"clips": list(records), "summary": summarize(records, targeted)}
@@ -427,6 +427,7 @@ def main(args) -> int:
         eot_eval_draws(args)
     modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS + modes.MARGIN, modes.Ctx(search=modes.SearchConfig.of(args)))
     modes.check(modes.Modes.of(args), modes.ANNEAL_FLAGS, modes.anneal_ctx(args))
+    modes.check(modes.Modes.of(args), modes.MASK_TIME)
     if not torch.cuda.is_available():
         raise SystemExit("paa_amd.attack_clips needs a GPU; there is no CPU fallback")
     if not str(args.device).startswith("cuda"):
@@ -436,7 +437,7 @@ def main(args) -> int:
     args.attack_size_string = build.attack_size_string(args)
     root = getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"clips_{args.norm_type}_{args.attack_size_string}{build.masking_loss_suffix(args)}"
+                                 f"clips_{args.norm_type}_{args.attack_size_string}{build.masking_loss_suffix(args)}{build.masking_time_suffix(args)}"
                                  f"{chain.suffix(args) + f'_eot{int(args.eot_draws)}' if eot else ''}_"
                                  f"{args.attack_mode}_{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)

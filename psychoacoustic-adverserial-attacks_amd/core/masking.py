@@ -1,12 +1,26 @@
 """Clean-signal frequency-masking threshold (the ``masking`` norm): MPEG-1 psychoacoustic model 1 on the
 default frame geometry (n_fft = win_length = 1024, hop_length = 256), computed by libpaa_hip.so.  Device only: there is no
-CPU fallback."""
+CPU fallback.  With ``args.masking_post_ms`` / ``args.masking_pre_ms`` > 0 every threshold here is spread along time (temporal
+masking): the flags reach the library through the context ``runtime.get_proj`` hands out."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from .. import _lib, runtime
+
+
+def temporal_tables(args):
+    """(post_db, pre_db): the float32 decrement tables of temporal masking for ``args.masking_post_ms`` /
+    ``args.masking_pre_ms`` at ``args.hop_length`` / ``args.sr``; a flag that is 0 or missing gives an empty table.  A time of P ms
+    lets a frame's threshold fall by 60 dB over P ms: w[j] = j 60 hop 1000 / (P sr) dB at lag j, for the lags under 96 dB."""
+    if not getattr(args, "masking_post_ms", 0.0) and not getattr(args, "masking_pre_ms", 0.0):          # off: nothing to validate
+        return np.zeros(0, np.float32), np.zeros(0, np.float32)
+    from ..training_utils import modes
+    m = modes.check(modes.Modes.of(args), ("mask_time_range",))
+    tab = lambda ms: np.array([modes.mask_time_decrement(j, ms, m.hop, m.sr) for j in range(1, modes.mask_time_lags(ms, m.hop, m.sr) + 1)]
+                              if ms > 0 else [], dtype=np.float64).astype(np.float32)
+    return tab(m.post_ms), tab(m.pre_ms)
 
 
 def masking_threshold(clean: torch.Tensor, args, psd: bool = False):

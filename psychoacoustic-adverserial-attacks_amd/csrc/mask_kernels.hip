@@ -12,6 +12,8 @@
 //     10^(T_j(i) / 10) over that list in that order (hardware exp2 / log2), plus the ATH term, relative to a per-bin offset so
 //     that neither the loud end nor the 27 dB / Bark tails leave the f32 range.  Writes theta (dB) or the magnitude bound
 //     A = 10^((theta + margin - 96 + Pmax) / 20); in place over P when called from a projection.
+//  2b. k_mask_spread (temporal masking; only when paa_proj_set_masking_spread gave tables): pass 2 then writes
+//     theta into a second plane, and this pass spreads it along time (post- and pre-masking) into theta' or the bound A'.
 //  3. k_mask_min (universal perturbation only): A[0] = min over the clips.
 //
 // Deterministic: no atomics, every sum in a fixed order; results are written with vector stores.
@@ -134,6 +136,51 @@ __global__ __launch_bounds__(MW * 64) void k_mask_threshold(MaskArgs a) {
     }
 }
 
+// Temporal masking between passes 2 and 3.  grid: (ceil(T / ST), rows); a workgroup owns ST frames of one row and reads
+// its halo of n_post frames before and n_pre after from the theta plane, which is why the result goes to another plane.  A wave takes
+// units of 64 bins x SR frames: lanes along bins (dword accesses, coalesced), the SR running maxima in registers; every theta frame
+// of the unit's window is loaded once and meets all SR output frames.  The decrements sit in LDS indexed by the signed lag d = t - s,
+// 0 at d = 0 and +inf outside the two tables, so a term out of the window is -inf and the inner loop has no branch; the index is
+// uniform over the wave (a broadcast read).  Frames outside [0, T) are never loaded (T < J included), frames >= T never stored.
+constexpr int ST = 32, SR = 8, SOFF = SR - 1 + MASK_LAGS, SWN = 2 * SOFF + 1, SCH = (F + 63) / 64;
+__global__ __launch_bounds__(256) void k_mask_spread(MaskSpreadArgs a) {
+    __shared__ float wl[SWN];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (threadIdx.x < SWN) {
+        const int d = (int)threadIdx.x - SOFF;                        // frames from the masker to the masked frame
+        float w = INFINITY;
+        if (d == 0) w = 0.f;
+        else if (d > 0 && d <= a.n_post) w = a.post[d - 1];
+        else if (d < 0 && -d <= a.n_pre) w = a.pre[-d - 1];
+        wl[threadIdx.x] = w;
+    }
+    __syncthreads();
+    const int row = blockIdx.y, tile0 = blockIdx.x * ST;
+    const float* __restrict__ in = a.theta + (size_t)row * a.T * F;
+    float* __restrict__ out = a.out + (size_t)row * a.T * F;
+    const float c = a.bound ? a.margin - 96.f + a.pmax[row] : 0.f;
+    for (int u = wave; u < SCH * (ST / SR); u += 4) {
+        const int t0 = tile0 + (u / SCH) * SR, k = (u % SCH) * 64 + lane;
+        if (t0 >= a.T) break;
+        const bool live = k < F;                                      // the last chunk holds bin 512 only
+        float acc[SR];
+#pragma unroll
+        for (int r = 0; r < SR; ++r) acc[r] = -INFINITY;
+        const int s0 = max(t0 - a.n_post, 0), s1 = min(t0 + SR - 1 + a.n_pre, a.T - 1);
+#pragma unroll 4
+        for (int s = s0; s <= s1; ++s) {
+            const float v = live ? in[(size_t)s * F + k] : -INFINITY;
+            const float* w = wl + (t0 - s + SOFF);                    // w[r]: the decrement at lag (t0 + r) - s
+#pragma unroll
+            for (int r = 0; r < SR; ++r) acc[r] = fmaxf(acc[r], v - w[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < SR; ++r)
+            if (live && t0 + r < a.T) out[(size_t)(t0 + r) * F + k] = a.bound ? ex2((acc[r] + c) * (0.5f * C10)) : acc[r];
+    }
+}
+
 __global__ __launch_bounds__(256) void k_mask_min(float* __restrict__ A, int rows, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float v = A[i];
@@ -168,6 +215,12 @@ void mask_tables(int sr, float* z, float* quiet, float* ath, int* win, int* kA) 
 
 paa_status mask_threshold(const MaskArgs& a, int rows, hipStream_t st) {
     hipLaunchKernelGGL(k_mask_threshold, dim3(cdiv(a.T, MW), rows), dim3(MW * 64), 0, st, a);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
+}
+
+paa_status mask_spread(const MaskSpreadArgs& a, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(k_mask_spread, dim3(cdiv(a.T, ST), rows), dim3(256), 0, st, a);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }

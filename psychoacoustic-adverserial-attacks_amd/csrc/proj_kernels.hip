@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "paa_common.h"
@@ -513,6 +514,12 @@ struct paa_proj {
     float* d_mtab = nullptr;
     int* d_mwin = nullptr;
     int mask_kA = 0;
+    // temporal masking (paa_proj_set_masking_spread): off while both tables are empty.  d_mask2: the second
+    // (max_batch, Tmax, F) plane pass 2 writes theta into, allocated on first use; d_mpmax: Pmax per row for a caller that asks for none
+    int n_post = 0, n_pre = 0;
+    float post_db[MASK_LAGS] = {}, pre_db[MASK_LAGS] = {};
+    float* d_mask2 = nullptr;
+    float* d_mpmax = nullptr;
 };
 
 extern "C" const char* paa_last_error(void) { return paa::g_err.c_str(); }
@@ -614,7 +621,7 @@ extern "C" paa_status paa_debug_spec_stamps(paa_proj* h, long long* host, int n)
 extern "C" void paa_proj_destroy(paa_proj* h) {
     if (!h) return;
     void* ptrs[] = {h->d_tw, h->d_win, h->d_fm, h->d_thr, h->d_thr_max, h->d_frames, h->d_part, h->d_scal,
-                    h->d_mask, h->d_mpart, h->d_mtab, h->d_mwin};
+                    h->d_mask, h->d_mpart, h->d_mtab, h->d_mwin, h->d_mask2, h->d_mpmax};
     for (void* q : ptrs) if (q) (void)hipFree(q);
     delete h;
 }
@@ -649,8 +656,40 @@ static int spec_op_of(int norm) {
          : norm == PAA_NORM_MASKING ? SOP_MASK : SOP_NONE;
 }
 
+// Temporal masking: the decrement tables of the post- and pre-masking spread, post_db[j - 1] = w_post[j] dB at lag j
+// frames.  Both empty: the mode is off and masking_pass launches what it launched before this entry existed.
+extern "C" paa_status paa_proj_set_masking_spread(paa_proj* h, int n_post, const float* post_db, int n_pre, const float* pre_db) {
+    if (!h) PAA_FAIL(PAA_ERR_ARG, "paa_proj_set_masking_spread: null handle");
+    if (!fused_geometry(h) || !h->d_mask)
+        PAA_FAIL(PAA_ERR_ARG, "masking needs n_fft = win_length = 1024, hop_length = 256 (got %d / %d / %d)", h->n_fft, h->win, h->hop);
+    const int n[2] = {n_post, n_pre};
+    const float* tab[2] = {post_db, pre_db};
+    for (int s = 0; s < 2; ++s) {
+        const char* side = s ? "pre" : "post";
+        if (n[s] < 0 || n[s] > MASK_LAGS)
+            PAA_FAIL(PAA_ERR_ARG, "paa_proj_set_masking_spread: n_%s=%d must lie in [0, %d]", side, n[s], MASK_LAGS);
+        if (n[s] > 0 && !tab[s]) PAA_FAIL(PAA_ERR_ARG, "paa_proj_set_masking_spread: %s_db is null with n_%s=%d", side, side, n[s]);
+        for (int j = 0; j < n[s]; ++j)
+            if (!(std::isfinite(tab[s][j]) && tab[s][j] > 0.f && (j == 0 || tab[s][j] >= tab[s][j - 1])))
+                PAA_FAIL(PAA_ERR_ARG, "paa_proj_set_masking_spread: %s_db[%d]=%g must be finite, positive and not below %s_db[%d]", side, j,
+                         (double)tab[s][j], side, j > 0 ? j - 1 : 0);
+    }
+    if ((n_post || n_pre) && !h->d_mask2) {
+        const size_t Tmax = 1 + h->max_len / h->hop;
+        PAA_HIP(hipMalloc(&h->d_mask2, sizeof(float) * (size_t)h->max_batch * Tmax * h->F));
+        PAA_HIP(hipMalloc(&h->d_mpmax, sizeof(float) * (size_t)h->max_batch));
+    }
+    h->n_post = n_post; h->n_pre = n_pre;
+    for (int j = 0; j < MASK_LAGS; ++j) {
+        h->post_db[j] = j < n_post ? post_db[j] : 0.f;
+        h->pre_db[j] = j < n_pre ? pre_db[j] : 0.f;
+    }
+    return PAA_OK;
+}
+
 // Masking threshold of the clean clips (B, L) into h->d_mask (passes 1 and 2 of mask_kernels.hip): theta (dB) into d_theta when
-// given, else the magnitude bound A in place in h->d_mask; with min_rows, pass 3 leaves min_b A_b in row 0.
+// given, else the magnitude bound A in place in h->d_mask; with min_rows, pass 3 leaves min_b A_b in row 0.  With temporal masking on,
+// pass 2 writes theta into h->d_mask2 and k_mask_spread writes theta' into d_theta, or the bound A' into h->d_mask.
 static paa_status masking_pass(paa_proj* h, const float* d_clean, int B, int L, float margin, float* d_psd, float* d_theta,
                                float* d_pmax, bool min_rows, hipStream_t st) {
     if (!d_clean || B < 1) PAA_FAIL(PAA_ERR_NEED_CLEAN, "masking projection requires clean_audio");
@@ -666,7 +705,20 @@ static paa_status masking_pass(paa_proj* h, const float* d_clean, int B, int L, 
     ma.out = d_theta ? d_theta : h->d_mask; ma.psd = d_psd; ma.pmax = d_pmax;
     ma.tab = MaskTables{h->d_mtab, h->d_mtab + h->F, h->d_mtab + 2 * h->F, h->d_mwin, h->mask_kA};
     ma.T = T; ma.bound = d_theta ? 0 : 1; ma.margin = margin;
-    PAA_TRY(mask_threshold(ma, B, st));
+    if (h->n_post || h->n_pre) {
+        MaskSpreadArgs sp{};
+        sp.theta = h->d_mask2; sp.out = ma.out; sp.T = T; sp.bound = ma.bound; sp.margin = margin;
+        sp.n_post = h->n_post; sp.n_pre = h->n_pre;
+        std::copy(h->post_db, h->post_db + MASK_LAGS, sp.post);
+        std::copy(h->pre_db, h->pre_db + MASK_LAGS, sp.pre);
+        if (!ma.pmax) ma.pmax = h->d_mpmax;
+        sp.pmax = ma.pmax;
+        ma.out = h->d_mask2; ma.bound = 0;
+        PAA_TRY(mask_threshold(ma, B, st));
+        PAA_TRY(mask_spread(sp, B, st));
+    } else {
+        PAA_TRY(mask_threshold(ma, B, st));
+    }
     if (min_rows && !d_theta) PAA_TRY(mask_min_rows(h->d_mask, B, (int64_t)T * h->F, st));
     return PAA_OK;
 }

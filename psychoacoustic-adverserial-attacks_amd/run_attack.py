@@ -32,6 +32,7 @@ def main(args) -> int:
     chain.check_flags(args)
     modes.check(m, modes.MARGIN)
     mask_alpha = modes.check(m, modes.LENGTHS).alpha
+    modes.check(m, modes.MASK_TIME)
     build.start_process_group(args, world)
     if world > 1 and rank != 0:
         args.silent = True
@@ -56,6 +57,7 @@ def main(args) -> int:
     hist = {k: [] for k in ("train_ctc", "train_wer", "clean_ctc", "clean_wer", "pert_ctc", "pert_wer")}
     extra = {}          # results.json keys of the masking-threshold loss term: present only when masking_loss_alpha > 0
     place_extra = chain.results_extra(args, p.shape[-1])          # and those of placement, room responses and the playback channel
+    place_extra = {**build.masking_time_extra(args), **place_extra}      # and of temporal masking
     extra.update(place_extra)
     goal = scoring_helpers.Objective(args.attack_mode)      # targeted: perturbed WER down; untargeted: perturbed CTC up
     best_epoch, no_improve, best_eval = -1, 0, goal.worst

@@ -21,9 +21,10 @@ def weight_table():
 
 
 class Proj:
-    """Owns one ``paa_proj`` handle (FFT twiddles, window, FM table, max_phon contour, workspace)."""
+    """Owns one ``paa_proj`` handle (FFT twiddles, window, FM table, max_phon contour, workspace).  ``spread``: the (post_db, pre_db)
+    tables of temporal masking (core.masking.temporal_tables), set once here; None or two empty tables leave the mode off."""
 
-    def __init__(self, device, n_fft, hop, win, sr, max_batch, max_len, interp=None):
+    def __init__(self, device, n_fft, hop, win, sr, max_batch, max_len, interp=None, spread=None):
         self.device = torch.device(device)
         self.key = (n_fft, hop, win, sr)
         self.max_batch, self.max_len = max_batch, max_len
@@ -37,6 +38,12 @@ class Proj:
                                                   None, max_batch, max_len))
         self.h = h
         self._thr_key = None
+        self.spread = spread
+        if spread is not None and (len(spread[0]) or len(spread[1])):
+            post, pre = (np.ascontiguousarray(t, dtype=np.float32) for t in spread)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().paa_proj_set_masking_spread(h, len(post), post.ctypes.data_as(C.c_void_p),
+                                                                  len(pre), pre.ctypes.data_as(C.c_void_p)))
 
     def set_spl_thresh(self, spl_thresh):
         """spl_thresh: the (1, F, 1) tensor of build.init_phon_threshold_tensor (uploaded when it changes)."""
@@ -63,20 +70,25 @@ class Proj:
 
 
 def get_proj(args, device, rows: int, length: int, interp=None) -> Proj:
-    """One projection context per (device, frame geometry, weight table).  A custom ``iso.WeightTable`` gets a context of
+    """One projection context per (device, frame geometry, weight table, temporal-masking tables of ``args``).  A context with
+    temporal masking on is never handed to a caller that has it off, or has other tables.  A custom ``iso.WeightTable`` gets a context of
     its own (its identity is part of the key: it is never silently replaced by the default table); a context that has
-    to grow for a larger batch / length keeps its table and its max_phon contour."""
+    to grow for a larger batch / length keeps its tables and its max_phon contour."""
+    from .core.masking import temporal_tables
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("paa_amd runs on the GPU only (device %r); there is no CPU fallback" % (device,))
     table = interp if isinstance(interp, iso.WeightTable) else None
     key = (device.index if device.index is not None else torch.cuda.current_device(),
            int(args.n_fft), int(args.hop_length), int(args.win_length), int(args.sr), id(table) if table is not None else None)
+    spread = temporal_tables(args)
+    if len(spread[0]) or len(spread[1]):          # the mode off keeps the key it always had
+        key += (spread[0].tobytes(), spread[1].tobytes())
     pr = _PROJ.get(key)
     if pr is None or pr.max_batch < rows or pr.max_len < length:
         mb = max(rows, pr.max_batch if pr else 1)
         ml = max(length, pr.max_len if pr else 1)
-        new = Proj(device, key[1], key[2], key[3], key[4], mb, ml, table)
+        new = Proj(device, key[1], key[2], key[3], key[4], mb, ml, table, spread)
         new._table = table                      # keeps the table alive: its id is in the key
         if pr is not None and getattr(pr, "_thr_ref", None) is not None:
             new.set_spl_thresh(pr._thr_ref)

@@ -170,6 +170,18 @@ def masking_loss_suffix(args) -> str:
     return f"_ml{alpha:g}" if alpha > 0 else ""
 
 
+def masking_time_suffix(args) -> str:
+    """Run-directory suffix of temporal masking: "_mt<post>-<pre>" when either time is > 0, else empty."""
+    m = Modes.of(args)
+    return f"_mt{m.post_ms:g}-{m.pre_ms:g}" if m.mask_time_on else ""
+
+
+def masking_time_extra(args) -> dict:
+    """The results keys of temporal masking: present only with the mode on."""
+    m = Modes.of(args)
+    return {"masking_post_ms": float(m.post_ms), "masking_pre_ms": float(m.pre_ms)} if m.mask_time_on else {}
+
+
 def create_logger(args, logs_root=None):
     """build.py:233-286: derive save_dir = <logs>/<mode>/<dataset>/<norm>_<size>_<mode>_<opt>, set up the "asr_attack"
     logger (rotating file + console) and discover a resumable checkpoint: an existing perturbation.pt in save_dir makes
@@ -180,7 +192,7 @@ def create_logger(args, logs_root=None):
     args.attack_size_string = attack_size_string(args)
     root = logs_root or getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}{chain.suffix(args)}_"
+                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}{masking_time_suffix(args)}{chain.suffix(args)}_"
                                  f"{args.attack_mode}_{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)
     logger = logging.getLogger("asr_attack")

@@ -11,6 +11,8 @@ GAIN_DB_MAX = 20.0
 DRIFT_PPM_MAX = 100000.0
 NOISE_SNR_MIN, NOISE_SNR_MAX = -20.0, 100.0
 EOT_DRAWS_MAX = 64
+MASK_LAGS_MAX = 32            # lags a table of paa_proj_set_masking_spread holds
+MASK_DECAY_DB, MASK_RANGE_DB = 60.0, 96.0
 
 
 def _pair(v):
@@ -34,6 +36,32 @@ def _chan_bad(m):
     return None
 
 
+def mask_time_lags(ms, hop, sr):
+    """J of temporal masking: the largest lag j in frames whose decrement j 60 hop 1000 / (ms sr) dB stays under the
+    model's 96 dB range, counted up to MASK_LAGS_MAX + 1 (enough to refuse).  The products are taken in double in this written order."""
+    j = 0
+    while j <= MASK_LAGS_MAX and (j + 1) * MASK_DECAY_DB * hop * 1000.0 < MASK_RANGE_DB * ms * sr:
+        j += 1
+    return j
+
+
+def mask_time_decrement(j, ms, hop, sr):
+    """w[j] in dB, in double."""
+    return j * MASK_DECAY_DB * hop * 1000.0 / (ms * sr)
+
+
+def _mask_time_bad(m):
+    """None, or the first of --masking_post_ms / --masking_pre_ms out of range."""
+    for flag, v in (("masking_post_ms", m.post_ms), ("masking_pre_ms", m.pre_ms)):
+        ok = isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 <= v < float("inf")
+        if ok and (v == 0 or 1 <= mask_time_lags(v, m.hop, m.sr) <= MASK_LAGS_MAX):
+            continue
+        unit = 1000.0 * MASK_DECAY_DB / MASK_RANGE_DB * m.hop / m.sr          # the time whose decrement per frame is the whole range
+        return (f"{flag} must be 0 (off) or lie in ({unit:g}, {unit * (MASK_LAGS_MAX + 1):g}] ms at hop_length {m.hop} and sr {m.sr} "
+                f"(1 to {MASK_LAGS_MAX} frames of decay), got {v}")
+    return None
+
+
 @dataclass(frozen=True)
 class Modes:
     norms: tuple                   # --norm_type, '+'-separated, in the written order
@@ -54,6 +82,10 @@ class Modes:
     eot_draws: int = 0             # --eot_draws G (attack_clips only): draws of the playback chain per clip, 0 = off
     seconds_on: bool = False       # --perturbation_seconds set
     anneal_on: bool = False        # --alpha_search other than "off" (attack_clips only)
+    post_ms: float = 0.0           # --masking_post_ms (temporal masking), 0 = off
+    pre_ms: float = 0.0            # --masking_pre_ms
+    hop: int = 256                 # --hop_length and --sr: the frame period the two times are counted in
+    sr: int = 16000
     search_on: bool = False        # --bound_search other than "off" (attack_clips only)
 
     @classmethod
@@ -69,7 +101,9 @@ class Modes:
                    drift_ppm=_num(get("drift_ppm", 0.0) or 0.0), noise_snr=_pair(get("noise_snr_db", None)),
                    search_on=str(get("bound_search", "off")) != "off", anneal_on=str(get("alpha_search", "off")) != "off", loss_type=str(get("loss_type", "ctc")),
                    kappa=_num(get("margin_kappa", 1.0)), targeted=str(get("attack_mode", "untargeted")) == "targeted",
-                   eot_draws=get("eot_draws", 0) or 0, seconds_on=get("perturbation_seconds", None) is not None)
+                   eot_draws=get("eot_draws", 0) or 0, seconds_on=get("perturbation_seconds", None) is not None,
+                   post_ms=_num(get("masking_post_ms", 0.0) or 0.0), pre_ms=_num(get("masking_pre_ms", 0.0) or 0.0),
+                   hop=int(get("hop_length", 256)), sr=int(get("sr", 16000)))
 
     drift_on = property(lambda m: isinstance(m.drift_ppm, float) and m.drift_ppm > 0)
     noise_on = property(lambda m: m.noise_snr is not None)
@@ -80,6 +114,8 @@ class Modes:
     margin_on = property(lambda m: m.loss_type == "margin")
     eot_on = property(lambda m: isinstance(m.eot_draws, int) and not isinstance(m.eot_draws, bool) and m.eot_draws >= 1)
     link_on = property(lambda m: m.place_on or m.rir_on or m.chan_on)      # at least one link of the playback chain
+    mask_time_on = property(lambda m: any(isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0 for v in (m.post_ms, m.pre_ms)))
+    mask_time_why = property(lambda m: _mask_time_bad(m))
 
 
 SIZED_NORMS = ("l2", "linf", "snr", "tv", "fletcher_munson", "max_phon")      # the norms a bound scale tightens (min_max_freqs has no size)
@@ -252,6 +288,11 @@ RULES = {
     "margin_kappa": Rule("margin_on", lambda m, c: not (isinstance(m.kappa, (int, float)) and not isinstance(m.kappa, bool)
                                                         and 0.0 <= m.kappa < float("inf")), ValueError,
                          "margin_kappa must be finite and >= 0, got {m.kappa}"),
+    # temporal masking of the threshold
+    "mask_time_range": Rule(None, lambda m, c: _mask_time_bad(m) is not None, ValueError, "{m.mask_time_why}"),
+    "mask_time_unused": Rule("mask_time_on", lambda m, c: not m.masking, ValueError,
+                             "--masking_post_ms / --masking_pre_ms spread the masking threshold along time and need a consumer of it: "
+                             "--norm_type masking or --masking_loss_alpha > 0"),
     # per-clip perturbations through the playback chain
     "eot_range": Rule(None, lambda m, c: not (isinstance(m.eot_draws, int) and not isinstance(m.eot_draws, bool)
                                               and 0 <= m.eot_draws <= EOT_DRAWS_MAX), ValueError,
@@ -273,6 +314,7 @@ LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir", "len_chan")
 SEARCH_FLAGS = ("search_range", "search_masking", "search_no_size")       # known from the flags alone
 MARGIN = ("margin_untargeted", "margin_kappa")                            # known from the flags alone
 EOT = ("eot_range", "eot_links", "eot_shift")                              # known from the flags alone
+MASK_TIME = ("mask_time_range", "mask_time_unused")                        # known from the flags alone
 SEARCH = SEARCH_FLAGS + ("search_route",)                                  # ... and once the vocabulary and the references are known
 
 

@@ -63,6 +63,11 @@ def create_arg_parser():
     parser.add_argument('--masking_loss_alpha', type=float, default=0.0,
                         help='masking-threshold loss term (extension): the step optimises direction * CTC - alpha * sum_b l_b; '
                              '0 = off')
+    # temporal masking (extension); the defaults leave every threshold as it is.  Documented example: 200 / 20
+    parser.add_argument('--masking_post_ms', type=float, default=0.0,
+                        help='post-masking: a frame\'s masking threshold lasts on after it, falling by 60 dB over this many ms; 0 = off')
+    parser.add_argument('--masking_pre_ms', type=float, default=0.0,
+                        help='pre-masking: a frame\'s masking threshold reaches back before it, falling by 60 dB over this many ms; 0 = off')
     # sound properties (parser.py:57-63)
     parser.add_argument('--phon_reference_db', type=float, default=65)
     parser.add_argument('--sr', type=int, default=16000)
