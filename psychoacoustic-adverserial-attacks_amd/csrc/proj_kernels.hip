@@ -197,10 +197,9 @@ __global__ __launch_bounds__(FFT_NT) void k_frame(FrameArgs a) {
 }
 
 // Overlap-add + envelope division + trim + _align_to (train.py:27-35): out (rows, out_len).
-// Samples >= hop*(T-1) are zero (right zero-pad).  scal[0] (if non-null) is a uniform scale factor; ROWS: scal[row] is
-// the scale of row `row` (per-row projections, paa_project_rows).
-template <bool ROWS>
-__global__ void k_ola(const float* __restrict__ frames, const float* __restrict__ win, const float* __restrict__ scal,
+// Samples >= hop*(T-1) are zero (right zero-pad).  scal (nullable): row `row` is scaled by scal[row * scal_rs], scal_rs = 0 for
+// one factor over all rows, 1 for a factor per row (per-row projections, paa_project_rows).
+__global__ void k_ola(const float* __restrict__ frames, const float* __restrict__ win, const float* __restrict__ scal, int scal_rs,
                       float* __restrict__ out, int T, int N, int hop, int out_len) {
     const int row = blockIdx.y;
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -221,62 +220,57 @@ __global__ void k_ola(const float* __restrict__ frames, const float* __restrict_
             env += w * w;
         }
         v = sum / env;
-        if (scal) v *= scal[ROWS ? row : 0];
+        if (scal) v *= scal[row * scal_rs];
     }
     out[(size_t)row * out_len + m] = v;
 }
 
-// projections.py:116-133 project_fm_norm: scale = eps / max(norm, 1e-8) if norm > eps else 1
-// ROWS: one workgroup per row, row r sums part[r * n, (r + 1) * n) and writes its scale to scal[r] (no norm slot); rscale
-// (nullable): row r's eps is eps * rscale[r].
-template <bool ROWS>
-__global__ __launch_bounds__(RED_NT) void k_fm_finalize(const double* __restrict__ part, int n, float eps,
-                                                      float* __restrict__ scal, const float* __restrict__ rscale = nullptr) {
+// Statistic groups.  The kernels below take blockIdx.y as the group: a span of the rows projected under one statistic of its own,
+// either all the rows (one group: the universal perturbation) or one row each (paa_project_rows).  Element and partial counts are
+// per group, group g's partials start at g * (partials per group), rscale (nullable) holds one bound scale per group, and group
+// 0 alone writes the diagnostic slots scal[0..2].  One group is the many-group kernel at blockIdx.y = 0: every offset is zero,
+// row_scale(nullptr, .) is 1.0f and x * 1.0f is exact.
+
+// projections.py:116-133 project_fm_norm: scale = eps / max(norm, 1e-8) if norm > eps else 1, eps = eps * rscale[g].
+// One workgroup per group: it sums part[g * n, (g + 1) * n) and keeps the group's scale in gscale[g] (k_ola reads it there).
+// gscale may be scal itself (one group, the spectrum-level entries): no __restrict__ on the two.
+__global__ __launch_bounds__(RED_NT) void k_fm_finalize(const double* __restrict__ part, int n, float eps, float* gscale, float* scal,
+                                                      const float* __restrict__ rscale) {
     __shared__ double red[RED_NT / 64];
-    if (ROWS) {
-        part += (size_t)blockIdx.x * n;
-        eps = eps * row_scale(rscale, blockIdx.x);
-    }
+    const int g = blockIdx.y;
+    part += (size_t)g * n;
+    eps = eps * row_scale(rscale, g);
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += RED_NT) s += part[i];
     s = block_sum<double, RED_NT>(s, red);
     if (threadIdx.x == 0) {
         const float norm = sqrtf((float)s);
         const float scale = (norm <= eps) ? 1.f : eps / fmaxf(norm, 1e-8f);
-        if (ROWS) {
-            scal[blockIdx.x] = scale;
-        } else {
-            scal[0] = scale;
-            scal[1] = norm;
-        }
+        gscale[g] = scale;
+        if (g == 0) { scal[0] = scale; scal[1] = norm; }
     }
 }
 
 // Second launch of a fused spectral projection: dst = src * scale, the scale being the predicated FM factor computed from
-// the per-workgroup partial sums of the first launch (every block re-sums the few hundred partials: no third launch);
-// npart = 0: plain copy (min_max_freqs / max_phon, in-place form only).
-// ROWS: blockIdx.y is the row; n and npart are per row, and each row is scaled by the norm of its own partials; rscale
-// (nullable): row r's eps is eps * rscale[r].
-template <bool ROWS>
+// the per-workgroup partial sums of the first launch (every block re-sums the few hundred partials of its group: no third
+// launch); npart = 0: plain copy (min_max_freqs / max_phon / masking, in-place form only).
 __global__ __launch_bounds__(RED_NT) void k_spec_finish(const float* __restrict__ src, float* __restrict__ dst, int64_t n,
                                                       const double* __restrict__ part, int npart, float eps, float* __restrict__ scal,
-                                                      const float* __restrict__ rscale = nullptr) {
+                                                      const float* __restrict__ rscale) {
     __shared__ double red[RED_NT / 64];
-    if (ROWS) {
-        eps = eps * row_scale(rscale, blockIdx.y);
-        src += (size_t)blockIdx.y * n;
-        dst += (size_t)blockIdx.y * n;
-        part += (size_t)blockIdx.y * npart;
-        if (blockIdx.y != 0) scal = nullptr;
-    }
+    const int g = blockIdx.y;
+    eps = eps * row_scale(rscale, g);
+    src += (size_t)g * n;
+    dst += (size_t)g * n;
     float scale = 1.f;
     if (npart > 0) {
+        part += (size_t)g * npart;
         double s = 0.0;
         for (int i = threadIdx.x; i < npart; i += RED_NT) s += part[i];
         s = block_sum<double, RED_NT>(s, red);
         const float norm = sqrtf((float)s);
         scale = (norm <= eps) ? 1.f : eps / fmaxf(norm, 1e-8f);
-        if (blockIdx.x == 0 && threadIdx.x == 0 && scal) { scal[0] = scale; scal[1] = norm; }
+        if (g == 0 && blockIdx.x == 0 && threadIdx.x == 0) { scal[0] = scale; scal[1] = norm; }
     }
     const int64_t n4 = n >> 2;
     const float4* s4 = reinterpret_cast<const float4*>(src);
@@ -296,19 +290,17 @@ __global__ __launch_bounds__(RED_NT) void k_spec_finish(const float* __restrict_
 // ---- time-domain reductions --------------------------------------------------------------------
 enum RedMode { RED_SQ = 0, RED_TV = 1 };
 
-// Blocks [0, g1) reduce x1 (n1 elements, rows of length L1), blocks [g1, g1+g2) reduce x2.
-// ROWS: blockIdx.y is the row; x1 / x2 point at row blockIdx.y (n1 = L1, n2 = L2) and the row's g1 + g2 partials go to
-// part[blockIdx.y * (g1 + g2) + ...]: each row is reduced exactly as a one-row call reduces it.
-template <int MODE, bool ROWS>
+// Blocks [0, g1) reduce x1 (n1 elements, rows of length L1), blocks [g1, g1+g2) reduce x2; n1 / n2 are per group, group
+// blockIdx.y reads x1 + g n1 and x2 + g n2 and writes its g1 + g2 partials to part[g (g1 + g2) + ...]: each row of a per-row call is
+// reduced exactly as a one-row call reduces it.
+template <int MODE>
 __global__ __launch_bounds__(RED_NT) void k_reduce2(const float* __restrict__ x1, int64_t n1, int L1, int g1,
                                                   const float* __restrict__ x2, int64_t n2, int L2, int g2,
                                                   double* __restrict__ part) {
     __shared__ double red[RED_NT / 64];
-    if (ROWS) {
-        if (x1) x1 += (size_t)blockIdx.y * L1;
-        x2 += (size_t)blockIdx.y * L2;
-        part += (size_t)blockIdx.y * (g1 + g2);
-    }
+    x1 += (size_t)blockIdx.y * n1;
+    x2 += (size_t)blockIdx.y * n2;
+    part += (size_t)blockIdx.y * (g1 + g2);
     const bool first = (int)blockIdx.x < g1;
     const float* x = first ? x1 : x2;
     const int64_t n = first ? n1 : n2;
@@ -342,20 +334,18 @@ struct ApplyArgs {
     const float* ext;   // optional device [sum clean^2, TV(clean)] supplied by the caller (data-parallel runs)
     const float* ext_clips;   // optional device [1]: number of clean clips over ALL ranks (an exact small integer in f32);
     double clip_len;          //   numel_clean = ext_clips[0] * clip_len then replaces the host value above
-    const float* rscale;      // ROWS: optional device (rows) per-row bound scale s (paa_project_rows_scaled): l2 / tv eps * s, snr_db - 20 log10(s)
+    const float* rscale;      // optional device (groups) bound scale s of each group (paa_project_rows_scaled): l2 / tv eps * s, snr_db - 20 log10(s)
 };
 
 // p = src * scale (src == p: in place; otherwise the out-of-place form reads the caller's source directly — no copy in front)
-// ROWS: blockIdx.y is the row; n is the row length and the row's scale comes from its own g1 + g2 partials (k_reduce2 ROWS).
-template <int NORM, bool ROWS>
+// n is the element count of a group; group blockIdx.y's scale comes from its own g1 + g2 partials (k_reduce2).
+template <int NORM>
 __global__ __launch_bounds__(RED_NT) void k_apply_scale(const float* src, float* p, int64_t n, ApplyArgs a) {
     __shared__ double red[RED_NT / 64];
-    if (ROWS) {
-        src += (size_t)blockIdx.y * n;
-        p += (size_t)blockIdx.y * n;
-        a.part += (size_t)blockIdx.y * (a.g1 + a.g2);
-        if (blockIdx.y != 0) a.scal = nullptr;
-    }
+    const int g = blockIdx.y;
+    src += (size_t)g * n;
+    p += (size_t)g * n;
+    a.part += (size_t)g * (a.g1 + a.g2);
     double s1 = 0.0, s2 = 0.0;
     for (int i = threadIdx.x; i < a.g1; i += RED_NT) s1 += a.part[i];
     for (int i = threadIdx.x; i < a.g2; i += RED_NT) s2 += a.part[a.g1 + i];
@@ -364,8 +354,8 @@ __global__ __launch_bounds__(RED_NT) void k_apply_scale(const float* src, float*
     if (a.ext) s1 = (double)a.ext[NORM == PAA_NORM_TV ? 1 : 0];
     const double numel_clean = a.ext_clips ? (double)a.ext_clips[0] * a.clip_len : a.numel_clean;
     float scale = 1.f;
-    // the row's bound scale: x * 1.0f and x - 20 log10f(1.0f) are exact, so s = 1 gives the bits of the unscaled projection
-    const float rs = ROWS ? row_scale(a.rscale, blockIdx.y) : 1.f;
+    // the group's bound scale: x * 1.0f and x - 20 log10f(1.0f) are exact, so s = 1 gives the bits of the unscaled projection
+    const float rs = row_scale(a.rscale, g);
     if (NORM == PAA_NORM_L2) {                     // projections.py:41-46 (s2 = sum p^2)
         const float norm = sqrtf((float)s2);
         const float eps = a.eps * rs;
@@ -375,7 +365,7 @@ __global__ __launch_bounds__(RED_NT) void k_apply_scale(const float* src, float*
         const float np_ = (float)(s2 / a.numel_p);
         const float cur = 10.f * log10f(sp / (np_ + 1e-12f));
         float want = a.snr_db;
-        if (ROWS && a.rscale) want = a.snr_db - 20.f * log10f(rs);
+        if (a.rscale) want = a.snr_db - 20.f * log10f(rs);
         if (!(cur >= want)) {
             const float target = sqrtf(sp / a.snr_linear * (float)numel_clean) * rs;
             const float cn = sqrtf((float)s2);
@@ -386,7 +376,7 @@ __global__ __launch_bounds__(RED_NT) void k_apply_scale(const float* src, float*
         const float tv = (float)s2;
         if (tv > eps) scale = eps / tv;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && a.scal) { a.scal[0] = scale; a.scal[1] = (float)s1; a.scal[2] = (float)s2; }
+    if (g == 0 && blockIdx.x == 0 && threadIdx.x == 0) { a.scal[0] = scale; a.scal[1] = (float)s1; a.scal[2] = (float)s2; }
     if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(p)) & 15) == 0) {
         const int64_t n4 = n >> 2;
         const float4* s4 = reinterpret_cast<const float4*>(src);
@@ -759,273 +749,195 @@ extern "C" paa_status paa_istft(paa_proj* h, const float* d_S, int B, int T, flo
     a.S_in = d_S;
     PAA_TRY(launch_frames<OP_ISTFT>(h, a, B, st));
     const int out_len = h->hop * (T - 1);
-    hipLaunchKernelGGL(k_ola<false>, dim3(cdiv(out_len, 256), B), dim3(256), 0, st, h->d_frames, h->d_win, (const float*)nullptr,
+    hipLaunchKernelGGL(k_ola, dim3(cdiv(out_len, 256), B), dim3(256), 0, st, h->d_frames, h->d_win, (const float*)nullptr, 0,
                        d_out, T, h->n_fft, h->hop, out_len);
     PAA_LAUNCH_CHECK();
     return PAA_OK;
 }
 
-// d_src == nullptr: in place on d_p.  Otherwise out of place: reads d_src, writes d_p (the two must not overlap).
-static paa_status project_impl(paa_proj* h, const paa_params* prm, float* d_p, int rows_p, const float* d_clean, int B, int L,
-                               const float* d_ext, double ext_numel, void* stream, const float* d_src = nullptr,
-                               const float* d_ext_clips = nullptr) {
-    if (!h || !prm || !d_p) PAA_FAIL(PAA_ERR_ARG, "paa_project: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int nt = prm->norm_type;
-    const int64_t n = (int64_t)rows_p * L;
-    if (rows_p < 1 || L < 2) PAA_FAIL(PAA_ERR_SIZE, "paa_project: rows_p=%d L=%d", rows_p, L);
-    if (nt < PAA_NORM_L2 || nt > PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", nt);
-    if (nt == PAA_NORM_MASKING && d_ext) PAA_FAIL(PAA_ERR_BAD_NORM, "masking projection needs the clean clips, not their statistics");
-    const bool spectral = nt == PAA_NORM_FLETCHER_MUNSON || nt == PAA_NORM_MIN_MAX_FREQS || nt == PAA_NORM_MAX_PHON ||
-                          nt == PAA_NORM_MASKING;
-    if (nt == PAA_NORM_MASKING) {      // the bound of every clip, then its minimum over the clips (the universal perturbation hides under all)
-        PAA_TRY(check_rows(h, rows_p, L, "paa_project"));
-        PAA_TRY(masking_pass(h, d_clean, B, L, prm->masking_margin_db, nullptr, nullptr, nullptr, true, st));
+// One projection call, as every entry below describes its own.  The rows are projected in `groups` statistic groups: 1 = one
+// statistic over all the rows (the universal perturbation: perturbation_constraint(p, clean, args), train.py:69-99), rows = every
+// row under its own (per-clip perturbations: row r exactly as perturbation_constraint(src[r][None], clean[r][None], args) projects
+// it — l2 / fletcher_munson from the row's own norm, snr from clean row r's own mean power, tv from TV(clean[r])).
+struct ProjCall {
+    const char* who;           // the entry's name, for messages
+    const float* src;          // (rows, L); src == dst: in place, otherwise the two must not overlap
+    float* dst;
+    int rows, L;
+    int groups;                // 1 or rows
+    const float* clean;        // (B, L) clean clips, nullable; groups == rows: B == rows, clip r belongs to row r
+    int B;
+    const float* ext;          // device [sum clean^2, TV(clean)] in place of the clean clips (paa_project_ext), nullable
+    const float* ext_clips;    // with ext: device [1] clip count over all ranks, nullable (then ext_numel holds clean.numel())
+    double ext_numel;
+    const float* rscale;       // device (groups) bound scale of each group (paa_project_rows_scaled), nullable
+};
+
+static bool overlap(const float* a, const float* b, int64_t n) { return (a < b ? a : b) + n > (a < b ? b : a); }
+
+// The refusals every entry shares.  up_front: the sizes are held against the handle's for every norm (the per-row entries);
+// otherwise only the norms that need the frame workspace check them (check_rows in project_call).
+static paa_status check_call(const paa_proj* h, const paa_params* prm, const ProjCall& c, bool up_front) {
+    if (!h || !prm || !c.src || !c.dst) PAA_FAIL(PAA_ERR_ARG, "%s: null argument", c.who);
+    if (c.rows < 1 || c.L < 2) PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d", c.who, c.rows, c.L);
+    if (up_front && (c.rows > h->max_batch || c.L > h->max_len))
+        PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d exceeds max_batch=%d / max_len=%d", c.who, c.rows, c.L, h->max_batch, h->max_len);
+    if (prm->norm_type < PAA_NORM_L2 || prm->norm_type > PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", prm->norm_type);
+    return PAA_OK;
+}
+
+// Grid of a scaling launch (k_apply_scale, k_spec_finish) over `groups` groups of n elements: one group spreads over up to 1024
+// workgroups of per_wg elements each, several groups take up to 128 workgroups of 1024 elements per group.
+static dim3 scale_grid(int groups, int64_t n, int per_wg) {
+    return groups == 1 ? dim3(std::min(cdiv(n, per_wg), 1024)) : dim3(std::min(cdiv(n, (int64_t)RED_NT * 4), 128), groups);
+}
+
+template <class Args>
+static void set_bin_params(Args& a, const paa_params* prm) {
+    a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
+}
+
+// The projection of a checked call (P0-P7 of DESIGN.md §1).  A group spans rows / groups rows: n elements of the perturbation, nc of
+// the clean clips; its partial sums are laid out and summed as a call on that group alone lays them out and sums them.
+static paa_status project_call(paa_proj* h, const paa_params* prm, const ProjCall& c, hipStream_t st) {
+    const int nt = prm->norm_type, L = c.L, rows = c.rows, groups = c.groups;
+    const bool in_place = c.src == c.dst;
+    const int64_t all = (int64_t)rows * L, n = all / groups;
+    if (nt == PAA_NORM_LINF) {
+        if (c.rscale)
+            hipLaunchKernelGGL(k_clamp_rows, dim3(std::min(cdiv((int64_t)L, 256), 256), rows), dim3(256), 0, st, c.src, c.dst, L,
+                               prm->linf_size, c.rscale);
+        else
+            hipLaunchKernelGGL(k_clamp, dim3(std::min(cdiv(all, 256), 2048)), dim3(256), 0, st, c.src, c.dst, all, -prm->linf_size,
+                               prm->linf_size);
+        PAA_LAUNCH_CHECK();
+        return PAA_OK;
     }
-    if (spectral && fused_geometry(h)) {
+    if (nt == PAA_NORM_L2 || nt == PAA_NORM_SNR || nt == PAA_NORM_TV) {
+        // the reduction and the scaling pass read the source directly
+        if (nt != PAA_NORM_L2 && !c.ext && (!c.clean || c.B < 1)) {
+            if (nt == PAA_NORM_SNR) PAA_FAIL(PAA_ERR_NEED_CLEAN, "SNR projection requires clean_audio ro compare to");
+            PAA_FAIL(PAA_ERR_NEED_CLEAN, "TV projection can benefit from clean_audio for bounds");
+        }
+        const int64_t nc = (nt == PAA_NORM_L2 || c.ext) ? 0 : (int64_t)(c.B / groups) * L;
+        const int g1 = nc ? std::min(cdiv(nc, (int64_t)RED_NT * 16), 2048) : 0;
+        const int g2 = std::min(cdiv(n, (int64_t)RED_NT * 8), 1024);
+        // one group's partials (at most 3072) fit below the frame partials of d_part; several groups' go to the frame workspace, idle for these norms
+        double* part = groups == 1 ? h->d_part : reinterpret_cast<double*>(h->d_frames);
+        if (groups > 1 && (size_t)groups * (g1 + g2) * 2 > h->frames_floats)
+            PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d exceeds the workspace", c.who, rows, L);
+        if (nt == PAA_NORM_TV)
+            hipLaunchKernelGGL(k_reduce2<RED_TV>, dim3(g1 + g2, groups), dim3(RED_NT), 0, st, c.clean, nc, L, g1, c.src, n, L, g2, part);
+        else
+            hipLaunchKernelGGL(k_reduce2<RED_SQ>, dim3(g1 + g2, groups), dim3(RED_NT), 0, st, c.clean, nc, L, g1, c.src, n, L, g2, part);
+        PAA_LAUNCH_CHECK();
+        ApplyArgs a{};
+        a.part = part; a.g1 = g1; a.g2 = g2; a.scal = h->d_scal;
+        a.numel_clean = c.ext ? c.ext_numel : (double)nc; a.numel_p = (double)n; a.ext = c.ext;
+        a.ext_clips = c.ext ? c.ext_clips : nullptr; a.clip_len = (double)L; a.rscale = c.rscale;
+        a.snr_db = prm->snr_db; a.snr_linear = (float)pow(10.0, (double)prm->snr_db / 10.0);
+        a.eps = (nt == PAA_NORM_L2) ? prm->l2_size : prm->tv_epsilon;
+        const dim3 grid = scale_grid(groups, n, 256);
+        if (nt == PAA_NORM_L2) hipLaunchKernelGGL(k_apply_scale<PAA_NORM_L2>, grid, dim3(RED_NT), 0, st, c.src, c.dst, n, a);
+        else if (nt == PAA_NORM_SNR) hipLaunchKernelGGL(k_apply_scale<PAA_NORM_SNR>, grid, dim3(RED_NT), 0, st, c.src, c.dst, n, a);
+        else hipLaunchKernelGGL(k_apply_scale<PAA_NORM_TV>, grid, dim3(RED_NT), 0, st, c.src, c.dst, n, a);
+        PAA_LAUNCH_CHECK();
+        return PAA_OK;
+    }
+    // the spectral norms: fletcher_munson, min_max_freqs, max_phon, masking
+    PAA_TRY(check_rows(h, rows, L, c.who));
+    const bool fm = nt == PAA_NORM_FLETCHER_MUNSON;
+    const int T = 1 + L / h->hop;
+    // masking: every clip's bound; one group hides under all of them (their minimum, left in row 0), a row of its own under its own clip's
+    if (nt == PAA_NORM_MASKING) PAA_TRY(masking_pass(h, c.clean, c.B, L, prm->masking_margin_db, nullptr, nullptr, nullptr, groups == 1, st));
+    if (fused_geometry(h)) {
         // one fused launch STFT -> per-bin op -> iSTFT + overlap-add (spec_kernels.hip), then the scale / copy-back launch
-        PAA_TRY(check_rows(h, rows_p, L, "paa_project"));
-        const int T = 1 + L / h->hop;
         SpecArgs a = spec_args(h, L, T, L);
-        a.mask = h->d_mask; a.mask_rs = 0;
-        a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
-        a.x = d_src ? d_src : d_p;
-        a.out = d_src ? d_p : h->d_frames;                     // in place: through the workspace (neighbouring workgroups re-read the halo)
+        a.mask = h->d_mask; a.mask_rs = groups == 1 ? 0 : (int64_t)T * h->F;
+        set_bin_params(a, prm);
+        a.x = c.src; a.rscale = c.rscale;
+        a.out = in_place ? h->d_frames : c.dst;                // in place: through the workspace (neighbouring workgroups re-read the halo)
         int npart = 0;
-        PAA_TRY(spec_project(a, spec_op_of(nt), rows_p, &npart, st));
-        const bool fm = nt == PAA_NORM_FLETCHER_MUNSON;
-        if (fm || !d_src) {
-            hipLaunchKernelGGL(k_spec_finish<false>, dim3(std::min(cdiv(n, (int64_t)RED_NT * 4), 1024)), dim3(RED_NT), 0, st,
-                               (const float*)a.out, d_p, n, (const double*)a.part, fm ? npart : 0, prm->fm_epsilon, h->d_scal);
+        PAA_TRY(spec_project(a, spec_op_of(nt), rows, &npart, st));
+        if (fm || in_place) {
+            const int fg = fm ? groups : 1;                    // a plain copy back has no statistic: one span over all the rows
+            const int64_t fn = all / fg;
+            hipLaunchKernelGGL(k_spec_finish, scale_grid(fg, fn, RED_NT * 4), dim3(RED_NT), 0, st, (const float*)a.out, c.dst, fn,
+                               (const double*)a.part, fm ? npart / fg : 0, prm->fm_epsilon, h->d_scal, c.rscale);
             PAA_LAUNCH_CHECK();
         }
         return PAA_OK;
     }
-    const bool scale_type = nt == PAA_NORM_L2 || nt == PAA_NORM_SNR || nt == PAA_NORM_TV || nt == PAA_NORM_LINF;
-    if (d_src && !scale_type) {          // the generic frame kernels work in place: copy first
-        PAA_TRY(check_rows(h, rows_p, L, "paa_project"));      // a refused size must leave the destination untouched
-        PAA_HIP(hipMemcpyAsync(d_p, d_src, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+    // the generic frame kernels work in place: copy first.  FM keeps the groups' scales as floats at the front of d_part, below the
+    // frame partials
+    if (fm && groups > 2 * MAX_PART) PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d exceeds %d", c.who, rows, 2 * MAX_PART);
+    if (!in_place) PAA_HIP(hipMemcpyAsync(c.dst, c.src, sizeof(float) * all, hipMemcpyDeviceToDevice, st));
+    FrameArgs a = frame_args(h, L, T);
+    a.x = c.dst; a.rscale = c.rscale;
+    set_bin_params(a, prm);
+    float* gscale = nullptr;
+    if (nt == PAA_NORM_MIN_MAX_FREQS) PAA_TRY(launch_frames<OP_MINMAX>(h, a, rows, st));
+    else if (nt == PAA_NORM_MAX_PHON) PAA_TRY(launch_frames<OP_PHON>(h, a, rows, st));
+    else {
+        PAA_TRY(launch_frames<OP_FM>(h, a, rows, st));
+        gscale = reinterpret_cast<float*>(h->d_part);
+        hipLaunchKernelGGL(k_fm_finalize, dim3(1, groups), dim3(RED_NT), 0, st, (const double*)a.part, rows / groups * T,
+                           prm->fm_epsilon, gscale, h->d_scal, c.rscale);
+        PAA_LAUNCH_CHECK();
     }
-    const float* d_in = d_src ? d_src : d_p;      // scale-type norms and linf: the reduction and the scaling pass read the source directly
-    switch (nt) {
-        case PAA_NORM_FLETCHER_MUNSON:
-        case PAA_NORM_MIN_MAX_FREQS:
-        case PAA_NORM_MAX_PHON: {
-            PAA_TRY(check_rows(h, rows_p, L, "paa_project"));
-            const int T = 1 + L / h->hop;
-            FrameArgs a = frame_args(h, L, T);
-            a.x = d_p;
-            a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
-            const float* scal = nullptr;
-            if (nt == PAA_NORM_MIN_MAX_FREQS) PAA_TRY(launch_frames<OP_MINMAX>(h, a, rows_p, st));
-            else if (nt == PAA_NORM_MAX_PHON) PAA_TRY(launch_frames<OP_PHON>(h, a, rows_p, st));
-            else {
-                PAA_TRY(launch_frames<OP_FM>(h, a, rows_p, st));
-                hipLaunchKernelGGL(k_fm_finalize<false>, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, rows_p * T,
-                                   prm->fm_epsilon, h->d_scal);
-                PAA_LAUNCH_CHECK();
-                scal = h->d_scal;
-            }
-            hipLaunchKernelGGL(k_ola<false>, dim3(cdiv(L, 256), rows_p), dim3(256), 0, st, h->d_frames, h->d_win, scal, d_p, T,
-                               h->n_fft, h->hop, L);
-            PAA_LAUNCH_CHECK();
-            return PAA_OK;
-        }
-        case PAA_NORM_LINF: {
-            hipLaunchKernelGGL(k_clamp, dim3(std::min(cdiv(n, 256), 2048)), dim3(256), 0, st, d_in, d_p, n, -prm->linf_size,
-                               prm->linf_size);
-            PAA_LAUNCH_CHECK();
-            return PAA_OK;
-        }
-        case PAA_NORM_L2:
-        case PAA_NORM_SNR:
-        case PAA_NORM_TV: {
-            if (nt != PAA_NORM_L2 && !d_ext && (!d_clean || B < 1)) {
-                if (nt == PAA_NORM_SNR) PAA_FAIL(PAA_ERR_NEED_CLEAN, "SNR projection requires clean_audio ro compare to");
-                PAA_FAIL(PAA_ERR_NEED_CLEAN, "TV projection can benefit from clean_audio for bounds");
-            }
-            const int64_t nc = (nt == PAA_NORM_L2 || d_ext) ? 0 : (int64_t)B * L;
-            const int g1 = nc ? std::min(cdiv(nc, (int64_t)RED_NT * 16), 2048) : 0;
-            const int g2 = std::min(cdiv(n, (int64_t)RED_NT * 8), 1024);
-            if (nt == PAA_NORM_TV)
-                hipLaunchKernelGGL((k_reduce2<RED_TV, false>), dim3(g1 + g2), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_in,
-                                   n, L, g2, h->d_part);
-            else
-                hipLaunchKernelGGL((k_reduce2<RED_SQ, false>), dim3(g1 + g2), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_in,
-                                   n, L, g2, h->d_part);
-            PAA_LAUNCH_CHECK();
-            ApplyArgs a{};
-            a.part = h->d_part; a.g1 = g1; a.g2 = g2; a.scal = h->d_scal;
-            a.numel_clean = d_ext ? ext_numel : (double)nc; a.numel_p = (double)n; a.ext = d_ext;
-            a.ext_clips = d_ext ? d_ext_clips : nullptr; a.clip_len = (double)L;
-            a.snr_db = prm->snr_db; a.snr_linear = (float)pow(10.0, (double)prm->snr_db / 10.0);
-            a.eps = (nt == PAA_NORM_L2) ? prm->l2_size : prm->tv_epsilon;
-            const int ga = std::min(cdiv(n, 256), 1024);
-            if (nt == PAA_NORM_L2) hipLaunchKernelGGL((k_apply_scale<PAA_NORM_L2, false>), dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
-            else if (nt == PAA_NORM_SNR) hipLaunchKernelGGL((k_apply_scale<PAA_NORM_SNR, false>), dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
-            else hipLaunchKernelGGL((k_apply_scale<PAA_NORM_TV, false>), dim3(ga), dim3(RED_NT), 0, st, d_in, d_p, n, a);
-            PAA_LAUNCH_CHECK();
-            return PAA_OK;
-        }
-        default:
-            PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", nt);
-    }
+    hipLaunchKernelGGL(k_ola, dim3(cdiv(L, 256), rows), dim3(256), 0, st, h->d_frames, h->d_win, (const float*)gscale,
+                       groups == 1 ? 0 : 1, c.dst, T, h->n_fft, h->hop, L);
+    PAA_LAUNCH_CHECK();
+    return PAA_OK;
 }
 
 extern "C" paa_status paa_project(paa_proj* h, const paa_params* prm, float* d_p, int rows_p, const float* d_clean,
                                   int B, int L, void* stream) {
-    return project_impl(h, prm, d_p, rows_p, d_clean, B, L, nullptr, 0.0, stream);
+    const ProjCall c{"paa_project", d_p, d_p, rows_p, L, 1, d_clean, B};
+    PAA_TRY(check_call(h, prm, c, false));
+    return project_call(h, prm, c, (hipStream_t)stream);
 }
 
 extern "C" paa_status paa_project_to(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows_p,
                                      const float* d_clean, int B, int L, void* stream) {
+    const ProjCall c{"paa_project_to", d_src, d_dst, rows_p, L, 1, d_clean, B};
     if (!d_src || !d_dst) PAA_FAIL(PAA_ERR_ARG, "paa_project_to: null argument");
-    const float* lo = d_src < d_dst ? d_src : d_dst;
-    const float* hi = d_src < d_dst ? d_dst : d_src;
-    if (rows_p > 0 && L > 0 && lo + (int64_t)rows_p * L > hi) PAA_FAIL(PAA_ERR_ARG, "paa_project_to: source and destination overlap");
-    return project_impl(h, prm, d_dst, rows_p, d_clean, B, L, nullptr, 0.0, stream, d_src);
+    if (rows_p > 0 && L > 0 && overlap(d_src, d_dst, (int64_t)rows_p * L)) PAA_FAIL(PAA_ERR_ARG, "paa_project_to: source and destination overlap");
+    PAA_TRY(check_call(h, prm, c, false));
+    return project_call(h, prm, c, (hipStream_t)stream);
 }
 
-// Per-row form (per-clip perturbations): row r of d_src (rows, L) is projected exactly as the one-row call
-// perturbation_constraint(src[r][None], clean[r][None], args) projects it (train.py:69-99) — l2 / fletcher_munson from the
-// row's own norm, snr from clean row r's own mean power (clean.numel() = L), tv from TV(clean[r]).  The launch sequence
-// is the one of a one-row projection with a row grid dimension; no launch per row.
-// d_scale (nullable, device (rows)): the per-row bound scale of paa_project_rows_scaled; null launches what it always launched.
-static paa_status project_rows_impl(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
-                                    const float* d_clean, int L, hipStream_t st, const float* d_scale = nullptr) {
-    const int nt = prm->norm_type;
-    const int64_t n = (int64_t)rows * L;
-    const bool in_place = d_src == d_dst;
-    const char* who = d_scale ? "paa_project_rows_scaled" : "paa_project_rows";
-    switch (nt) {
-        case PAA_NORM_LINF:
-            if (d_scale) {
-                hipLaunchKernelGGL(k_clamp_rows, dim3(std::min(cdiv((int64_t)L, 256), 256), rows), dim3(256), 0, st, d_src, d_dst, L,
-                                   prm->linf_size, d_scale);
-                PAA_LAUNCH_CHECK();
-                return PAA_OK;
-            }
-            hipLaunchKernelGGL(k_clamp, dim3(std::min(cdiv(n, 256), 2048)), dim3(256), 0, st, d_src, d_dst, n, -prm->linf_size,
-                               prm->linf_size);
-            PAA_LAUNCH_CHECK();
-            return PAA_OK;
-        case PAA_NORM_L2:
-        case PAA_NORM_SNR:
-        case PAA_NORM_TV: {
-            if (nt != PAA_NORM_L2 && !d_clean) {
-                if (nt == PAA_NORM_SNR) PAA_FAIL(PAA_ERR_NEED_CLEAN, "SNR projection requires clean_audio ro compare to");
-                PAA_FAIL(PAA_ERR_NEED_CLEAN, "TV projection can benefit from clean_audio for bounds");
-            }
-            // the reduction geometry of a one-row call on each row: the same partials, summed in the same order
-            const int64_t nc = nt == PAA_NORM_L2 ? 0 : L;
-            const int g1 = nc ? std::min(cdiv(nc, (int64_t)RED_NT * 16), 2048) : 0;
-            const int g2 = std::min(cdiv((int64_t)L, (int64_t)RED_NT * 8), 1024);
-            if ((size_t)rows * (g1 + g2) * 2 > h->frames_floats)
-                PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d exceeds the workspace", who, rows, L);
-            double* part = reinterpret_cast<double*>(h->d_frames);     // the frame workspace is idle for these norms
-            if (nt == PAA_NORM_TV)
-                hipLaunchKernelGGL((k_reduce2<RED_TV, true>), dim3(g1 + g2, rows), dim3(RED_NT), 0, st, d_clean, nc, L, g1, d_src,
-                                   (int64_t)L, L, g2, part);
-            else
-                hipLaunchKernelGGL((k_reduce2<RED_SQ, true>), dim3(g1 + g2, rows), dim3(RED_NT), 0, st, nc ? d_clean : nullptr, nc, L,
-                                   g1, d_src, (int64_t)L, L, g2, part);
-            PAA_LAUNCH_CHECK();
-            ApplyArgs a{};
-            a.part = part; a.g1 = g1; a.g2 = g2; a.scal = h->d_scal;
-            a.numel_clean = (double)nc; a.numel_p = (double)L; a.clip_len = (double)L; a.rscale = d_scale;
-            a.snr_db = prm->snr_db; a.snr_linear = (float)pow(10.0, (double)prm->snr_db / 10.0);
-            a.eps = (nt == PAA_NORM_L2) ? prm->l2_size : prm->tv_epsilon;
-            const dim3 grid(std::min(cdiv((int64_t)L, (int64_t)RED_NT * 4), 128), rows);
-            if (nt == PAA_NORM_L2) hipLaunchKernelGGL((k_apply_scale<PAA_NORM_L2, true>), grid, dim3(RED_NT), 0, st, d_src, d_dst, (int64_t)L, a);
-            else if (nt == PAA_NORM_SNR) hipLaunchKernelGGL((k_apply_scale<PAA_NORM_SNR, true>), grid, dim3(RED_NT), 0, st, d_src, d_dst, (int64_t)L, a);
-            else hipLaunchKernelGGL((k_apply_scale<PAA_NORM_TV, true>), grid, dim3(RED_NT), 0, st, d_src, d_dst, (int64_t)L, a);
-            PAA_LAUNCH_CHECK();
-            return PAA_OK;
-        }
-        case PAA_NORM_FLETCHER_MUNSON:
-        case PAA_NORM_MIN_MAX_FREQS:
-        case PAA_NORM_MAX_PHON:
-        case PAA_NORM_MASKING: {
-            PAA_TRY(check_rows(h, rows, L, who));
-            const bool fm = nt == PAA_NORM_FLETCHER_MUNSON;
-            const int T = 1 + L / h->hop;
-            if (nt == PAA_NORM_MASKING)        // row r under its own clip's bound
-                PAA_TRY(masking_pass(h, d_clean, rows, L, prm->masking_margin_db, nullptr, nullptr, nullptr, false, st));
-            if (fused_geometry(h)) {
-                SpecArgs a = spec_args(h, L, T, L);
-                a.mask = h->d_mask; a.mask_rs = (int64_t)T * h->F;
-                a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
-                a.x = d_src; a.rscale = d_scale;
-                a.out = in_place ? h->d_frames : d_dst;
-                int npart = 0;
-                PAA_TRY(spec_project(a, spec_op_of(nt), rows, &npart, st));
-                if (fm) {                                      // each row re-sums only its own partials
-                    hipLaunchKernelGGL(k_spec_finish<true>, dim3(std::min(cdiv((int64_t)L, (int64_t)RED_NT * 4), 128), rows),
-                                       dim3(RED_NT), 0, st, (const float*)a.out, d_dst, (int64_t)L, (const double*)a.part,
-                                       npart / rows, prm->fm_epsilon, h->d_scal, d_scale);
-                    PAA_LAUNCH_CHECK();
-                } else if (in_place) {
-                    hipLaunchKernelGGL(k_spec_finish<false>, dim3(std::min(cdiv(n, (int64_t)RED_NT * 4), 1024)), dim3(RED_NT), 0, st,
-                                       (const float*)a.out, d_dst, n, (const double*)nullptr, 0, prm->fm_epsilon, h->d_scal);
-                    PAA_LAUNCH_CHECK();
-                }
-                return PAA_OK;
-            }
-            if (!in_place) PAA_HIP(hipMemcpyAsync(d_dst, d_src, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
-            if (fm && rows > 2 * MAX_PART) PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d exceeds %d", who, rows, 2 * MAX_PART);
-            FrameArgs a = frame_args(h, L, T);
-            a.x = d_dst; a.rscale = d_scale;
-            a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
-            float* scal = nullptr;
-            if (nt == PAA_NORM_MIN_MAX_FREQS) PAA_TRY(launch_frames<OP_MINMAX>(h, a, rows, st));
-            else if (nt == PAA_NORM_MAX_PHON) PAA_TRY(launch_frames<OP_PHON>(h, a, rows, st));
-            else {
-                PAA_TRY(launch_frames<OP_FM>(h, a, rows, st));
-                scal = reinterpret_cast<float*>(h->d_part);           // rows scales, below the frame partials
-                hipLaunchKernelGGL(k_fm_finalize<true>, dim3(rows), dim3(RED_NT), 0, st, (const double*)a.part, T, prm->fm_epsilon,
-                                   scal, d_scale);
-                PAA_LAUNCH_CHECK();
-            }
-            hipLaunchKernelGGL(k_ola<true>, dim3(cdiv(L, 256), rows), dim3(256), 0, st, h->d_frames, h->d_win, (const float*)scal,
-                               d_dst, T, h->n_fft, h->hop, L);
-            PAA_LAUNCH_CHECK();
-            return PAA_OK;
-        }
-        default:
-            PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", nt);
-    }
+// Statistics of the clean clips from the device in place of the clips themselves (data-parallel runs): l2 / snr / tv
+extern "C" paa_status paa_project_ext(paa_proj* h, const paa_params* prm, float* d_p, int rows_p, const float* d_clean_stats,
+                                      const float* d_clip_count, double clean_numel, int L, void* stream) {
+    if (prm && prm->norm_type == PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "paa_project_ext: the masking norm needs the clean clips (paa_project)");
+    if (!d_clean_stats) PAA_FAIL(PAA_ERR_NEED_CLEAN, "paa_project_ext: clean statistics are required");
+    if (!d_clip_count && !(clean_numel > 0.0)) PAA_FAIL(PAA_ERR_ARG, "paa_project_ext: neither a device clip count nor a positive clean_numel");
+    const ProjCall c{"paa_project_ext", d_p, d_p, rows_p, L, 1, nullptr, 0, d_clean_stats, d_clip_count, clean_numel};
+    PAA_TRY(check_call(h, prm, c, false));
+    return project_call(h, prm, c, (hipStream_t)stream);
 }
 
-static paa_status project_rows_entry(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
-                                     const float* d_clean, int L, const float* d_scale, void* stream, const char* who) {
-    if (!h || !prm || !d_src || !d_dst) PAA_FAIL(PAA_ERR_ARG, "%s: null argument", who);
-    if (rows < 1 || L < 2) PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d", who, rows, L);
-    if (rows > h->max_batch || L > h->max_len)
-        PAA_FAIL(PAA_ERR_SIZE, "%s: rows=%d L=%d exceeds max_batch=%d / max_len=%d", who, rows, L, h->max_batch, h->max_len);
-    if (prm->norm_type < PAA_NORM_L2 || prm->norm_type > PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "Unknown norm_type: %d", prm->norm_type);
-    if (d_src != d_dst) {
-        const float* lo = d_src < d_dst ? d_src : d_dst;
-        const float* hi = d_src < d_dst ? d_dst : d_src;
-        if (lo + (int64_t)rows * L > hi) PAA_FAIL(PAA_ERR_ARG, "%s: source and destination overlap", who);
-    }
+// Per-row form: every row is a group, clean clip r belongs to row r; no launch per row.  d_scale (nullable, device (rows)): the
+// per-row bound scale of paa_project_rows_scaled; null is paa_project_rows.
+static paa_status project_rows(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows, const float* d_clean,
+                               int L, const float* d_scale, void* stream, const char* who) {
+    const ProjCall c{who, d_src, d_dst, rows, L, rows, d_clean, rows, nullptr, nullptr, 0.0, d_scale};
+    PAA_TRY(check_call(h, prm, c, true));
+    if (d_src != d_dst && overlap(d_src, d_dst, (int64_t)rows * L)) PAA_FAIL(PAA_ERR_ARG, "%s: source and destination overlap", who);
     if (d_scale && prm->norm_type == PAA_NORM_MASKING)
-        PAA_FAIL(PAA_ERR_BAD_NORM, "paa_project_rows_scaled: the masking norm takes no bound scale (norm_type %d)", prm->norm_type);
-    if (rows == 1 && !d_scale) {  // one row: the universal projection of that row, the same launches
-        if (d_src == d_dst) return project_impl(h, prm, d_dst, 1, d_clean, d_clean ? 1 : 0, L, nullptr, 0.0, stream);
-        return project_impl(h, prm, d_dst, 1, d_clean, d_clean ? 1 : 0, L, nullptr, 0.0, stream, d_src);
-    }
-    // with a scale one row takes the row form too: its reductions are those of the one-row call, partial for partial
-    return project_rows_impl(h, prm, d_src, d_dst, rows, d_clean, L, (hipStream_t)stream, d_scale);
+        PAA_FAIL(PAA_ERR_BAD_NORM, "%s: the masking norm takes no bound scale (norm_type %d)", who, prm->norm_type);
+    return project_call(h, prm, c, (hipStream_t)stream);
 }
 
 extern "C" paa_status paa_project_rows(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
                                        const float* d_clean, int L, void* stream) {
-    return project_rows_entry(h, prm, d_src, d_dst, rows, d_clean, L, nullptr, stream, "paa_project_rows");
+    return project_rows(h, prm, d_src, d_dst, rows, d_clean, L, nullptr, stream, "paa_project_rows");
 }
 
 extern "C" paa_status paa_project_rows_scaled(paa_proj* h, const paa_params* prm, const float* d_src, float* d_dst, int rows,
                                               const float* d_clean, int L, const float* d_scale, void* stream) {
-    return project_rows_entry(h, prm, d_src, d_dst, rows, d_clean, L, d_scale, stream, "paa_project_rows_scaled");
+    return project_rows(h, prm, d_src, d_dst, rows, d_clean, L, d_scale, stream, "paa_project_rows_scaled");
 }
 
 // core/projections.py:68-159 called directly on a spectrum (the reference's project_min_max_freqs / project_fm_norm /
@@ -1042,7 +954,7 @@ extern "C" paa_status paa_spectrum_project(paa_proj* h, const paa_params* prm, c
     hipStream_t st = (hipStream_t)stream;
     SpecArgs a = spec_args(h, 0, T, 0);
     a.part = h->d_part;
-    a.min_f = prm->min_freq_attack; a.max_f = prm->max_freq_attack; a.phon_ref = prm->phon_reference_db;
+    set_bin_params(a, prm);
     a.S_in = d_S_in;
     if (op != SOP_FM) {
         a.S_out = d_S_out;
@@ -1051,7 +963,8 @@ extern "C" paa_status paa_spectrum_project(paa_proj* h, const paa_params* prm, c
     int npart = 0;
     a.S_out = nullptr;                                       // pass 1: weighted power only
     PAA_TRY(spec_apply(a, SOP_FM, B, nullptr, &npart, st));
-    hipLaunchKernelGGL(k_fm_finalize<false>, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, npart, prm->fm_epsilon, h->d_scal);
+    hipLaunchKernelGGL(k_fm_finalize, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, npart, prm->fm_epsilon, h->d_scal, h->d_scal,
+                       (const float*)nullptr);
     PAA_LAUNCH_CHECK();
     a.S_out = d_S_out; a.part = nullptr;                     // pass 2: S * predicated scale
     return spec_apply(a, SOP_NONE, B, h->d_scal, nullptr, st);
@@ -1120,18 +1033,11 @@ extern "C" paa_status paa_fm_weighted_norm(paa_proj* h, const float* d_S, int B,
     a.S_in = d_S; a.S_out = nullptr;
     int npart = 0;
     PAA_TRY(spec_apply(a, SOP_FM, B, nullptr, &npart, st));
-    hipLaunchKernelGGL(k_fm_finalize<false>, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, npart, 0.f, h->d_scal);
+    hipLaunchKernelGGL(k_fm_finalize, dim3(1), dim3(RED_NT), 0, st, (const double*)a.part, npart, 0.f, h->d_scal, h->d_scal,
+                       (const float*)nullptr);
     PAA_LAUNCH_CHECK();
     PAA_HIP(hipMemcpyAsync(d_out, h->d_scal + 1, sizeof(float), hipMemcpyDeviceToDevice, st));
     return PAA_OK;
-}
-
-extern "C" paa_status paa_project_ext(paa_proj* h, const paa_params* prm, float* d_p, int rows_p, const float* d_clean_stats,
-                                      const float* d_clip_count, double clean_numel, int L, void* stream) {
-    if (prm && prm->norm_type == PAA_NORM_MASKING) PAA_FAIL(PAA_ERR_BAD_NORM, "paa_project_ext: the masking norm needs the clean clips (paa_project)");
-    if (!d_clean_stats) PAA_FAIL(PAA_ERR_NEED_CLEAN, "paa_project_ext: clean statistics are required");
-    if (!d_clip_count && !(clean_numel > 0.0)) PAA_FAIL(PAA_ERR_ARG, "paa_project_ext: neither a device clip count nor a positive clean_numel");
-    return project_impl(h, prm, d_p, rows_p, nullptr, 0, L, d_clean_stats, clean_numel, stream, nullptr, d_clip_count);
 }
 
 namespace paa {
@@ -1153,10 +1059,10 @@ extern "C" paa_status paa_batch_stats(paa_proj* h, const float* d_clean, int B, 
     hipStream_t st = (hipStream_t)stream;
     const int64_t nc = (int64_t)B * L;
     const int g = std::min(cdiv(nc, (int64_t)RED_NT * 16), 2048);
-    hipLaunchKernelGGL((k_reduce2<RED_SQ, false>), dim3(g), dim3(RED_NT), 0, st, d_clean, nc, L, g, (const float*)nullptr, (int64_t)0, L, 0,
+    hipLaunchKernelGGL(k_reduce2<RED_SQ>, dim3(g), dim3(RED_NT), 0, st, d_clean, nc, L, g, (const float*)nullptr, (int64_t)0, L, 0,
                        h->d_part);
     PAA_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_reduce2<RED_TV, false>), dim3(g), dim3(RED_NT), 0, st, d_clean, nc, L, g, (const float*)nullptr, (int64_t)0, L, 0,
+    hipLaunchKernelGGL(k_reduce2<RED_TV>, dim3(g), dim3(RED_NT), 0, st, d_clean, nc, L, g, (const float*)nullptr, (int64_t)0, L, 0,
                        h->d_part + g);
     PAA_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(RED_NT), 0, st, (const double*)h->d_part, g, g, d_out2, d_clip_count, (float)B);

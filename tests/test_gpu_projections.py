@@ -1,12 +1,16 @@
 """-m gpu: the HIP projection path against (a) the goldens produced by the reference itself and
 (b) the oracle at BASELINE sizes, plus size-independent properties (idempotence, STFT round trip)."""
+import functools
+import hashlib
+import json
+import os
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from gpu_util import rel_err
+from gpu_util import PROJ_ARGS, SCALES, branch, rel_err, rows_input, scaled_args
 from oracle import projections as OP
 from oracle.gen_cases import AMPS, LENGTHS, NORM_CASES, case_name, cli_to_args
 from paa_amd import synth
@@ -255,3 +259,108 @@ def test_out_of_place_equals_in_place_scale_norms():
                 assert torch.equal(a, b), (norm, rows, L)
                 assert torch.equal(src, x[:rows]), "the source must stay untouched"
                 assert float((a - src).abs().max()) > 0, (norm, rows, "projection did nothing: pick a smaller bound")
+
+
+# ---- the bits of the parent ---------------------------------------------------------------------------------------------------------
+PIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "proj_parent.json")
+PIN_NORMS = ("l2", "linf", "snr", "tv", "fletcher_munson", "max_phon", "min_max_freqs", "masking")
+PIN_SPECTRAL = ("fletcher_munson", "max_phon", "min_max_freqs")
+PIN_GEOMETRIES = {"1024": [], "512": ["--n_fft", "512", "--hop_length", "128", "--win_length", "512"]}
+PIN_LOW = 2                  # the amplitude-0.01 row of rows_input(3, L)
+# entry -> its shapes: "all" / "low" rows of the perturbation under ONE statistic (the clean clips are all three either way), or the
+# row count of a per-row call; *_to: out of place
+PIN_ENTRIES = {"project": ("all", "low"), "project_to": ("all", "low"), "ext": ("all", "low"),
+               "rows": (1, 3), "rows_to": (1, 3), "scaled": (1, 3), "scaled_to": (1, 3)}
+
+
+def pin_cases():
+    """name -> (norm, L, geometry, entry, shape): every fact the projection driver decides, at the smallest sizes that still give
+    several partial blocks per row and per clean batch.  L = 5001 is no multiple of four: rows 1 and 2 of a per-row call start off a
+    16-byte boundary.  n_fft 512 (the generic frame kernels) for the spectral norms at L = 5001 only; masking has the default
+    geometry only and takes neither statistics nor a bound scale."""
+    cases = {}
+    for L in (6144, 5001):
+        for geo in PIN_GEOMETRIES:
+            for norm in PIN_NORMS:
+                if geo != "1024" and (L != 5001 or norm not in PIN_SPECTRAL):
+                    continue
+                for entry, shapes in PIN_ENTRIES.items():
+                    if entry == "ext" and (norm not in ("l2", "snr", "tv") or geo != "1024"):
+                        continue
+                    if norm == "masking" and entry in ("ext", "scaled", "scaled_to"):
+                        continue
+                    for shape in shapes:
+                        cases[f"{norm}|L{L}|n_fft{geo}|{entry}|{shape}"] = (norm, L, geo, entry, shape)
+    return cases
+
+
+@functools.lru_cache(maxsize=None)
+def _pin_input(L):
+    return rows_input(3, L)
+
+
+def pin_args(norm, geo):
+    return _args(norm, PROJ_ARGS + PIN_GEOMETRIES[geo])
+
+
+def pin_operands(case):
+    """(source rows, clean clips, per-row scales or None) of a case, as numpy arrays"""
+    norm, L, geo, entry, shape = case
+    src, clean = _pin_input(L)
+    if shape == "all":
+        return src, clean, None
+    if shape == "low":
+        return src[PIN_LOW:PIN_LOW + 1], clean, None
+    return src[:shape], clean[:shape], SCALES[:shape].copy() if entry.startswith("scaled") else None
+
+
+def pin_branches(case):
+    """[(rescaled?, distance from the branch)] of the oracle, one per statistic of the case (gpu_util.branch); needs no device"""
+    norm, L, geo, entry, shape = case
+    args = pin_args(norm, geo)
+    src, clean, scale = (None if a is None else torch.from_numpy(a) for a in pin_operands(case))
+    if shape in ("all", "low"):
+        return [branch(norm, src, clean, args)]
+    return [branch(norm, src[r:r + 1], clean[r:r + 1], scaled_args(args, norm, 1.0 if scale is None else scale[r]))
+            for r in range(shape)]
+
+
+def pin_sha256(case):
+    """SHA-256 of the bytes the entry of ``case`` leaves in its destination"""
+    from paa_amd import _lib, runtime
+    lib, st = _lib.lib(), _lib.stream_ptr()
+    norm, L, geo, entry, shape = case
+    args = pin_args(norm, geo)
+    src, clean, scale = (None if a is None else torch.from_numpy(a).cuda() for a in pin_operands(case))
+    rows, B = src.shape[0], clean.shape[0]
+    pr = runtime.get_proj(args, src.device, 3, L)
+    pr.set_spl_thresh(OP.spl_thresh_tensor(args).cuda())
+    prm = runtime.params_of(args)
+    in_place = not entry.endswith("_to")
+    dst = src.clone() if in_place else torch.full_like(src, float("nan"))
+    a = dst if in_place else src
+    if entry == "project":
+        _lib.check(lib.paa_project(pr.h, prm, _lib.ptr(dst), rows, _lib.ptr(clean), B, L, st))
+    elif entry == "project_to":
+        _lib.check(lib.paa_project_to(pr.h, prm, _lib.ptr(src), _lib.ptr(dst), rows, _lib.ptr(clean), B, L, st))
+    elif entry == "ext":
+        stats, count = torch.zeros(2, device="cuda"), torch.zeros(1, device="cuda")
+        _lib.check(lib.paa_batch_stats(pr.h, _lib.ptr(clean), B, L, _lib.ptr(stats), _lib.ptr(count), st))
+        _lib.check(lib.paa_project_ext(pr.h, prm, _lib.ptr(dst), rows, _lib.ptr(stats), _lib.ptr(count), 0.0, L, st))
+    elif scale is None:
+        _lib.check(lib.paa_project_rows(pr.h, prm, _lib.ptr(a), _lib.ptr(dst), rows, _lib.ptr(clean), L, st))
+    else:
+        _lib.check(lib.paa_project_rows_scaled(pr.h, prm, _lib.ptr(a), _lib.ptr(dst), rows, _lib.ptr(clean), L, _lib.ptr(scale), st))
+    torch.cuda.synchronize()
+    return hashlib.sha256(dst.cpu().numpy().tobytes()).hexdigest()
+
+
+def test_projection_bits_of_the_parent():
+    """Every case of pin_cases() leaves, bit for bit, what the commit named in the fixture left (tools/proj_parent_bits.py wrote it
+    from a build of that commit): giving the universal and the per-row projections one driver and one set of kernels changed no bit."""
+    with open(PIN) as f:
+        gold = json.load(f)
+    cases = pin_cases()
+    assert sorted(gold["cases"]) == sorted(cases)
+    differ = [name for name, case in cases.items() if pin_sha256(case) != gold["cases"][name]]
+    assert not differ, f"{len(differ)} of {len(cases)} cases differ from {gold['commit']}: {differ}"

@@ -6,14 +6,14 @@ import os
 import socket
 import subprocess
 import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
 import search_ref as SR
-from gpu_util import record_launches, rel_err
+from gpu_util import PROJ_ARGS, SCALES, branch as _branch, record_launches, rel_err, rows_input as _rows_input, \
+    scaled_args as _scaled_args, with_ as _with
 from oracle import pgd as opgd, projections as OP
 from oracle.gen_cases import cli_to_args
 from paa_amd import _lib, arch as A, runtime, synth
@@ -26,15 +26,6 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NORMS = ["l2", "linf", "snr", "tv", "fletcher_munson", "max_phon", "min_max_freqs+tv"]
-# Sizes under which, with the rows of test_project_rows_vs_oracle (amplitudes 1 / 0.1 / 0.01 / 1 / 0.1) and the scales below, the
-# 0.01 row (scale 0.8^3) is left alone and the others are rescaled, every row far from its projection's branch (chosen with the
-# oracle on the CPU: l2 norms 127 / 12.6 / 1.28 (L = 16000) and 155 / 15.6 / 1.56 (24001); TV(p) / TV(clean) 19.8 / 2.0 / 0.20; SNR
-# -26 / -6.1 / +13.9 dB; FM norms 2702 / 327 / 35.5 and 3288 / 402 / 43.2, at n_fft 512: 1975 / 237 / 25.1; max |p| 4.5 / 0.49 /
-# 0.043).  phon_reference_db 0 puts the contour where the two louder rows reach it.
-PROJ_ARGS = ["--l2_size", "5", "--linf_size", "0.2", "--snr_db", "5", "--tv_epsilon", "1", "--fm_epsilon", "100",
-             "--phon_reference_db", "0"]
-SCALES = np.array([1.0, 0.5, 0.8 ** 3, 0.01, 1.0], dtype=np.float32)
-SIZE_OF = {"l2": "l2_size", "linf": "linf_size", "tv": "tv_epsilon", "fletcher_munson": "fm_epsilon"}
 ROW_TOL = 2e-5          # the project's own bound for row projections (test_gpu_clip_attack.test_project_rows_vs_oracle)
 
 
@@ -43,48 +34,6 @@ def _fresh_projection_contexts():
     yield
     torch.cuda.synchronize()
     runtime._PROJ.clear()
-
-
-def _rows_input(rows, L, seed=5):
-    amp = np.array([10.0 ** -(r % 3) for r in range(rows)], dtype=np.float32)[:, None]
-    src = np.stack([synth.normal(synth.key_of(f"rowsrc{r}", seed), L) for r in range(rows)]).astype(np.float32) * amp
-    return src, synth.clean_audio(rows, L, seed=seed)
-
-
-def _with(args, **kw):
-    return types.SimpleNamespace(**{**vars(args), **kw})
-
-
-def _scaled_args(args, n, s):
-    """The oracle's args of norm ``n`` with its size tightened by s."""
-    s = float(s)
-    if n in SIZE_OF:
-        return _with(args, norm_type=n, **{SIZE_OF[n]: float(getattr(args, SIZE_OF[n])) * s})
-    if n == "snr":
-        return _with(args, norm_type=n, snr_db=float(args.snr_db) - 20.0 * np.log10(s))
-    if n == "max_phon":
-        return _with(args, norm_type=n, phon_reference_db=float(args.phon_reference_db) + 20.0 * np.log10(s))
-    return _with(args, norm_type=n)
-
-
-def _branch(n, p, clean, a):
-    """(rescaled?, distance from the branch) of the oracle's projection of one row under args ``a``: relative for l2 / tv / fm,
-    in dB for snr; None for the norms without a row-level branch."""
-    if n == "l2":
-        v, eps = float(p.norm()), a.l2_size
-    elif n == "tv":
-        v = float((p[:, 1:] - p[:, :-1]).abs().sum())
-        eps = a.tv_epsilon * float((clean[:, 1:] - clean[:, :-1]).abs().sum())
-    elif n == "fletcher_munson":
-        v, eps = float(OP.fm_weighted_norm(OP.compute_stft(p, a), a)), a.fm_epsilon
-    elif n == "snr":
-        cur = float(10 * torch.log10((clean ** 2).mean() / ((p ** 2).mean() + 1e-12)))
-        return cur < a.snr_db, abs(cur - a.snr_db) / 0.01 * 1e-4        # 0.01 dB counts as 1e-4 relative
-    elif n == "linf":
-        return bool((p.abs() > a.linf_size).any()), 1.0
-    else:
-        return None, 1.0
-    return v > eps, abs(v - eps) / eps
 
 
 def _scaled(pr, prm, src, dst, rows, clean, L, scale):
@@ -143,7 +92,7 @@ def test_scaled_rows_vs_oracle(norm):
 
 @pytest.mark.parametrize("norm", ["fletcher_munson", "max_phon"])
 def test_scaled_rows_vs_oracle_generic_frames(norm):
-    """n_fft 512, hop 128: the generic one-frame-per-workgroup kernels (k_fm_finalize<true>, the OP_PHON frame kernel)."""
+    """n_fft 512, hop 128: the generic one-frame-per-workgroup kernels (k_fm_finalize with one group per row, the OP_PHON frame kernel)."""
     args = cli_to_args(norm, PROJ_ARGS + ["--n_fft", "512", "--hop_length", "128", "--win_length", "512"])
     seen = set()
     _check_scaled_vs_oracle(norm, args, 16000, 3, seen)

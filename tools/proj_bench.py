@@ -3,6 +3,7 @@ launch-latency-bound — and in the batched mode (32, L), reported as algorithmi
 plus 4*B*L for the clean-batch statistic of snr / tv) against the 8 TB/s HBM peak.  Run on the GPU box:
 
     python tools/proj_bench.py                 # every norm, JSON list on the last line
+    python tools/proj_bench.py --rows-form     # every norm through paa_project_rows at (32, L): every row under its own statistic
     rocprofv3 --kernel-trace --stats ... -- python3 tools/proj_bench.py --spectral   # the three FFT norms only
 
 `roofline_block()` is what bench.py embeds as `roofline_fft`.
@@ -22,9 +23,10 @@ ALL = ("l2", "linf", "snr", "tv") + SPECTRAL
 HBM_PEAK_GBPS = 8000.0
 
 
-def measure(norms=ALL, rows_list=(1, 32), L=160000, B=32, iters=50, dev="cuda", verbose=True, in_place=False):
+def measure(norms=ALL, rows_list=(1, 32), L=160000, B=32, iters=50, dev="cuda", verbose=True, in_place=False, rows_form=False):
     """in_place=False times paa_project_to (reads p, writes a new tensor — what the reference's functions do, and the one
-    fused launch of the FFT norms); in_place=True times paa_project (what the PGD step calls on its resident p)."""
+    fused launch of the FFT norms); in_place=True times paa_project (what the PGD step calls on its resident p).
+    rows_form=True times paa_project_rows instead (rows <= B: clean clip r belongs to row r), in place or out of place."""
     lib = _lib.lib()
     out = []
     clean = torch.from_numpy(synth.clean_audio(B, L)).to(dev)
@@ -39,7 +41,9 @@ def measure(norms=ALL, rows_list=(1, 32), L=160000, B=32, iters=50, dev="cuda", 
             st = _lib.stream_ptr()
 
             def call():
-                if in_place:
+                if rows_form:
+                    _lib.check(lib.paa_project_rows(pr.h, prm, _lib.ptr(p), _lib.ptr(p if in_place else q), rows, _lib.ptr(clean), L, st))
+                elif in_place:
                     _lib.check(lib.paa_project(pr.h, prm, _lib.ptr(p), rows, _lib.ptr(clean), B, L, st))
                 else:
                     _lib.check(lib.paa_project_to(pr.h, prm, _lib.ptr(p), _lib.ptr(q), rows, _lib.ptr(clean), B, L, st))
@@ -54,7 +58,7 @@ def measure(norms=ALL, rows_list=(1, 32), L=160000, B=32, iters=50, dev="cuda", 
             torch.cuda.synchronize()
             us = e0.elapsed_time(e1) * 1e3 / iters
             nbytes = 8 * rows * L + (4 * B * L if norm in ("snr", "tv") else 0)
-            out.append(dict(norm=norm, rows=rows, in_place=in_place, us=round(us, 2), algorithmic_MB=round(nbytes / 1e6, 2),
+            out.append(dict(norm=norm, rows=rows, in_place=in_place, form="rows" if rows_form else "universal", us=round(us, 2), algorithmic_MB=round(nbytes / 1e6, 2),
                             GBps=round(nbytes / us / 1e3, 1), frac_of_8TBps=round(nbytes / us / 1e3 / HBM_PEAK_GBPS, 4)))
             if verbose:
                 print(out[-1], file=sys.stderr, flush=True)
@@ -86,6 +90,10 @@ def roofline_block(dev="cuda", L=160000, B=32):
 if __name__ == "__main__":
     if "--batch-only" in sys.argv:          # counter passes (tools/fft_pmc.sh): the (32, L) launches only
         res = measure(SPECTRAL, rows_list=(32,), iters=10)
+        print(json.dumps(res))
+        sys.exit(0)
+    if "--rows-form" in sys.argv:
+        res = measure(ALL, rows_list=(32,), rows_form=True) + measure(ALL, rows_list=(32,), rows_form=True, in_place=True)
         print(json.dumps(res))
         sys.exit(0)
     res = measure(SPECTRAL if "--spectral" in sys.argv else ALL)
