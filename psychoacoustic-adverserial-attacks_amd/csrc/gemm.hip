@@ -671,11 +671,12 @@ static int classify_epilogue(const paa_gemm_desc& d) {
     const bool mask = d.row_period > 0;
     switch (d.act) {
         case PAA_ACT_GELU:
-            return (d.bias && d.C_pre && d.aux_gate && il && !d.C && !d.aux && !d.residual && !d.res_ln_stats) ? EPK_GELU_FWD : EPK_GENERIC;
+            return (d.C_pre && d.aux_gate && il && !d.C && !d.aux && !d.residual && !d.res_ln_stats) ? EPK_GELU_FWD : EPK_GENERIC;
         case PAA_ACT_GELU_GRAD:
             if (!(d.aux && d.aux_gate && (il || planar) && !d.bias && !d.C && !d.C_pre && !d.residual && !d.res_ln_stats && !mask)) return EPK_GENERIC;
-#ifdef PAA_EXPERIMENTS      // tools/model_ab.py epik_la2 / epik_la4: the aux stream 2 / 4 row groups ahead
-            { const char* e = getenv("PAA_EPIK_AHEAD"); if (e && e[0] == '2') return EPK_GELU_GRAD_LA2; if (e && e[0] == '4') return EPK_GELU_GRAD_LA4; }
+#ifdef PAA_EXPERIMENTS      // tools/model_ab.py epik_la2 / epik_la4: the aux stream 2 / 4 row groups ahead; epik_la1: one, settled at the group's top
+            { const char* e = getenv("PAA_EPIK_AHEAD"); if (e && e[0] == '2') return EPK_GELU_GRAD_LA2; if (e && e[0] == '4') return EPK_GELU_GRAD_LA4;
+              if (e && e[0] == '1') return EPK_GELU_GRAD_LA1; }
 #endif
             return EPK_GELU_GRAD;
         case PAA_ACT_NONE:
@@ -892,11 +893,11 @@ paa_status gemm(const paa_gemm_desc& d, hipStream_t st) {
         else
 #endif
         if (ring >= 20) {
-            // Which kinds are TAKEN: GELU_FWD only — the one whose step A/B showed a gain; the others lengthen the K
-            // loop of their instantiations by more than their epilogues save and exist in -DPAA_EXPERIMENTS builds only, where
-            // PAA_EPIK_MASK (a bit set of 1 << EPK_*; tools/model_ab.py, tools/gemm_stamps.py, the tests) switches them on per launch.
+            // Which kinds are TAKEN: EPK_SHIPPED (gemm_dev.h) — those whose step A/B cleared the bar; the others exist in
+            // -DPAA_EXPERIMENTS builds only, where PAA_EPIK_MASK (a bit set of 1 << EPK_*; tools/model_ab.py, tools/gemm_stamps.py, the
+            // tests) switches kinds on per launch.
             g.kind = g_last_kind = classify_epilogue(d);
-            int taken = 1 << EPK_GELU_FWD;
+            int taken = EPK_SHIPPED;
 #ifdef PAA_EXPERIMENTS
             { const char* e = getenv("PAA_EPIK_MASK"); const int mask = e ? atoi(e) : 0; if (mask > 0) taken = mask; }
 #endif

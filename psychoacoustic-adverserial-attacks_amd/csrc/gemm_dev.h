@@ -25,7 +25,10 @@ struct GemmArgs {
 // one class of the model's fp32-parity products (classify_epilogue in gemm.hip maps a descriptor to a kind only on an exact
 // match).  Every kind runs the same arithmetic statements in the same order, so results are bit-identical to EpiGeneric.
 enum { EPK_GENERIC = 0, EPK_GELU_FWD = 1, EPK_GELU_GRAD = 2, EPK_RESID = 3, EPK_RESID_LN = 4, EPK_PLANES = 5,
-       EPK_GELU_GRAD_LA2 = 6, EPK_GELU_GRAD_LA4 = 7, EPK_COUNT = 8 };      // GELU_GRAD with 2 / 4 row groups of aux lookahead (experiment)
+       EPK_GELU_GRAD_LA2 = 6, EPK_GELU_GRAD_LA4 = 7, EPK_GELU_GRAD_LA1 = 8, EPK_COUNT = 9 };      // GELU_GRAD with 2 / 4 row groups of aux lookahead,
+                                                                                                   // and with one, settled at the top of its group (experiments)
+// the kinds the shipped library holds and takes: those whose step A/B cleared the bar (gemm_ring2.hip, launch_ring2_kind)
+constexpr int EPK_SHIPPED = (1 << EPK_GELU_FWD) | (1 << EPK_GELU_GRAD) | (1 << EPK_PLANES);
 enum { EPI_NO = 0, EPI_YES = 1, EPI_RT = 2 };
 template <int S>
 __device__ __forceinline__ bool epi_on(bool rt) {
@@ -38,41 +41,48 @@ struct EpiGeneric {      // everything from the descriptor
                          RES = EPI_RT, RLN = EPI_RT, PERIOD = EPI_RT, ACCUM = EPI_RT;
     static constexpr bool ALPHA1 = false;
     static constexpr int AHEAD = 1;          // row groups (8 rows) the extra operand stream is requested ahead of its use
+    static constexpr bool SETTLE_EARLY = false;     // true in GELU_GRAD only: the next row group's gate vectors are waited for in front of this group's stores (epilogue_vec, EARLY)
 };
-struct EpiGeluFwd {      // bias + GELU, f32 gate kept in C_pre, interleaved planes out (FFN up; a conv forward product when it has a bias); row mask either way
-    static constexpr int ACT = PAA_ACT_GELU, BIAS = EPI_YES, C = EPI_NO, CPRE = EPI_YES, X16 = EPI_NO, GATE = EPI_YES, CIL = EPI_YES, CB = EPI_NO, CBLO = EPI_NO,
+struct EpiGeluFwd {      // [bias +] GELU, f32 gate kept in C_pre, interleaved planes out (FFN up, the bias-free conv forward products); bias and row mask either way
+    static constexpr int ACT = PAA_ACT_GELU, BIAS = EPI_RT, C = EPI_NO, CPRE = EPI_YES, X16 = EPI_NO, GATE = EPI_YES, CIL = EPI_YES, CB = EPI_NO, CBLO = EPI_NO,
                          RES = EPI_NO, RLN = EPI_NO, PERIOD = EPI_RT, ACCUM = EPI_NO;
     static constexpr bool ALPHA1 = true;
     static constexpr int AHEAD = 1;
+    static constexpr bool SETTLE_EARLY = false;
 };
 struct EpiGeluGrad {     // acc x f32 gate, planes out — interleaved or planar hi + lo (conv dgrads, FFN-down dgrad); no bias registers
     static constexpr int ACT = PAA_ACT_GELU_GRAD, BIAS = EPI_NO, C = EPI_NO, CPRE = EPI_NO, X16 = EPI_NO, GATE = EPI_YES, CIL = EPI_RT, CB = EPI_YES, CBLO = EPI_YES,
                          RES = EPI_NO, RLN = EPI_NO, PERIOD = EPI_NO, ACCUM = EPI_NO;
     static constexpr bool ALPHA1 = true;
     static constexpr int AHEAD = 1;
+    static constexpr bool SETTLE_EARLY = true;
 };
 // experiment: the aux stream AH row groups ahead instead of one — 8 registers per group, which the folded kind has to spare
 template <int AH>
 struct EpiGeluGradAhead : EpiGeluGrad {
     static constexpr int AHEAD = AH;
+    static constexpr bool SETTLE_EARLY = false;      // every group's vectors waited for at its top (AH = 1: the form GELU_GRAD had before)
 };
 struct EpiResid {        // f32 C = acc + f32 residual (FFN-up dgrad, QKV dgrad)
     static constexpr int ACT = PAA_ACT_NONE, BIAS = EPI_NO, C = EPI_YES, CPRE = EPI_NO, X16 = EPI_NO, GATE = EPI_NO, CIL = EPI_NO, CB = EPI_NO, CBLO = EPI_NO,
                          RES = EPI_YES, RLN = EPI_NO, PERIOD = EPI_NO, ACCUM = EPI_NO;
     static constexpr bool ALPHA1 = true;
     static constexpr int AHEAD = 1;
+    static constexpr bool SETTLE_EARLY = false;
 };
 struct EpiResidLn {      // f32 C = acc + bias + LN(stored x) through res_ln_stats (out-proj, FFN down)
     static constexpr int ACT = PAA_ACT_NONE, BIAS = EPI_YES, C = EPI_YES, CPRE = EPI_NO, X16 = EPI_NO, GATE = EPI_NO, CIL = EPI_NO, CB = EPI_NO, CBLO = EPI_NO,
                          RES = EPI_YES, RLN = EPI_YES, PERIOD = EPI_NO, ACCUM = EPI_NO;
     static constexpr bool ALPHA1 = true;
     static constexpr int AHEAD = 1;
+    static constexpr bool SETTLE_EARLY = false;
 };
 struct EpiPlanes {       // planar hi + lo planes out, bias as a run-time flag (QKV forward, out-proj dgrad)
     static constexpr int ACT = PAA_ACT_NONE, BIAS = EPI_RT, C = EPI_NO, CPRE = EPI_NO, X16 = EPI_NO, GATE = EPI_NO, CIL = EPI_NO, CB = EPI_YES, CBLO = EPI_YES,
                          RES = EPI_NO, RLN = EPI_NO, PERIOD = EPI_NO, ACCUM = EPI_NO;
     static constexpr bool ALPHA1 = true;
     static constexpr int AHEAD = 1;
+    static constexpr bool SETTLE_EARLY = false;
 };
 
 // ---- persistent-grid sizing (host) ----------------------------------------------------------------
@@ -217,6 +227,19 @@ __device__ __forceinline__ float mul_unfused(float a, float b) {
     return a * b;
 }
 
+// "These registers are read here": an empty statement the compiler must have the registers' pending loads landed for.  The epilogue's
+// loads are issued under one bounds test and consumed under another; on the path where the consumer is skipped the compiler carried the
+// load as still pending out of the epilogue and into the next tile's K loop, where the first write of a register it had targeted — a DMA
+// offset, a fragment address — got an s_waitcnt vmcnt(0) on EVERY slab.  Touched on every path, a vector is waited
+// for once, where it is first used, with the count of the operations issued after it; vmcnt retires in issue order, so the loop-invariant
+// vectors loaded before it (bias, LayerNorm gain / bias) are covered by the same wait and cost none of their own.
+__device__ __forceinline__ void epi_landed(const uint4& v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
+template <int N>
+__device__ __forceinline__ void epi_landed(const float (&v)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) asm volatile("" ::"v"(v[k]));
+}
+
 // FAST: GELU / GELU' through the branch-free Abramowitz-Stegun erf (|error| <= 1.5e-7 absolute, paa_common.h) instead of
 // libm's erff.  Since round 2 BOTH precision modes take it in the vector epilogue: the split-bf16 products themselves
 // carry ~2^-16 = 1.5e-5 relative error, a hundred times the erf approximation's, and exact erff made the epilogue of the
@@ -263,7 +286,6 @@ __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&ac
     const unsigned co = (unsigned)row0 * ldc + (unsigned)col;
     const unsigned cob = cil ? (unsigned)row0 * 2u * ldc + (((unsigned)col >> 5) << 6) + ((unsigned)col & 31u) : co;      // bf16 result offset
     const unsigned ldcb = cil ? 2u * ldc : ldc;
-    const unsigned xo = (unsigned)row0 * ldx + (unsigned)col;
     float bv[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) bv[k] = 0.f;
@@ -296,26 +318,49 @@ __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&ac
     constexpr int NG = 4 * MI;                           // row groups of 8 rows: (i, g)
     constexpr int AH = T::AHEAD < NG ? T::AHEAD : NG - 1, NX = AH + 1;      // groups in flight; a ring of AH + 1 register sets (AH = 1: two)
     uint4 xv[NX][2];                                      // raw bits: 2 x float4, or one uint4 of 8 bf16 in [0]
+    // (mean, rstd) of this lane's row of the group (res_ln_stats): fetched with the residual where the kind has them for certain; the
+    // generic epilogue, at its register limit on 256-row tiles, reads them inside the group as it always did
+    constexpr bool RS_AHEAD = T::RLN == EPI_YES;
+    float rsv[NX][2];
+    // EARLY: GELU_GRAD — an extra stream for certain, one group ahead, and its only stores the planes at the END of a row group — waits for
+    // the next group's vectors in front of this group's stores instead of at the next group's top (see there).  Not RESID / RESID_LN:
+    // with their f32 halves held back to the group's end the same wait was built and measured (stamps): a group of
+    // plain adds has no arithmetic to hide the fetch under, the RESID epilogue went from 31 600 to 48 200 cycles.
+    constexpr bool EARLY = T::SETTLE_EARLY && AH == 1 && T::ACT == PAA_ACT_GELU_GRAD && T::X16 != EPI_RT && T::C == EPI_NO && T::CPRE == EPI_NO;
+    constexpr bool EX_ANY = EX_RT || T::ACT == PAA_ACT_GELU_GRAD || T::RES == EPI_YES;      // the kind may have an extra stream at all
 #pragma unroll
-    for (int u = 0; u < NX; ++u) { xv[u][0] = make_uint4(0u, 0u, 0u, 0u); xv[u][1] = xv[u][0]; }
-    auto fetch = [&](int grp, uint4 (&v2)[2]) {
-        const int dm = (grp >> 2) * 32 + (grp & 3) * 8;
-        if (col_ok && row0 + dm < d.M) {
-            const unsigned o = xo + (unsigned)dm * ldx;
-            if (has_ex) {
-                v2[0] = *reinterpret_cast<const uint4*>(ex + o);
-                v2[1] = *reinterpret_cast<const uint4*>(ex + o + 4u);
-            } else if (has_exh) {
-                v2[0] = *reinterpret_cast<const uint4*>(exh + o);
-            }
+    for (int u = 0; u < NX; ++u) { xv[u][0] = make_uint4(0u, 0u, 0u, 0u); xv[u][1] = xv[u][0]; rsv[u][0] = 0.f; rsv[u][1] = 1.f; }
+    auto fetch = [&](int grp, uint4 (&v2)[2], float (&r2)[2]) {
+        // No bounds test around the loads: a lane outside the matrix reads the last valid row / the first column group instead (its
+        // values reach no store).  Under a test the compiler branches around them, and a wait further down that cannot tell whether
+        // they were issued has to assume they were not — it comes out as vmcnt(0) instead of "all but the group after mine".
+        // Contract this relies on (gemm.h; gemm.hip admits the vector epilogue only with N, ld_aux, ld_res multiples of 8): the aux /
+        // residual array has M rows of at least 8 elements behind its base, so row M - 1 and columns 0..7 of any row exist.
+        const unsigned rowc = (unsigned)min(row0 + (grp >> 2) * 32 + (grp & 3) * 8, d.M - 1);
+        if (RS_AHEAD && rln) {
+            const float2 st = *reinterpret_cast<const float2*>(d.res_ln_stats + 2 * (size_t)rowc);
+            r2[0] = st.x; r2[1] = st.y;
+        }
+        const unsigned o = rowc * ldx + (col_ok ? (unsigned)col : 0u);
+        if (has_ex) {
+            v2[0] = *reinterpret_cast<const uint4*>(ex + o);
+            v2[1] = *reinterpret_cast<const uint4*>(ex + o + 4u);
+        } else if (has_exh) {
+            v2[0] = *reinterpret_cast<const uint4*>(exh + o);
         }
     };
 #pragma unroll
-    for (int a = 0; a < AH; ++a) fetch(a, xv[a]);
+    for (int a = 0; a < AH; ++a) fetch(a, xv[a], rsv[a]);
 #pragma unroll
     for (int grp = 0; grp < NG; ++grp) {
         const int i = grp >> 2, gq = grp & 3, u = grp % NX;
-        if (grp + AH < NG) fetch(grp + AH, xv[(grp + AH) % NX]);
+        if (grp + AH < NG) fetch(grp + AH, xv[(grp + AH) % NX], rsv[(grp + AH) % NX]);
+        if (grp == 0) {                                      // loop-invariant vectors: settled once, under the first group's wait
+            if constexpr (T::BIAS != EPI_NO) epi_landed(bv);
+            if constexpr (RLN_HELD && T::RLN != EPI_NO) { epi_landed(lg); epi_landed(lb); }
+        }
+        if constexpr (EX_ANY) { epi_landed(xv[u][0]); epi_landed(xv[u][1]); }
+        if constexpr (RS_AHEAD) epi_landed(rsv[u]);
         const int dm = i * 32 + gq * 8;
         const bool live = col_ok && row0 + dm < d.M;
         bool dead = false;
@@ -325,8 +370,8 @@ __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&ac
             dead = rem >= d.row_valid;
         }
         const unsigned ci = co + (unsigned)dm * ldc;
-        float2 rst = make_float2(0.f, 1.f);                  // (mean, rstd) of this lane's row of the group (res_ln_stats)
-        if (rln && live) rst = *reinterpret_cast<const float2*>(d.res_ln_stats + 2 * (size_t)(row0 + dm));
+        float2 rst = make_float2(rsv[u][0], rsv[u][1]);
+        if (!RS_AHEAD && rln && live) rst = *reinterpret_cast<const float2*>(d.res_ln_stats + 2 * (size_t)(row0 + dm));
         unsigned hp[4], lp[4], pp[4];                        // packed bf16 pairs of the 8 columns (result hi / lo, C_pre)
         // the two 4-column halves go through the math one after the other: with the tile's 64 accumulator registers
         // still live there is no room for eight interleaved GELU chains
@@ -412,6 +457,12 @@ __device__ __forceinline__ void epilogue_vec(const paa_gemm_desc& d, f32x16 (&ac
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
+        }
+        // Kinds whose only stores are the planes below: settle the NEXT group's vectors here, in front of this group's stores.  vmcnt
+        // retires in issue order, so at the top of the next group the same wait would also wait for the stores just issued; here the
+        // youngest thing it waits for is the fetch a whole group of arithmetic ago, the youngest store the previous group's.
+        if constexpr (EARLY) {
+            if (grp + 1 < NG) { epi_landed(xv[(grp + 1) % NX][0]); epi_landed(xv[(grp + 1) % NX][1]); }
         }
         if (has_cp16 && live && act == PAA_ACT_GELU) *reinterpret_cast<uint4*>(Cp16 + ci) = make_uint4(pp[0], pp[1], pp[2], pp[3]);
         if (has_cb && live) {

@@ -51,10 +51,34 @@ namespace {
 #ifndef PAA_R2_B_AUX
 #define PAA_R2_B_AUX 0
 #endif
-typedef __attribute__((address_space(1))) const void* gas_ptr2;
 typedef __attribute__((address_space(3))) void* las_ptr2;
+// The counted wait goes through the builtin, not through inline assembly: the compiler's own wait insertion reads it and knows what has
+// retired (gfx9 encoding: vmcnt in bits 3:0 and 15:14, expcnt 6:4 and lgkmcnt 11:8 left at "no wait").
 template <int N>
-__device__ __forceinline__ void wait_vmcnt2() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ void wait_vmcnt2() {
+    static_assert(N >= 0 && N < 64, "vmcnt is six bits");
+    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70);
+}
+// The operand DMA is a MUBUF `buffer_load ... lds`, not `global_load_lds`: the latter is FLAT-encoded, and while one is pending the compiler
+// takes vmcnt for out of order and answers EVERY vector-memory dependency — an epilogue vector, a reused address register in the K loop —
+// with s_waitcnt vmcnt(0), a drain of the whole operand pipeline and of the stores (tools/ring2_waits.py).
+// One DMA wave-instruction: 16 bytes per lane from base + voff + soff to the LDS row at dst.  `base` is wave-uniform (a tile's first row);
+// its halves go through v_readfirstlane so that the resource is in SGPRs whatever registers the compiler kept the pointer in — left to
+// itself it wraps every instruction whose resource it selected per plane, or whose slab offset a cursor holds in a VGPR, into a
+// waterfall loop; soff (wave-uniform too) goes the same way.  Raw buffer: stride 0, no swizzle,
+// num_records = 2^32 - 1 bytes, i.e. no range check of its own — the caller clamps rows, and voff + soff stays far below 2^32: at most
+// 255 rows x 4 lda bytes + one row of K (voff is an int, so lda < 2^21 elements).  Word 3 = 0x00020000: 32-bit data format on gfx9.
+// (Only this statement needs the device pass: the resource type does not exist in the host pass.)
+template <int AUX>
+__device__ __forceinline__ void ring2_dma(const void* base, las_ptr2 dst, int voff, int soff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned long long b = (unsigned long long)base;
+    const unsigned long long u = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+                                 (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc((void*)u, 0, -1, 0x00020000), dst, 16, voff,
+                                             __builtin_amdgcn_readfirstlane(soff), 0, AUX);
+#endif
+}
 
 // Diagnostic build -DPAA_R2_STAMP (tools/gemm_stamps.py): where a K slab's cycles go, per wave of workgroup 0 — s_memtime around the
 // counted vmcnt wait and around the barrier of every slab, summed per tile.
@@ -142,8 +166,10 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void k_gemm_ring2(GemmArgs g) {
         return false;
     };
     Cursor ca{(int)blockIdx.x, 0, 0, 0, 0, 0}, cb = ca;
-    const unsigned short* srcA[GA];
-    const unsigned short* srcB[GB];
+    // per operand: one base per plane, the requested tile's first row (wave-uniform, 64-bit), and per DMA wave-instruction one 32-bit
+    // byte offset of this lane's row and chunk inside the tile; the K slab is the instruction's scalar offset
+    const unsigned short *rsA[NPL], *rsB[NPL];
+    int offA[GA], offB[GB];
     auto set_srcA = [&](int t) {
         const Tile c = decode(t);
         const int64_t aoff = c.z1 * d.a_s1 + c.z2 * d.a_s2;
@@ -153,18 +179,24 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void k_gemm_ring2(GemmArgs g) {
         // (the lane id itself comes from v_mbcnt inside the statement: an opaque copy of `lane` would just move the spill to `lane`)
         int lane_o;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_o));
+        const int mlast = d.M - 1 - c.m0;                      // last valid row of the tile: rows past it re-read it
+        if constexpr (AIL) {
+            rsA[0] = reinterpret_cast<const unsigned short*>(d.A_il) + 2 * aoff + (int64_t)c.m0 * (2 * d.lda);
+        } else {
+            rsA[0] = reinterpret_cast<const unsigned short*>(d.A) + aoff + (int64_t)c.m0 * d.lda;
+            if constexpr (NPL == 2) rsA[1] = reinterpret_cast<const unsigned short*>(d.A_lo) + aoff + (int64_t)c.m0 * d.lda;
+        }
 #pragma unroll
         for (int i = 0; i < GA; ++i) {
             if constexpr (AIL) {
                 const int rr = (i * NW + wave) * RPIA + lane_o / CPRA;    // row of the slot (128-byte rows: chunks 0-3 hi, 4-7 lo)
                 const int ch = (lane_o % CPRA) ^ ((rr / RBRA) & (CPRA - 1));
-                srcA[i] = reinterpret_cast<const unsigned short*>(d.A_il) + 2 * aoff + (int64_t)min(c.m0 + rr, d.M - 1) * (2 * d.lda) + ch * 8;
+                offA[i] = min(rr, mlast) * (int)(4 * d.lda) + ch * 16;
             } else {
                 const int r = (i * NW + wave) * RPI + lane_o / CPR;       // row of the slot: hi rows, then lo rows
-                const int pl = r / BM, rr = r - pl * BM;
+                const int rr = r % BM;
                 const int ch = (lane_o % CPR) ^ ((rr / RBR) & (CPR - 1)); // global chunk that lands in slot lane % CPR
-                const unsigned short* A = reinterpret_cast<const unsigned short*>(pl ? d.A_lo : (const void*)d.A) + aoff;
-                srcA[i] = A + (int64_t)min(c.m0 + rr, d.M - 1) * d.lda + ch * 8;
+                offA[i] = min(rr, mlast) * (int)(2 * d.lda) + ch * 16;
             }
         }
     };
@@ -173,35 +205,42 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void k_gemm_ring2(GemmArgs g) {
         const int64_t boff = c.z1 * d.b_s1 + c.z2 * d.b_s2;
         int lane_o;                                            // as in set_srcA
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_o));
+        const int nlast = d.N - 1 - c.n0;
+        if constexpr (BIL) {
+            rsB[0] = reinterpret_cast<const unsigned short*>(d.B_il) + 2 * boff + (int64_t)c.n0 * (2 * d.ldb);
+        } else {
+            rsB[0] = reinterpret_cast<const unsigned short*>(d.B) + boff + (int64_t)c.n0 * d.ldb;
+            if constexpr (NPL == 2) rsB[1] = reinterpret_cast<const unsigned short*>(d.B_lo) + boff + (int64_t)c.n0 * d.ldb;
+        }
 #pragma unroll
         for (int i = 0; i < GB; ++i) {
             const int r = (i * NW + wave) * RPIB + lane_o / CPRB;
-            const int pl = BIL ? 0 : r / BN, p = r - pl * BN;
+            const int p = BIL ? r : r % BN;
             const int ch = (lane_o % CPRB) ^ ((p / RBRB) & (CPRB - 1));
             const int nl = (p & ~63) + 8 * ((p & 31) >> 2) + 4 * ((p >> 5) & 1) + (p & 3);      // row permutation of the vector epilogue
-            if constexpr (BIL) {
-                srcB[i] = reinterpret_cast<const unsigned short*>(d.B_il) + 2 * boff + (int64_t)min(c.n0 + nl, d.N - 1) * (2 * d.ldb) + ch * 8;
-            } else {
-                const unsigned short* B = reinterpret_cast<const unsigned short*>(pl ? d.B_lo : (const void*)d.B) + boff;
-                srcB[i] = B + (int64_t)min(c.n0 + nl, d.N - 1) * d.ldb + ch * 8;
-            }
+            offB[i] = min(nl, nlast) * (int)((BIL ? 4 : 2) * d.ldb) + ch * 16;
         }
     };
+    // plane of DMA wave-instruction i (planar slots: hi rows, then lo rows; a wave-instruction never straddles the two): wave-uniform
+    auto planeA = [&](int i) { return AIL ? 0 : ((i * NW + wave) * RPI) / BM; };
+    auto planeB = [&](int i) { return BIL ? 0 : ((i * NW + wave) * RPIB) / BN; };
     auto issueA = [&]() {                      // -> true if a slab was requested
         if (ca.t >= total) return false;
         unsigned char* st = smA + ca.slot * ASZ;
+        const int so = ca.slab * ((AIL ? 2 * BK : BK) * 2);
 #pragma unroll
         for (int i = 0; i < GA; ++i)
-            __builtin_amdgcn_global_load_lds((gas_ptr2)(srcA[i] + (int64_t)ca.slab * (AIL ? 2 * BK : BK)), (las_ptr2)(st + (i * NW + wave) * 1024), 16, 0, PAA_R2_A_AUX);
+            ring2_dma<PAA_R2_A_AUX>(NPL == 2 && planeA(i) ? rsA[NPL - 1] : rsA[0], (las_ptr2)(st + (i * NW + wave) * 1024), offA[i], so);
         if (advance(ca, NSTA) && ca.t < total) set_srcA(ca.t);
         return true;
     };
     auto issueB = [&]() {
         if (cb.t >= total) return;
         unsigned char* st = smB + cb.slot * BSZ;
+        const int so = cb.slab * ((BIL ? 2 * BK : BK) * 2);
 #pragma unroll
         for (int i = 0; i < GB; ++i)
-            __builtin_amdgcn_global_load_lds((gas_ptr2)(srcB[i] + (int64_t)cb.slab * (BIL ? 2 * BK : BK)), (las_ptr2)(st + (i * NW + wave) * 1024), 16, 0, PAA_R2_B_AUX);
+            ring2_dma<PAA_R2_B_AUX>(NPL == 2 && planeB(i) ? rsB[NPL - 1] : rsB[0], (las_ptr2)(st + (i * NW + wave) * 1024), offB[i], so);
         if (advance(cb, NSTB) && cb.t < total) set_srcB(cb.t);
     };
     set_srcA(ca.t);
@@ -396,31 +435,34 @@ void launch_ring2_il(const GemmArgs& g, hipStream_t st) {
     hipLaunchKernelGGL((k_gemm_ring2<BM, BN, BK, PREC, WR, WC, BIL, AIL, EPI>), dim3(blocks), dim3(WR * WC * 64), 0, st, g);
 }
 // Split mode with interleaved weights (what the model's fp32-parity products run): the epilogue kind gemm.hip's classifier found picks
-// the instantiation.  Only what the automatic selection reaches at the model's shapes is held: both GELU kinds on both tiles (FFN up /
-// FFN-down dgrad at N = 3072 and the conv stack take 256 x 256 or 192 x 256 by the round count), the f32-result and plane kinds on the
+// the instantiation.  Only what the automatic selection reaches at the model's shapes is held: both GELU kinds on both tiles (FFN up / the
+// conv forward products, FFN-down dgrad / the conv dgrads: 256 x 256 or 192 x 256 by the round count), the plane and f32-result kinds on the
 // 192-row tile (N = 768 / 2304).  Every other (tile, kind) pair runs the generic epilogue.
-// SHIPPED: GELU_FWD (FFN up: -0.15 .. -0.46 ms on the step, in-process A/Bs on two devices).  The other kinds shorten their epilogues too but
-// their instantiations run a LONGER K loop (stamps: 4550 -> 5480 cycles per slab for GELU_GRAD, 3650 -> 4620 for RESID), the step loses:
-// measured and rejected, held by -DPAA_EXPERIMENTS builds only, like the other rejected kernels.
+// SHIPPED (gemm_dev.h EPK_SHIPPED): GELU_FWD, GELU_GRAD, PLANES — each more than 3 x the spread of its in-process step A/B (DESIGN.md
+// section 9: -0.7, -0.58, -0.36 ms).  RESID and RESID_LN gain too (-0.12 .. -0.32 ms) but not by that margin; with the lookahead forms of
+// GELU_GRAD they are held by -DPAA_EXPERIMENTS builds only.
 template <int BM, int BN, int BK, int WR, int WC, bool AIL>
 void launch_ring2_kind(const GemmArgs& g, hipStream_t st) {
-    if (g.kind == EPK_GELU_FWD) { launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluFwd>(g, st); return; }
-#ifdef PAA_EXPERIMENTS
     switch (g.kind) {
+        case EPK_GELU_FWD: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluFwd>(g, st); return;
         case EPK_GELU_GRAD: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluGrad>(g, st); return;
+#ifdef PAA_EXPERIMENTS
         case EPK_GELU_GRAD_LA2: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluGradAhead<2>>(g, st); return;
         case EPK_GELU_GRAD_LA4: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluGradAhead<4>>(g, st); return;
+        case EPK_GELU_GRAD_LA1: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiGeluGradAhead<1>>(g, st); return;
+#endif
         default: break;
     }
     if constexpr (BM == 192) {
         switch (g.kind) {
+            case EPK_PLANES: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiPlanes>(g, st); return;
+#ifdef PAA_EXPERIMENTS
             case EPK_RESID: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiResid>(g, st); return;
             case EPK_RESID_LN: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiResidLn>(g, st); return;
-            case EPK_PLANES: launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL, EpiPlanes>(g, st); return;
+#endif
             default: break;
         }
     }
-#endif
     launch_ring2_il<BM, BN, BK, 1, WR, WC, true, AIL>(g, st);
 }
 template <int BM, int BN, int BK, int PREC, int WR, int WC>

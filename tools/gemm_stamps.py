@@ -14,7 +14,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("PAA_EXTRA_HIPCC_FLAGS", "-DPAA_EXPERIMENTS -DPAA_R2_STAMP")
-os.environ.setdefault("PAA_EPIK_MASK", "255")      # every epilogue kind taken (the library's default: GELU_FWD only)
+os.environ.setdefault("PAA_EPIK_MASK", "255")      # every epilogue kind taken (the library's default: gemm_dev.h EPK_SHIPPED)
 import numpy as np
 import torch
 
@@ -25,7 +25,7 @@ import gemm_ring_bench as G          # noqa: E402  (tools/ on sys.path through t
 
 L = G.L
 L.paa_debug_r2_stamps.argtypes = [C.POINTER(C.c_longlong)]
-KINDS = ["GENERIC", "GELU_FWD", "GELU_GRAD", "RESID", "RESID_LN", "PLANES", "GELU_GRAD_LA2", "GELU_GRAD_LA4"]      # gemm_dev.h EPK_*
+KINDS = ["GENERIC", "GELU_FWD", "GELU_GRAD", "RESID", "RESID_LN", "PLANES", "GELU_GRAD_LA2", "GELU_GRAD_LA4", "GELU_GRAD_LA1"]      # gemm_dev.h EPK_*
 buf = (C.c_longlong * (8 * 16 * 6))()
 for (nm, M, N, K, lda, ep) in G.SHAPES:
     if nm.endswith(" kg"):

@@ -8,8 +8,9 @@ Variants: default = the shipped behaviour; no_ail = planar activation planes ins
 read at model creation); no_c0dma = the register-staged conv0 GroupNorm backward instead of the LDS-DMA one (read per launch);
 no_rln = f32 LayerNorm outputs written and read back as residuals instead of LN(x) evaluated in the epilogue (gemm.h res_ln_stats);
 no_epik = the generic epilogue in every ring GEMM instead of the compile-time epilogue kinds (gemm_dev.h EPK_*; read per launch);
-default takes the GELU_FWD kind only, as the shipped library does; epik_all = every kind (PAA_EPIK_MASK, a bit set of 1 << EPK_*);
-epik_fwd_rln = GELU_FWD + RESID_LN; epik_la2 / epik_la4 = every kind, the GELU' one with its aux stream 2 / 4 row groups ahead.
+default takes the shipped kinds (gemm_dev.h EPK_SHIPPED: GELU_FWD, GELU_GRAD, PLANES); epik_fwd = GELU_FWD alone; epik_all = every kind (PAA_EPIK_MASK, a bit set of 1 << EPK_*);
+epik_fwd_rln = GELU_FWD + RESID_LN (epik_fwd_grad / epik_fwd_resid / epik_fwd_planes: GELU_FWD + that one kind; epik_no_resid / epik_no_rln: every kind but that one); epik_la2 / epik_la4 = every kind, the GELU' one with its aux stream 2 / 4 row groups ahead;
+epik_la1 = every kind, the GELU' one with its gate vectors waited for at the top of their row group instead of in front of the group before's stores.
 Variants that only change how a result is computed, not the result (no_epik), must leave p bit-identical to the first variant: asserted.
 """
 import json
@@ -29,11 +30,15 @@ from paa_amd.training_utils.pgd import PgdStepper
 
 
 VARIANTS = {"default": {}, "no_ail": {"PAA_NO_AIL": "1"}, "no_c0dma": {"PAA_NO_C0DMA": "1"}, "no_rln": {"PAA_NO_RLN": "1"},
-            "no_epik": {"PAA_NO_EPIK": "1"}, "epik_all": {"PAA_EPIK_MASK": "255"},
+            "no_epik": {"PAA_NO_EPIK": "1"}, "epik_all": {"PAA_EPIK_MASK": "255"}, "epik_fwd": {"PAA_EPIK_MASK": "2"},
             "epik_fwd_rln": {"PAA_EPIK_MASK": str((1 << 1) | (1 << 4))},
-            "epik_la2": {"PAA_EPIK_MASK": "255", "PAA_EPIK_AHEAD": "2"}, "epik_la4": {"PAA_EPIK_MASK": "255", "PAA_EPIK_AHEAD": "4"}}
+            "epik_fwd_grad": {"PAA_EPIK_MASK": str((1 << 1) | (1 << 2))}, "epik_fwd_resid": {"PAA_EPIK_MASK": str((1 << 1) | (1 << 3))},
+            "epik_fwd_planes": {"PAA_EPIK_MASK": str((1 << 1) | (1 << 5))},
+            "epik_no_resid": {"PAA_EPIK_MASK": str(255 & ~(1 << 3))}, "epik_no_rln": {"PAA_EPIK_MASK": str(255 & ~(1 << 4))},
+            "epik_la2": {"PAA_EPIK_MASK": "255", "PAA_EPIK_AHEAD": "2"}, "epik_la4": {"PAA_EPIK_MASK": "255", "PAA_EPIK_AHEAD": "4"},
+            "epik_la1": {"PAA_EPIK_MASK": "511", "PAA_EPIK_AHEAD": "1"}}
 SWITCHES = ("PAA_NO_AIL", "PAA_NO_C0DMA", "PAA_NO_RLN", "PAA_NO_EPIK", "PAA_EPIK_AHEAD", "PAA_EPIK_MASK")
-BIT_IDENTICAL = ("default", "no_epik", "epik_all", "epik_la2", "epik_la4", "epik_fwd_rln")      # arms that must compute the same bits
+BIT_IDENTICAL = ("default", "no_epik", "epik_all", "epik_la2", "epik_la4", "epik_fwd_rln", "epik_fwd_grad", "epik_fwd_resid", "epik_fwd_planes", "epik_no_resid", "epik_no_rln", "epik_fwd", "epik_la1")      # arms that must compute the same bits
 
 
 def set_env(name):
