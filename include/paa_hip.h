@@ -647,6 +647,40 @@ paa_status paa_align_margin(const float* logits, const int32_t* labels, const in
  * capturable (it changes what later calls launch).  PAA_ERR_ARG: a null model, another kind, kappa negative or not finite. */
 paa_status paa_model_set_loss(paa_model* m, int kind, float kappa);
 
+/* ------------------------------------------------------ feature-distance loss ----- */
+/* Cosine distance between the rows of two hidden states, with its cotangent.  For clip b with T_b = d_frames[b] frames (clamped to
+ * [1, T]; d_frames NULL: T) and the rows h = h[b][t], r = ref[b][t] of H floats:
+ *   d[b][t]  = 1 - <h, r> / (|h| |r|)                           loss[b] = sum_{t < T_b} d[b][t]
+ *   dh[b][t] = -grad_scale (r / |r| - cos h / |h|) / |h|        = grad_scale * d d[b][t] / d h
+ * A row with |h| <= 1e-8 or |r| <= 1e-8 has d = 1 and a zero cotangent row (the definition, not an approximation).  The three dot
+ * products are accumulated in float64 from the f32 inputs, d is rounded to f32 once, loss[b] is the float64 sum of those f32
+ * values in a fixed order, rounded once; no atomics, so two calls give the same bits.  h and dh are (B, h_rows, H) with
+ * h_rows >= T (the model's padded layout), ref is (B, ref_rows, H) with ref_rows >= T: rows [T, ..) of h and ref are not read, and
+ * rows t >= T_b and the pad rows of dh are zeros.  dist (B, T), nullable, receives d (zeros for t >= T_b); dh nullable: loss only.
+ * work: paa_feature_cos_work_floats(B, T) floats, 16-byte aligned.  PAA_ERR_ARG: a null h / ref / loss / work or a misaligned
+ * work buffer; PAA_ERR_SIZE: B or T < 1, a row count below T, H not a multiple of 4 in [4, 4096].  Additions to ABI 350. */
+int64_t paa_feature_cos_work_floats(int B, int T);
+paa_status paa_feature_cos(const float* h, int h_rows, const float* ref, int ref_rows, const int32_t* d_frames /* nullable */,
+                           int B, int T, int H, float grad_scale, float* loss /* B */, float* dist /* (B, T), nullable */,
+                           float* dh /* (B, h_rows, H), nullable */, float* work, void* stream);
+/* The last hidden state of the encoder (the output of its final LayerNorm, the operand of lm_head; HF
+ * Wav2Vec2Model(...).last_hidden_state in eval mode) of B clips -> d_out (B, T_e, H) f32, dense.  d_clean / d_p / p_rows / clamp
+ * as paa_model_forward_rows; under paa_model_set_lengths the rows t >= T_b are zeros.  The f32 copy of the hidden state lives in a
+ * buffer that is allocated at the first call of this entry or of paa_model_set_feature_loss, so a model that never uses either is
+ * launch for launch what it was; once the buffer exists the call is capturable.  The debug-read name "hfinal" reads that buffer
+ * in the model's padded layout. */
+paa_status paa_model_features(paa_model* m, const float* d_clean, const float* d_p /* nullable */, int p_rows, int clamp, int B,
+                              float* d_out /* (B, T_e, H) */, void* stream);
+/* d_ref (max_batch, T_e, H) f32 on the device switches the loss of every later paa_model_fwd_bwd{,_rows} call to the feature
+ * distance above between the call's last hidden state and d_ref (direction as grad_scale, the model's true clip lengths as
+ * d_frames); NULL switches it off and restores bits identical to a model that never had it set.  The pointer is KEPT and read on
+ * the stream, so a replayed graph follows the buffer.  While it is set: d_stats[0] = sum_b loss[b] (the per-clip values land where
+ * the CTC values do); d_labels may be NULL even with a gradient and is not read; the backward pass starts from dh at the hidden
+ * state, without the lm_head input-gradient product; the logits are produced as ever.  paa_model_forward{,_rows} keep reporting
+ * CTC.  Mutually exclusive with loss kind 1: each of the two setters returns PAA_ERR_ARG while the other loss is active.  Not
+ * itself capturable. */
+paa_status paa_model_set_feature_loss(paa_model* m, const float* d_ref);
+
 #ifdef __cplusplus
 }
 #endif

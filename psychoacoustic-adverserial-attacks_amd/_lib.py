@@ -175,6 +175,12 @@ _SIGS = {
     "paa_align_margin_work_floats": (C.c_int64, [C.c_int] * 4),
     "paa_align_margin": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float] * 2 + [C.c_void_p] * 7),
     "paa_model_set_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    # feature-distance loss
+    "paa_feature_cos_work_floats": (C.c_int64, [C.c_int] * 2),
+    "paa_feature_cos": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_float] +
+                        [C.c_void_p] * 5),
+    "paa_model_features": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 2),
+    "paa_model_set_feature_loss": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -17,6 +17,11 @@ successful delta (``found``, ``found_step``, ``bound_scale``, ``last_scale``), o
 the greedy decode is the target — the search's success test.  The step's ``loss`` then holds the margin loss; the records'
 ``clean_ctc`` / ``final_ctc`` stay CTC.
 
+``--loss_type feature`` (untargeted attacks): the steps push the encoder's last hidden state of x + delta away from that
+of the clean x (cosine distance per frame, no labels read).  The step's ``loss`` then holds the feature distance; the records'
+``clean_ctc`` / ``final_ctc`` stay CTC and the WER scoring is unchanged.  The run directory carries ``_feature`` and the results
+``"loss_type": "feature"``.
+
 ``--alpha_search qin`` (needs ``--masking_loss_alpha`` > 0, the weight every clip starts from) answers "how quiet, under
 the masking threshold, can this clip's successful perturbation be?": every clip carries its own weight of the masking loss, raised
 while its attack succeeds and lowered while it fails, and the record describes the successful delta with the smallest masking loss
@@ -163,7 +168,7 @@ def results_dict(records, args, length=None):
     """``length``: the clip length, for the chain's keys of a run with --eot_draws."""
     targeted = args.attack_mode == "targeted"
     out = {"norm_type": str(args.norm_type), "attack_mode": args.attack_mode, "optimizer_type": args.optimizer_type,
-           "split": args.split, "pgd_steps": int(args.pgd_steps)} | build.masking_time_extra(args)
+           "split": args.split, "pgd_steps": int(args.pgd_steps)} | build.masking_time_extra(args) | build.loss_extra(args)
     if modes.Modes.of(args).eot_on:
         out |= {"eot_draws": int(args.eot_draws), "eot_eval_draws": eot_eval_draws(args), **chain.results_extra(args, length)}
     return out | {"clips": list(records), "summary": summarize(records, targeted)}
@@ -222,10 +227,18 @@ def anneal_route(args, processor, texts):
     return ctx.anneal, canon, refs
 
 
+def _begin(stepper, x):
+    """What a stepper needs once per batch before its first step: under --loss_type feature the clean batch's reference features
+    (after the model's lengths are set)."""
+    if stepper.modes.feature_on:
+        stepper.feature_reset(x)
+
+
 def _run_search(stepper, delta, x, labels, steps, refs):
     """``steps`` steps of the bound search on one batch -> (reported delta, found_step, bound_scale, last_scale), the last three on
     the host.  The reported delta is ``best_b`` of a clip that fell, the last iterate of the others."""
     B = x.shape[0]
+    _begin(stepper, x)
     stepper.set_refs(refs)
     stepper.search_reset(B)
     stepper.stats_log.cursor.zero_()                                    # nobody reads the per-step log here: keep it from filling
@@ -243,6 +256,7 @@ def _run_anneal(stepper, delta, x, labels, steps, refs):
     """``steps`` steps of the alpha schedule on one batch -> (last iterate, best rows, and on the host: alpha_step, best_loss,
     best_alpha, last_alpha, l_b of the delta that entered)."""
     B = x.shape[0]
+    _begin(stepper, x)
     stepper.set_refs(refs)
     stepper.anneal_reset(B)
     stepper.stats_log.cursor.zero_()
@@ -334,6 +348,7 @@ def attack_batch(model, processor, args, x, texts, idx, interp, spl_thresh, step
             stepper.set_eot_clip(int(idx[0]))
             stepper.set_eot_step(0)
         if search is None:
+            _begin(stepper, x)
             for _ in range(steps):
                 stepper.step(delta.data, x, labels, want_logits=False)          # reads the model's length buffer, set above
             delta = delta.detach()
@@ -425,7 +440,7 @@ def main(args) -> int:
     if eot:
         chain.check_flags(args)
         eot_eval_draws(args)
-    modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS + modes.MARGIN, modes.Ctx(search=modes.SearchConfig.of(args)))
+    modes.check(modes.Modes.of(args), modes.SEARCH_FLAGS + modes.MARGIN + modes.FEATURE, modes.Ctx(search=modes.SearchConfig.of(args)))
     modes.check(modes.Modes.of(args), modes.ANNEAL_FLAGS, modes.anneal_ctx(args))
     modes.check(modes.Modes.of(args), modes.MASK_TIME)
     if not torch.cuda.is_available():
@@ -437,7 +452,7 @@ def main(args) -> int:
     args.attack_size_string = build.attack_size_string(args)
     root = getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"clips_{args.norm_type}_{args.attack_size_string}{build.masking_loss_suffix(args)}{build.masking_time_suffix(args)}"
+                                 f"clips_{args.norm_type}_{args.attack_size_string}{build.masking_loss_suffix(args)}{build.masking_time_suffix(args)}{build.loss_suffix(args)}"
                                  f"{chain.suffix(args) + f'_eot{int(args.eot_draws)}' if eot else ''}_"
                                  f"{args.attack_mode}_{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)

@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
-SOURCES = ["proj_kernels.hip", "spec_kernels.hip", "mask_kernels.hip", "gemm.hip", "gemm_ring.hip", "gemm_ring2.hip", "model_kernels.hip", "conv0_dgrad.hip", "attention.hip", "model.hip", "wer_kernels.hip", "place_kernels.hip", "rir_kernels.hip", "chan_kernels.hip", "search_kernels.hip", "eot_kernels.hip"]
+SOURCES = ["proj_kernels.hip", "spec_kernels.hip", "mask_kernels.hip", "gemm.hip", "gemm_ring.hip", "gemm_ring2.hip", "model_kernels.hip", "conv0_dgrad.hip", "attention.hip", "model.hip", "wer_kernels.hip", "place_kernels.hip", "rir_kernels.hip", "chan_kernels.hip", "search_kernels.hip", "eot_kernels.hip", "feat_kernels.hip"]
 # PAA_EXTRA_HIPCC_FLAGS: diagnostic builds of tools/ (e.g. "-DPAA_EXPERIMENTS -DPAA_ABL=3"); never set by __graft_entry__.build()
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wno-unused-value"] + os.environ.get("PAA_EXTRA_HIPCC_FLAGS", "").split()
 # a diagnostic build lives NEXT to the shipped library (its own file and object directory), never in its place

@@ -220,6 +220,11 @@ struct paa_model {
     // the loss of paa_model_fwd_bwd{,_rows} (paa_model_set_loss): 0 = CTC, 1 = alignment margin with `kappa`
     int loss_kind = 0;
     float kappa = 0.f;
+    // the feature-distance loss (paa_model_set_feature_loss): the caller's reference hidden states (device,
+    // (Bmax, T, H); null = off).  hfinal (M, H) is the f32 copy of the last hidden state and feat_work the d[b][t] of
+    // paa_feature_cos; both are allocated at the first use of the feature entries, never in paa_model_create
+    const float* feat_ref = nullptr;
+    float *hfinal = nullptr, *feat_work = nullptr;
 };
 
 static const float* find(paa_model* m, const std::string& n, int64_t numel, paa_status* st) {
@@ -243,6 +248,8 @@ static const float* find(paa_model* m, const std::string& n, int64_t numel, paa_
 extern "C" void paa_model_destroy(paa_model* m) {
     if (!m) return;
     if (m->arena) (void)hipFree(m->arena);
+    if (m->hfinal) (void)hipFree(m->hfinal);
+    if (m->feat_work) (void)hipFree(m->feat_work);
     delete m;
 }
 extern "C" int64_t paa_model_workspace_bytes(const paa_model* m) { return m ? m->arena_floats * 4 : 0; }
@@ -476,8 +483,10 @@ static paa_status linear(const paa_model* m, CBf x, CBf w, const float* bias, fl
     return gemm(d, st);
 }
 
-// p_ld: row stride of p (0 = the universal row, L = one row per clip)
-static paa_status forward(paa_model* m, const float* clean, const float* p, int p_ld, int clamp, int B, hipStream_t st) {
+// p_ld: row stride of p (0 = the universal row, L = one row per clip).  hf (nullable): the final LayerNorm also writes its output
+// in f32 there, (M, H); head = false stops before lm_head (paa_model_features)
+static paa_status forward(paa_model* m, const float* clean, const float* p, int p_ld, int clamp, int B, hipStream_t st,
+                          float* hf = nullptr, bool head = true) {
     const paa_arch& a = m->a;
     const int nc = a.n_conv, H = a.hidden, F = a.ffn, V = a.vocab, nh = a.heads, hd = H / nh, G = a.pos_groups, Hg = H / G;
     const int M = B * m->P, T = m->T, P = m->P, Tp = m->Tp;
@@ -590,7 +599,7 @@ static paa_status forward(paa_model* m, const float* clean, const float* p, int 
             if (m->rln) y1 = LnRef{e.ln1_in, e.st1, e.ln1_g, e.ln1_b};
             PAA_TRY(linear(m, ro(m->xbH), e.w1, e.b1, nullptr, m->factH, M, F, H, st, nullptr, PAA_ACT_GELU, e.fpre, nullptr, m->pre16));
             PAA_TRY(linear(m, ro(m->factH), e.w2, e.b2, e.ln2_in, NOBF, M, H, F, st, m->xb, 0, nullptr, nullptr, false, &y1));   // r2 = y1 + ffn
-            if (lastl) PAA_TRY(layernorm_fwd(e.ln2_in, e.ln2_g, e.ln2_b, nullptr, e.st2, M, H, a.ln_eps, m->xfinalH, NOBF, nullptr, st));
+            if (lastl) PAA_TRY(layernorm_fwd(e.ln2_in, e.ln2_g, e.ln2_b, hf, e.st2, M, H, a.ln_eps, m->xfinalH, NOBF, nullptr, st));
             else PAA_TRY(layernorm_fwd(e.ln2_in, e.ln2_g, e.ln2_b, m->xa, e.st2, M, H, a.ln_eps, m->xaH, NOBF, nullptr, st));
             if (m->rln) xln = LnRef{e.ln2_in, e.st2, e.ln2_g, e.ln2_b};
             x = m->xa; xH = ro(m->xaH);
@@ -604,19 +613,21 @@ static paa_status forward(paa_model* m, const float* clean, const float* p, int 
         }
     }
     if (a.stable_ln)
-        PAA_TRY(layernorm_fwd(x, m->enc_ln_g, m->enc_ln_b, nullptr, m->enc_stats, M, H, a.ln_eps, m->xfinalH, NOBF, nullptr, st));
-    PAA_TRY(linear(m, ro(m->xfinalH), m->lm_w, m->lm_b, m->logits, NOBF, M, V, H, st));
+        PAA_TRY(layernorm_fwd(x, m->enc_ln_g, m->enc_ln_b, hf, m->enc_stats, M, H, a.ln_eps, m->xfinalH, NOBF, nullptr, st));
+    if (head) PAA_TRY(linear(m, ro(m->xfinalH), m->lm_w, m->lm_b, m->logits, NOBF, M, V, H, st));
     return PAA_OK;
 }
 
-static paa_status backward(paa_model* m, const float* clean, const float* p, int p_ld, int clamp, int B, float* grad, hipStream_t st) {
+// from_hidden: the cotangent of the last hidden state is already in m->dxa (the feature-distance loss); else it is dlogits W_lm
+static paa_status backward(paa_model* m, const float* clean, const float* p, int p_ld, int clamp, int B, float* grad, hipStream_t st,
+                           bool from_hidden = false) {
     const paa_arch& a = m->a;
     const int nc = a.n_conv, H = a.hidden, F = a.ffn, V = a.vocab, nh = a.heads, hd = H / nh, G = a.pos_groups, Hg = H / G;
     const int M = B * m->P, T = m->T, P = m->P, Tp = m->Tp;
     const float scale = 1.0f / sqrtf((float)hd);
     float* dx = m->dxa;   Bf dxH = m->dxaH;      // gradient of the layer output (f32 + bf16 planes)
     float* dx2 = m->dxb;  Bf dx2H = m->dxbH;
-    PAA_TRY(linear(m, ro(m->dlogitsH), m->lm_wt, nullptr, dx, NOBF, M, H, V, st));
+    if (!from_hidden) PAA_TRY(linear(m, ro(m->dlogitsH), m->lm_wt, nullptr, dx, NOBF, M, H, V, st));
     if (a.stable_ln)
         PAA_TRY(layernorm_bwd(dx, m->final_in, m->enc_ln_g, m->enc_stats, nullptr, dx, dxH, M, H, st));
     for (int l = a.layers - 1; l >= 0; --l) {
@@ -757,18 +768,23 @@ static paa_status fwd_bwd_impl(paa_model* m, const float* d_clean, const float* 
     if (B < 1 || B > m->Bmax) PAA_FAIL(PAA_ERR_SIZE, "batch %d exceeds max_batch %d", B, m->Bmax);
     if (p_rows != 1 && p_rows != B) PAA_FAIL(PAA_ERR_SIZE, "p_rows=%d must be 1 or the batch %d", p_rows, B);
     if (d_labels && (S_max < 1 || S_max > m->S_cap)) PAA_FAIL(PAA_ERR_SIZE, "S_max=%d exceeds capacity %d", S_max, m->S_cap);
-    if (d_grad && !d_labels) PAA_FAIL(PAA_ERR_ARG, "gradient requested without labels");
+    const bool feat = m->feat_ref != nullptr;
+    if (d_grad && !d_labels && !feat) PAA_FAIL(PAA_ERR_ARG, "gradient requested without labels");
     hipStream_t st = (hipStream_t)stream;
     const int clamp = d_p ? 1 : 0;
     const int p_ld = p_rows > 1 ? m->L : 0;
-    PAA_TRY(forward(m, d_clean, d_p, p_ld, clamp, B, st));
+    PAA_TRY(forward(m, d_clean, d_p, p_ld, clamp, B, st, feat ? m->hfinal : nullptr));
     const int V = m->a.vocab;
     if (d_logits) {
         hipLaunchKernelGGL(k_copy_logits, dim3(std::min(cdiv((int64_t)B * m->T * V, 256), 2048)), dim3(256), 0, st,
                            (const float*)m->logits, d_logits, B, m->T, m->P, V, m->fr());
         PAA_LAUNCH_CHECK();
     }
-    if (d_labels) {
+    if (feat) {      // the feature distance to the reference, its cotangent straight into the backward pass's first operand
+        PAA_TRY(feature_cos(m->hfinal, m->P, m->feat_ref, m->T, m->fr(), B, m->T, m->a.hidden, (float)direction, m->nll, nullptr,
+                            d_grad ? m->dxa : nullptr, m->feat_work, st));
+        if (d_stats) PAA_TRY(sum_small(m->nll, B, d_stats, st));
+    } else if (d_labels) {
         if (m->loss_kind == 1)
             PAA_TRY(align_margin(m->logits, d_labels, m->fr(), B, m->T, m->P, V, S_max, m->a.blank, m->kappa, (float)direction, m->nll,
                                  nullptr, d_grad ? m->dlogits : nullptr, d_grad ? m->dlogitsH : NOBF, m->ctc_work, st));
@@ -777,7 +793,7 @@ static paa_status fwd_bwd_impl(paa_model* m, const float* d_clean, const float* 
                         d_grad ? m->dlogits : nullptr, d_grad ? m->dlogitsH : NOBF, m->ctc_work, st, m->fr()));
         if (d_stats) PAA_TRY(sum_small(m->nll, B, d_stats, st));
     }
-    if (d_grad) PAA_TRY(backward(m, d_clean, d_p, p_ld, clamp, B, d_grad, st));
+    if (d_grad) PAA_TRY(backward(m, d_clean, d_p, p_ld, clamp, B, d_grad, st, feat));
     return PAA_OK;
 }
 
@@ -852,8 +868,44 @@ extern "C" paa_status paa_model_set_loss(paa_model* m, int kind, float kappa) {
     if (kind != 0 && kind != 1) PAA_FAIL(PAA_ERR_ARG, "paa_model_set_loss: kind=%d must be 0 (CTC) or 1 (alignment margin)", kind);
     if (kind == 1 && !(kappa >= 0.f && kappa < INFINITY))
         PAA_FAIL(PAA_ERR_ARG, "paa_model_set_loss: kappa=%g must be finite and >= 0", (double)kappa);
+    if (kind == 1 && m->feat_ref)
+        PAA_FAIL(PAA_ERR_ARG, "paa_model_set_loss: the feature-distance loss is active (paa_model_set_feature_loss); switch it off first");
     m->loss_kind = kind;
     m->kappa = kind == 1 ? kappa : 0.f;
+    return PAA_OK;
+}
+// ---- the feature-distance loss and the hidden state's way out ----
+// the f32 hidden state and the loss's work buffer, allocated at the first use (hipMalloc: not inside a stream capture)
+static paa_status feature_buffers(paa_model* m) {
+    if (!m->hfinal) {
+        const size_t n = sizeof(float) * (size_t)m->M * m->a.hidden;
+        PAA_HIP(hipMalloc(&m->hfinal, n));
+        PAA_HIP(hipMemset(m->hfinal, 0, n));
+    }
+    if (!m->feat_work) PAA_HIP(hipMalloc(&m->feat_work, sizeof(float) * (size_t)feature_cos_work_floats(m->Bmax, m->T)));
+    return PAA_OK;
+}
+extern "C" paa_status paa_model_set_feature_loss(paa_model* m, const float* d_ref) {
+    if (!m) PAA_FAIL(PAA_ERR_ARG, "paa_model_set_feature_loss: null model");
+    if (d_ref && m->loss_kind == 1)
+        PAA_FAIL(PAA_ERR_ARG, "paa_model_set_feature_loss: the alignment-margin loss is active (paa_model_set_loss); switch it off first");
+    if (d_ref && ((uintptr_t)d_ref & 3)) PAA_FAIL(PAA_ERR_ARG, "paa_model_set_feature_loss: the reference is not a float array");
+    if (d_ref) PAA_TRY(feature_buffers(m));
+    m->feat_ref = d_ref;
+    return PAA_OK;
+}
+extern "C" paa_status paa_model_features(paa_model* m, const float* d_clean, const float* d_p, int p_rows, int clamp, int B,
+                                         float* d_out, void* stream) {
+    if (!m || !d_clean || !d_out) PAA_FAIL(PAA_ERR_ARG, "paa_model_features: null argument");
+    if (B < 1 || B > m->Bmax) PAA_FAIL(PAA_ERR_SIZE, "batch %d exceeds max_batch %d", B, m->Bmax);
+    if (p_rows != 1 && p_rows != B) PAA_FAIL(PAA_ERR_SIZE, "p_rows=%d must be 1 or the batch %d", p_rows, B);
+    PAA_TRY(feature_buffers(m));
+    hipStream_t st = (hipStream_t)stream;
+    PAA_TRY(forward(m, d_clean, d_p, p_rows > 1 ? m->L : 0, (d_p && clamp) ? 1 : 0, B, st, m->hfinal, false));
+    const int H = m->a.hidden;
+    hipLaunchKernelGGL(k_copy_logits, dim3(std::min(cdiv((int64_t)B * m->T * H, 256), 2048)), dim3(256), 0, st,
+                       (const float*)m->hfinal, d_out, B, m->T, m->P, H, m->fr());
+    PAA_LAUNCH_CHECK();
     return PAA_OK;
 }
 extern "C" paa_status paa_model_frame_counts(paa_model* m, int B, int32_t* d_out, void* stream) {
@@ -915,7 +967,7 @@ extern "C" void paa_abi_sizes(int32_t* out4) {
 // Test/diagnostic access to the internal activations (synchronous copy to host as f32; never on the step path).
 // conv{i}.pre (i < last, group-norm extractor) and L{l}.fpre return gelu'(pre) in both modes (see paa_model::pre16).
 // f32 buffers: conv{i}.pre, conv{last}.act, conv{i}.cv, h0, pos_pre, hsum, logits, dlogits, nll, G, gbuf0, dh0, dfn, dxa,
-//              gn_stats, L{l}.qkv|P|ln1_in|fpre|ln2_in.   bf16 planes (hi + lo summed): conv{i}.act (i < last), fn, xfinal.
+//              gn_stats, hfinal (once paa_model_features / paa_model_set_feature_loss allocated it), L{l}.qkv|P|ln1_in|fpre|ln2_in.   bf16 planes (hi + lo summed): conv{i}.act (i < last), fn, xfinal.
 extern "C" int64_t paa_model_debug_read(paa_model* m, const char* name, float* host, int64_t max_floats, int B) {
     if (!m || !name) return 0;
     const std::string n(name);
@@ -949,6 +1001,7 @@ extern "C" int64_t paa_model_debug_read(paa_model* m, const char* name, float* h
         else if (n == "pos_pre") { p = m->pos_pre; cnt = M * H; }
         else if (n == "hsum") { p = a.stable_ln ? m->enc[0].ln1_in : m->hsum; cnt = M * H; }
         else if (n == "xfinal") { pb = m->xfinalH; cnt = M * H; }
+        else if (n == "hfinal" && m->hfinal) { p = m->hfinal; cnt = M * H; }
         else if (n == "logits") { p = m->logits; cnt = M * V; }
         else if (n == "dlogits") { p = m->dlogits; cnt = M * V; }
         else if (n == "nll") { p = m->nll; cnt = B; }

@@ -91,6 +91,10 @@ paa_status align_margin(const float* logits, const int32_t* labels, const int32_
                         int blank, float kappa, float grad_scale, float* loss, int16_t* align, float* dlogits, Bf dlb, float* work,
                         hipStream_t st);
 paa_status sum_small(const float* x, int n, float* out, hipStream_t st);
+// feat_kernels.hip: the feature-distance loss (paa_feature_cos); h / dh have h_rows >= T rows per clip, ref has ref_rows >= T
+int64_t feature_cos_work_floats(int B, int T);
+paa_status feature_cos(const float* h, int h_rows, const float* ref, int ref_rows, const int32_t* frames, int B, int T, int H,
+                       float grad_scale, float* loss, float* dist, float* dh, float* work, hipStream_t st);
 
 // Fused attention (attention.hip): bf16 hi planes only (bf16 mode), head_dim 64.
 struct AttnArgs {

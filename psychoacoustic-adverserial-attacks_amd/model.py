@@ -199,6 +199,7 @@ class PaaModel:
         self._len_slots, self._len_events, self._len_i = None, None, 0      # pinned host slots behind its asynchronous copies
         self.lengths_on = False
         self.loss_kind, self.loss_kappa = 0, 0.0      # set_loss
+        self.feature_ref = None                       # set_feature_loss: the reference tensor the C side holds a pointer into
 
     @classmethod
     def from_hf(cls, hf_model, max_batch, length, dtype="bf16", device="cuda"):
@@ -265,6 +266,43 @@ class PaaModel:
         _lib.check(_lib.lib().paa_model_set_loss(self.h, k, float(kappa)))
         self.loss_kind, self.loss_kappa = k, float(kappa) if k else 0.0
 
+    def set_feature_loss(self, ref):
+        """The label-free feature-distance loss of every later ``fwd_bwd`` call: ``ref`` is a contiguous float32
+        (max_batch, T_e, H) tensor on the model's GPU — usually ``features(clean)`` written into a persistent buffer — and the
+        loss sum_b sum_{t < T_b} (1 - cos(h[b][t], ref[b][t])) between the call's last hidden state h and it; ``None`` switches
+        it off (bits as a model that never had it).  The model keeps the tensor and reads it on the stream at every call, so
+        a captured graph follows its contents.  ``fwd_bwd`` then takes ``labels=None``; ``direction`` scales the gradient (+1
+        pushes the features away from ``ref``, -1 pulls them towards it); ``forward`` keeps reporting CTC.  Mutually exclusive
+        with ``set_loss("margin")``.  Like ``set_lengths`` it changes what later calls launch."""
+        if ref is not None:
+            want = (self.max_batch, self.frames, self.arch.hidden_size)
+            if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or not ref.is_cuda or not ref.is_contiguous() \
+                    or tuple(ref.shape) != want:
+                raise ValueError(f"the feature reference must be a contiguous float32 {want} tensor on the GPU, got "
+                                 f"{getattr(ref, 'dtype', type(ref).__name__)} {tuple(getattr(ref, 'shape', ()))}")
+            if ref.device != self._weights.device:
+                raise RuntimeError(f"the feature reference lives on {ref.device}, the model on {self._weights.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().paa_model_set_feature_loss(self.h, _lib.ptr(ref)))
+        self.feature_ref = ref
+
+    def features(self, clean, p=None, clamp=True, out=None):
+        """The encoder's last hidden state (HF ``Wav2Vec2Model(...).last_hidden_state`` in eval mode: the output of the final
+        LayerNorm, the operand of lm_head) of ``clamp(clean + p, -1, 1)`` (``clamp=False``: the plain sum; ``p=None``: the clean
+        batch) -> (B, T_e, H) float32.  p is (1, L), (L,) or one row per clip (B, L).  Under ``set_lengths`` the rows t >= T_b are
+        zeros.  ``out``: a contiguous float32 tensor of at least B * T_e * H elements to write into (its first B rows)."""
+        clean, p, p_rows = self._checked(clean, p)
+        B = clean.shape[0]
+        n = B * self.frames * self.arch.hidden_size
+        if out is None:
+            out = torch.empty(B, self.frames, self.arch.hidden_size, dtype=torch.float32, device=clean.device)
+        elif out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.numel() < n:
+            raise ValueError(f"out must be a contiguous float32 GPU tensor of at least {n} elements")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().paa_model_features(self.h, _lib.ptr(clean), _lib.ptr(p), p_rows, int(bool(clamp)), B,
+                                                     _lib.ptr(out), _lib.stream_ptr()))
+        return out.view(-1)[:n].view(B, self.frames, self.arch.hidden_size)
+
     def frame_counts(self, B):
         """T_b of the current length buffer for the first B clips, as an int32 device tensor."""
         out = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -302,7 +340,8 @@ class PaaModel:
         """clean (B, L) f32 cuda; p (1, L), (L,), (B, L) (one row per clip) or None; labels (B, S) integer tensor,
         negatives = padding.  Returns dict(loss=0-d tensor, logits=(B, T_e, V) | None, grad=(1, L) | (B, L) | None,
         stats=(8,)); with a per-clip p the gradient has one row per clip (no sum over the clips).  ``loss`` is the CTC loss, or the
-        alignment-margin loss after ``set_loss("margin", kappa)``."""
+        alignment-margin loss after ``set_loss("margin", kappa)``, or the feature distance after ``set_feature_loss(ref)``, which
+        reads no labels: ``labels`` may then be None."""
         clean, p, p_rows = self._checked(clean, p)
         B, L = clean.shape
         dev = self.device

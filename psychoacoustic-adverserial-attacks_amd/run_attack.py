@@ -7,6 +7,11 @@ report :265-279) with its eight defects fixed, on the HIP path.
 With ``--loss_type margin`` (targeted attacks) the training step optimises the alignment-margin loss: the ``ctc`` field
 of the training scores (``train_ctc``, ``train_score`` / ``best_train_score`` in results.json) then holds the margin loss.  The
 evaluation scores stay CTC, so runs of either loss type compare.
+
+With ``--loss_type feature`` (untargeted attacks) the training step maximises the cosine distance between the encoder's
+last hidden state of the perturbed clips and that of the clean clips, recomputed from every step's batch; the ``ctc`` field of the
+training scores then holds that distance, results.json carries ``"loss_type": "feature"`` and the run directory ``_feature``.  The
+evaluation scores stay CTC and WER.
 """
 from __future__ import annotations
 
@@ -30,7 +35,7 @@ def main(args) -> int:
     # refusals before any collective, so that every rank raises
     m = modes.check(modes.Modes.of(args), ("route",), modes.Ctx(world))
     chain.check_flags(args)
-    modes.check(m, modes.MARGIN)
+    modes.check(m, modes.MARGIN + modes.FEATURE)
     mask_alpha = modes.check(m, modes.LENGTHS).alpha
     modes.check(m, modes.MASK_TIME)
     build.start_process_group(args, world)
@@ -58,6 +63,7 @@ def main(args) -> int:
     extra = {}          # results.json keys of the masking-threshold loss term: present only when masking_loss_alpha > 0
     place_extra = chain.results_extra(args, p.shape[-1])          # and those of placement, room responses and the playback channel
     place_extra = {**build.masking_time_extra(args), **place_extra}      # and of temporal masking
+    place_extra = {**build.loss_extra(args), **place_extra}              # and of the feature-distance loss
     extra.update(place_extra)
     goal = scoring_helpers.Objective(args.attack_mode)      # targeted: perturbed WER down; untargeted: perturbed CTC up
     best_epoch, no_improve, best_eval = -1, 0, goal.worst

@@ -170,6 +170,17 @@ def masking_loss_suffix(args) -> str:
     return f"_ml{alpha:g}" if alpha > 0 else ""
 
 
+def loss_suffix(args) -> str:
+    """Run-directory suffix of the feature-distance loss: "_feature" with --loss_type feature, else empty."""
+    return "_feature" if Modes.of(args).feature_on else ""
+
+
+def loss_extra(args) -> dict:
+    """The results key of the feature-distance loss: present only with the mode on.  The training field named ``ctc`` then holds
+    the feature distance; the evaluation fields stay CTC."""
+    return {"loss_type": "feature"} if Modes.of(args).feature_on else {}
+
+
 def masking_time_suffix(args) -> str:
     """Run-directory suffix of temporal masking: "_mt<post>-<pre>" when either time is > 0, else empty."""
     m = Modes.of(args)
@@ -192,7 +203,7 @@ def create_logger(args, logs_root=None):
     args.attack_size_string = attack_size_string(args)
     root = logs_root or getattr(args, "logs_dir", None) or os.path.join(os.getcwd(), "logs")
     args.save_dir = os.path.join(root, args.attack_mode, args.dataset,
-                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}{masking_time_suffix(args)}{chain.suffix(args)}_"
+                                 f"{args.norm_type}_{args.attack_size_string}{masking_loss_suffix(args)}{masking_time_suffix(args)}{loss_suffix(args)}{chain.suffix(args)}_"
                                  f"{args.attack_mode}_{args.optimizer_type}")
     os.makedirs(args.save_dir, exist_ok=True)
     logger = logging.getLogger("asr_attack")

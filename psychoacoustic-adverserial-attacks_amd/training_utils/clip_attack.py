@@ -48,7 +48,7 @@ import torch
 
 from .. import _lib, runtime, synth
 from . import chain, place
-from .modes import (EOT, LENGTHS, SEARCH_FLAGS, AnnealConfig, Ctx, Modes, SearchConfig, check,  # noqa: F401  (configs: re-exported)
+from .modes import (EOT, FEATURE, LENGTHS, SEARCH_FLAGS, AnnealConfig, Ctx, Modes, SearchConfig, check,  # noqa: F401  (configs: re-exported)
                     replace)
 from .pgd import N_STATS, ST_LOSS, PgdStepper, _StepperCore
 
@@ -70,7 +70,7 @@ class ClipStepper(_StepperCore):
         self.search, self.anneal = search, anneal
         self.G = int(check(Modes.of(args, eot_draws=eot_draws), ("eot_range",)).eot_draws)
         if self.G:       # refusals first: the new rules, then the links' own (masking, eager Adam) in the chain's order
-            check(Modes.of(args, eot_draws=self.G), EOT)
+            check(Modes.of(args, eot_draws=self.G), FEATURE + EOT)
             chain.check(args, int(length), int(length))
             if anneal is not None:
                 raise NotImplementedError("the alpha schedule needs the masking loss, which does not run through the playback chain")
@@ -118,11 +118,26 @@ class ClipStepper(_StepperCore):
             self.best_alpha = torch.zeros(nb, dtype=torch.float32, device=self.dev)    # ... the alpha it was optimised under
             self.best_step = torch.full((nb,), -1, dtype=torch.int32, device=self.dev)  # ... its step, -1: none kept yet
             self.anneal_step = torch.zeros(1, dtype=torch.int32, device=self.dev)      # device step counter
+        self._feat_batch = None          # feature_reset: (B, data_ptr of clean) the reference was computed for
         self.bound_scale = None
         if bound_scale is not None:
             if not (isinstance(bound_scale, torch.Tensor) and bound_scale.is_cuda):
                 raise ValueError("bound_scale must be a float32 (B) device tensor: the step reads it on the stream")
             self.bound_scale = _scale_dev(bound_scale, 1, self.dev)
+
+    def feature_reset(self, clean):
+        """A new batch under ``--loss_type feature``: the reference of the feature-distance loss, the clean batch's
+        last hidden state, is computed here — once per batch, outside any graph: the clips stay the same over a batch's steps —
+        into the persistent buffer every later step reads.  Call it before the first step (or ``capture``) of every batch, after
+        ``set_lengths``."""
+        if not self.modes.feature_on:
+            raise RuntimeError("the stepper was built without the feature-distance loss (--loss_type feature)")
+        clean = runtime.as_f32_cuda(clean, "clean_audio")
+        if clean.dim() != 2 or clean.shape[1] != self.L or clean.shape[0] > self.max_batch:
+            raise ValueError(f"clean_audio must be (B <= {self.max_batch}, {self.L}), got {tuple(clean.shape)}")
+        self._apply_loss()
+        self._feature_reference(clean)
+        self._feat_batch = int(clean.shape[0])
 
     def anneal_reset(self, B=None):
         """A new batch: alpha_rows = alpha0, best_loss = +inf, best_step = -1, step = 0 (stream-ordered fills, outside any graph).
@@ -207,7 +222,7 @@ class ClipStepper(_StepperCore):
 
     def _row_labels(self, labels, B):
         """Labels of B clips -> one row per draw (host-side repeat; rows already B * G are taken as they are)."""
-        if self.G > 1 and labels.shape[0] == B:
+        if self.G > 1 and labels is not None and labels.shape[0] == B:
             labels = labels.repeat_interleave(self.G, dim=0)
         return labels
 
@@ -250,6 +265,9 @@ class ClipStepper(_StepperCore):
 
     def _body(self, delta, clean, labels, want_logits=True, logits_out=None):
         lib, L, B = _lib.lib(), self.L, clean.shape[0]
+        if self.modes.feature_on and self._feat_batch != B:
+            raise RuntimeError("--loss_type feature: call feature_reset(clean) before the first step of every batch "
+                               f"(the reference holds {self._feat_batch} clips, the batch {B})")
         grad = self.grad_buf[: B * L].view(B, L)
         self.grad = grad
         G = self.G

@@ -76,7 +76,7 @@ class Modes:
     optimizer_type: str
     drift_ppm: float = 0.0         # --drift_ppm
     noise_snr: tuple = None        # --noise_snr_db (LO, HI), or None
-    loss_type: str = "ctc"         # --loss_type: "ctc" or "margin" (the alignment-margin loss)
+    loss_type: str = "ctc"         # --loss_type: "ctc", "margin" (the alignment-margin loss) or "feature" (§6q)
     kappa: float = 1.0             # --margin_kappa, in logits
     targeted: bool = False         # --attack_mode targeted
     eot_draws: int = 0             # --eot_draws G (attack_clips only): draws of the playback chain per clip, 0 = off
@@ -112,6 +112,7 @@ class Modes:
     masking = property(lambda m: m.masking_norm or m.alpha > 0)      # either pairs delta's frames with the clean clip's
     chan_why = property(lambda m: _chan_bad(m))
     margin_on = property(lambda m: m.loss_type == "margin")
+    feature_on = property(lambda m: m.loss_type == "feature")          # the label-free feature-distance loss
     eot_on = property(lambda m: isinstance(m.eot_draws, int) and not isinstance(m.eot_draws, bool) and m.eot_draws >= 1)
     link_on = property(lambda m: m.place_on or m.rir_on or m.chan_on)      # at least one link of the playback chain
     mask_time_on = property(lambda m: any(isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0 for v in (m.post_ms, m.pre_ms)))
@@ -293,6 +294,14 @@ RULES = {
     "mask_time_unused": Rule("mask_time_on", lambda m, c: not m.masking, ValueError,
                              "--masking_post_ms / --masking_pre_ms spread the masking threshold along time and need a consumer of it: "
                              "--norm_type masking or --masking_loss_alpha > 0"),
+    # the feature-distance loss
+    "feature_targeted": Rule("feature_on", lambda m, c: m.targeted, ValueError,
+                             "--loss_type feature does not run with --attack_mode targeted: that mode names a target phrase, not a "
+                             "target recording; targeted feature matching is available through the API (PaaModel.set_feature_loss "
+                             "with any reference and direction = -1)"),
+    "feature_eot": Rule("feature_on", lambda m, c: m.eot_on, NIE,
+                        "--loss_type feature is not implemented with --eot_draws: the model's rows are then draws of the playback "
+                        "chain on a zero clean operand, and the clean reference would need a chain of its own"),
     # per-clip perturbations through the playback chain
     "eot_range": Rule(None, lambda m, c: not (isinstance(m.eot_draws, int) and not isinstance(m.eot_draws, bool)
                                               and 0 <= m.eot_draws <= EOT_DRAWS_MAX), ValueError,
@@ -313,6 +322,7 @@ CHANNEL = CHANNEL_FLAGS + ("chan_eager",)
 LENGTHS = ("len_masking", "len_alpha", "len_place", "len_rir", "len_chan")
 SEARCH_FLAGS = ("search_range", "search_masking", "search_no_size")       # known from the flags alone
 MARGIN = ("margin_untargeted", "margin_kappa")                            # known from the flags alone
+FEATURE = ("feature_targeted", "feature_eot")                             # known from the flags alone
 EOT = ("eot_range", "eot_links", "eot_shift")                              # known from the flags alone
 MASK_TIME = ("mask_time_range", "mask_time_unused")                        # known from the flags alone
 SEARCH = SEARCH_FLAGS + ("search_route",)                                  # ... and once the vocabulary and the references are known

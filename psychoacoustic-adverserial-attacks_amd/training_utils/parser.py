@@ -125,10 +125,11 @@ def create_arg_parser():
     parser.add_argument('--noise_snr_db', type=_ranged("noise_snr_db", -20.0, 100.0, float), nargs=2, default=None,
                         metavar=("LO", "HI"), help='ambient noise: white Gaussian noise is added to every clip of every step at an '
                         'SNR uniform in [LO, HI] dB below the clean clip; absent = off')
-    # the loss of the device step (extension, DESIGN.md 6l); the default leaves the step as it is
-    parser.add_argument('--loss_type', type=str, choices=["ctc", "margin"], default="ctc",
+    # the loss of the device step (extension, DESIGN.md 6l, 6q); the default leaves the step as it is
+    parser.add_argument('--loss_type', type=str, choices=["ctc", "margin", "feature"], default="ctc",
                         help='margin (targeted attacks only): the alignment-margin loss, a hinge on the frames where the forced '
                              'alignment of the target does not yet win the argmax by --margin_kappa; zero exactly when the greedy '
-                             'decode is the target')
+                             'decode is the target.  feature (untargeted attacks only): the label-free cosine distance between '
+                             'the encoder\'s last hidden state of the perturbed clip and that of the clean clip')
     parser.add_argument('--margin_kappa', type=float, default=1.0, help='margin loss: the margin in logits, finite and >= 0')
     return parser

@@ -29,6 +29,12 @@
     margin loss (``loss_type`` = "margin",     inside paa_model_fwd_bwd{,_rows}: the alignment-margin      DESIGN.md §6l
     targeted only)                             sequence (paa_align_margin) in place of CTC; slot 0 of the
                                                stats then holds the margin loss
+    feature loss (``loss_type`` = "feature",   paa_model_features(clean) into the stepper's reference      DESIGN.md §6q
+    untargeted only)                           buffer: before paa_model_fwd_bwd in every universal step,
+                                               once per batch (``feature_reset``) for the per-clip step;
+                                               inside paa_model_fwd_bwd{,_rows}: paa_feature_cos in place
+                                               of the loss sequence, no lm_head input-gradient product;
+                                               slot 0 of the stats then holds the feature distance
     true clip lengths (``lengths=`` /          inside paa_model_fwd_bwd{,_rows}: frame counts, zeroed      DESIGN.md §6h
     ``set_lengths``)                           frames, masked compose / attention / CTC
                                                paa_model_frame_counts, paa_argmax_ids_len                 in place of paa_argmax_ids (device WER)
@@ -189,7 +195,7 @@ class _StepperCore:
     def __init__(self, model, args, length, interp, spl_thresh, optimizer, device_wer, canon, r_cap, log_cap, proj_rows, proj_len):
         self.model, self.args, self.L = model, args, int(length)
         self.dev = model.device
-        self.modes = modes.check(Modes.of(args), modes.MARGIN)
+        self.modes = modes.check(Modes.of(args), modes.MARGIN + modes.FEATURE)
         self.norms = list(self.modes.norms)
         for n in self.norms:
             if n not in _lib.NORM_IDS:
@@ -212,6 +218,11 @@ class _StepperCore:
         self._ring = _HostRing(4, self.dev) if (self.collective or optimizer is not None) else None
         self._init_masking_loss()
         self._init_device_wer(device_wer, canon, r_cap, log_cap)
+        # the feature-distance loss: the persistent reference buffer the model reads on the stream
+        self.feat_ref = None
+        if self.modes.feature_on:
+            self.feat_ref = torch.zeros(int(model.max_batch), int(model.frames), int(model.arch.hidden_size), dtype=torch.float32,
+                                        device=self.dev)
         self._apply_loss()
         self._lengths_captured = None        # capture() records whether the captured launch sequence runs in the length mode
 
@@ -219,11 +230,24 @@ class _StepperCore:
     def _apply_loss(self):
         """``--loss_type`` / ``--margin_kappa`` of ``args`` go to the model (``PaaModel.set_loss``; a host-side switch read by every
         later ``fwd_bwd``).  Steppers of different loss types may share a model: every eager step sets its own; a captured graph
-        keeps the launches it was captured with.  A model that never saw the margin loss is not touched."""
+        keeps the launches it was captured with.  A model that never saw the margin loss is not touched.  ``--loss_type feature``
+         hands the model this stepper's reference buffer (``PaaModel.set_feature_loss``); the two losses exclude
+        each other on the model, so the one that is going off is switched off first."""
         kind = 1 if self.modes.margin_on else 0
         kappa = float(self.modes.kappa) if kind else 0.0
+        ref = self.feat_ref if self.modes.feature_on else None
+        if ref is None and getattr(self.model, "feature_ref", None) is not None:
+            self.model.set_feature_loss(None)
         if (getattr(self.model, "loss_kind", 0), getattr(self.model, "loss_kappa", 0.0)) != (kind, kappa):
             self.model.set_loss(kind, kappa)
+        if ref is not None and getattr(self.model, "feature_ref", None) is not ref:
+            self.model.set_feature_loss(ref)
+
+    def _feature_reference(self, clean):
+        """The reference of the feature-distance loss: the clean batch's last hidden state into rows [0, B) of the persistent
+        buffer (``paa_model_features``: the forward pass up to the final LayerNorm and one copy; capturable once the model's f32
+        hidden buffer exists, which ``_apply_loss`` saw to).  Under true clip lengths the rows t >= T_b are zeros and not read."""
+        self.model.features(clean, None, out=self.feat_ref)
 
     # ---- true clip lengths ------------------------------------------------------------------------------------------
     @property
@@ -406,7 +430,7 @@ class _StepperCore:
         """What capture() does before it opens a graph: fixes the buffers the graph will point into (-> labels, logits_out), runs
         one eager step on a side stream, as torch's capture rules require, and undoes it — ``p``, the optimizer state and its
         step count, the log cursor (the log holds replayed steps only) and the leaf's ``_replay_state`` are as before."""
-        lab = labels.to(device=self.dev, dtype=torch.int32).contiguous()
+        lab = None if labels is None else labels.to(device=self.dev, dtype=torch.int32).contiguous()      # None: the feature loss only
         self._alpha_captured = self.mask_alpha > 0
         if lengths is not None:
             self.set_lengths(lengths)
@@ -571,6 +595,8 @@ class PgdStepper(_StepperCore):
         placed = self.place_on or self.rir_on or self.chan_on      # chain.PlaybackChain: one gradient row per clip, then their adjoint into self.grad
         if placed:
             out["grad"] = self.placed.placer.grad_rows[:B]
+        if self.modes.feature_on:          # the reference follows the step's clean batch: inside the launch sequence, so inside a graph
+            self._feature_reference(clean)
         r = self.model.fwd_bwd(clean, self.placed.rows(p, B, clean) if placed else p, labels, self.direction, want_grad=True,
                                want_logits=want_logits, out=out)
         if placed:

@@ -185,6 +185,8 @@ def train_epoch(args, train_data_loader, p: torch.Tensor, model, epoch: int, pro
             if p.dtype != torch.float32 or not p.is_cuda:
                 raise TypeError(f"the Adam branch needs a float32 perturbation on the GPU, got {p.dtype} on {p.device}")
             stepper._apply_loss()          # --loss_type, as the device step applies it
+            if stepper.modes.feature_on:
+                stepper._feature_reference(clean_audio)
             r = model.fwd_bwd(clean_audio, p.data, labels, stepper.direction)
             optimizer.zero_grad(set_to_none=True)
             p.grad = -r["grad"].view_as(p)          # gradient of (-direction * loss), train.py:170
